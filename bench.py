@@ -23,8 +23,14 @@ ensemble split over the ranks (configs[3], "1e6 packets, sharded
 torch.distributed environment launches `python -m torch.distributed.run
 --nproc-per-node N bench.py ...` as a CHILD process (never an exec) and
 relays its rank-0 line; under torch.distributed.run, WORLD_SIZE must equal
-`--gpus`.  At N = 1 the line also carries `strong_scaling_forecast`: the
-same workload timed at the shard sizes of 2/4/8 GPUs.
+`--gpus`.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line
+(`--dump-outputs DIR` also writes the packets the last timed step left).
+`--full` adds every other measurement to the same line: the FMA gather
+mode, the CPU baselines, the end-to-end driver steps (leapfrog and ode23)
+and, at N = 1, `strong_scaling_forecast` (the same workload timed at the
+shard sizes of 2/4/8 GPUs) and the driver-step forecasts.
 
 Prints ONE JSON line on rank 0.
 """
@@ -683,7 +689,51 @@ def parse_args(argv=None):
                     help="then this many driver steps with the reference's ode23 packet integrator (0: skip)")
     ap.add_argument("--gather", action="store_true",
                     help="after timing, gather all trajectories to rank 0 (one all_gather)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the metric, also run every other measurement: the FMA gather line, the scaling "
+                         "forecasts, the CPU baselines, the driver steps (leapfrog, forecasts, ode23); each keeps "
+                         "its own switch (--no-fma, --no-forecast, --no-cpu-baseline, --driver-steps 0, "
+                         "--ode23-steps 0).  Without --full only the metric is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the packets the timed path left (what swrt_packets_get returns "
+                         "after the last step) as DIR/x.npy and DIR/k.npy, float64 (see dump_outputs)")
     return ap.parse_args(argv)
+
+
+def metric_only(args):
+    """The switches of a run without --full: every measurement beside the
+    metric off (main applies this; the measuring functions themselves, which
+    tools/ call directly, are unchanged)."""
+    args.no_fma = args.no_forecast = args.no_cpu_baseline = True
+    args.driver_steps = args.ode23_steps = 0
+    return args
+
+
+DUMP_BYTES_MAX = 60_000_000  # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(out_dir, x, k, seed, rank=0, world=1):
+    """Write this rank's packets as <out_dir>/x.npy and k.npy ((N, 2) float64
+    each; x_rank<r>.npy, k_rank<r>.npy when there are several ranks).  Above
+    DUMP_BYTES_MAX in all, a fixed sample of rows instead: the sorted row
+    indices drawn without replacement from default_rng(seed), written beside
+    them as rows.npy (float64).  Returns what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    n = x.shape[0]
+    per_row = x[:1].nbytes + k[:1].nbytes if n else 1
+    info = {"dir": out_dir, "files": [f"x{sfx}.npy", f"k{sfx}.npy"], "rows": n, "of": n}
+    budget = DUMP_BYTES_MAX // world  # every rank writes its share
+    if n * per_row > budget:
+        m = budget // (per_row + 8)
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=m, replace=False))
+        x, k = x[rows], k[rows]
+        np.save(os.path.join(out_dir, f"rows{sfx}.npy"), rows.astype(np.float64))
+        info["files"].append(f"rows{sfx}.npy")
+        info["rows"] = int(m)
+    np.save(os.path.join(out_dir, f"x{sfx}.npy"), np.ascontiguousarray(x, dtype=np.float64))
+    np.save(os.path.join(out_dir, f"k{sfx}.npy"), np.ascontiguousarray(k, dtype=np.float64))
+    return info
 
 
 def _free_port():
@@ -830,6 +880,8 @@ def main(argv=None):
     cmd = launcher_cmd(args, argv, os.environ)
     if cmd is not None:
         sys.exit(relay(cmd))
+    if not args.full:
+        metric_only(args)
     _imports()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -868,6 +920,7 @@ def main(argv=None):
         elapsed = max_over_ranks(elapsed, backend=args.dist_backend)
     xg, kg = ctx.packets_get()
     finite = bool(np.isfinite(xg).all() and np.isfinite(kg).all())
+    dumped = dump_outputs(args.dump_outputs, xg, kg, args.seed, rank, world) if args.dump_outputs else None
     gathered = None
     if distributed and args.gather:
         # device-side gather of the trajectories (the frame writer's input): libswrt -> torch buffer -> all_gather
@@ -932,6 +985,8 @@ def main(argv=None):
     }
     if gathered is not None:
         out["gathered_finite"] = gathered
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if not args.no_fma and args.kernel in (0, 2) and args.gather_mode == 0:
         # the opt-in FMA gather (tolerance parity, tests/test_gpu_parity.py::test_fma_gather_mode_tolerance):
         # the same workload and packets, timed the same way; the headline stays bit-exact

@@ -53,6 +53,43 @@ def test_relay_forwards_only_the_metric_line(capfd):
     assert "noise" in err and "more" in err
 
 
+def test_plain_run_times_only_the_metric():
+    """Without --full every measurement beside the metric is switched off;
+    --full leaves each to its own switch."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None
+    bench.metric_only(a)
+    assert a.no_fma and a.no_forecast and a.no_cpu_baseline and a.driver_steps == 0 and a.ode23_steps == 0
+    assert a.steps == 7 and a.warmup == 2
+    f = bench.parse_args(["--full", "--no-fma"])
+    assert f.full and f.no_fma and not f.no_forecast and not f.no_cpu_baseline
+    assert f.driver_steps > 0 and f.ode23_steps > 0
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    import numpy as np
+    rng = np.random.default_rng(1)
+    x, k = rng.random((1000, 2)), rng.random((1000, 2))
+    info = bench.dump_outputs(str(tmp_path / "a"), x, k, seed=146)
+    assert info["rows"] == info["of"] == 1000 and sorted(info["files"]) == ["k.npy", "x.npy"]
+    xs, ks = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "k.npy")
+    assert xs.dtype == np.float64 and np.array_equal(xs, x) and np.array_equal(ks, k)
+    # above the size limit: the same seeded sample of rows every time, within the limit
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 4000)
+    for d in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / d), x, k, seed=146)
+    assert info["rows"] == 100 and info["of"] == 1000 and "rows.npy" in info["files"]
+    rows = np.load(tmp_path / "c" / "rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    r = rows.astype(np.int64)
+    assert np.all(np.diff(r) > 0) and np.array_equal(np.load(tmp_path / "c" / "x.npy"), x[r])
+    assert np.array_equal(np.load(tmp_path / "c" / "k.npy"), k[r])
+    assert sum(p.stat().st_size for p in (tmp_path / "c").iterdir()) <= 4000 + 3 * 128
+    # several ranks: one set of files each, the limit shared
+    info = bench.dump_outputs(str(tmp_path / "d"), x, k, seed=146, rank=1, world=2)
+    assert info["rows"] == 50 and sorted(info["files"]) == ["k_rank1.npy", "rows_rank1.npy", "x_rank1.npy"]
+
+
 @pytest.mark.parametrize("world", [1, 2, 8])
 def test_shards_cover_the_ensemble(world):
     from swraytracing_amd.dist import shard_range

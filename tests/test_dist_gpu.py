@@ -193,7 +193,8 @@ def test_bench_gpus_2_strong_scaling_line(tmp_path, driver):
     extra = ["--driver-steps", "0"] if driver == "none" else ["--driver-steps", "5", "--driver-warmup", "4",
                                                               "--driver-pde", "owner", "--owner-weight", "0.25",
                                                               "--no-forecast"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
+    # (--full: the driver step, and the FMA gather line, are measurements beside the metric)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--full",
                         "--steps", "3", "--warmup", "1", "--ode23-steps", "0", "--no-cpu-baseline", "--gather"] + extra,
                        cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=240)
     # every rank's own last lines (a failing rank's traceback sits mid-stream, before the launcher's report)

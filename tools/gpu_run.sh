@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU-box session: `bash tools/gpu_run.sh <step>...` with steps
 #   test   smoke + the GPU parity suite
-#   bench  the default bench.py line (what the driver runs)
+#   bench  the bench.py --full line (the metric and every measurement beside it)
 #   prof   the metric phase under rocprofv3 --kernel-trace --stats
 #   phase  per-workgroup phase stamps (build/var/phase*.so) at 1e6 and 1.25e5
 #   ab     bench A/B of build/var/*.so variants (AB_VARIANTS, AB_ARGS)
@@ -27,7 +27,7 @@ for s in "$@"; do
       step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
       step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     bench)
-      step bench 600 python bench.py ;;
+      step bench 600 python bench.py --full ;;
     prof)
       export TMPDIR=/tmp
       step prof 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv -- \

@@ -6,7 +6,7 @@ rc=$?; echo "pytest rc=$rc"; tail -4 $O/pytest.log
 [ $rc -ge 124 ] && exit $rc
 for i in 1 2; do
   for v in 1 0; do
-    SWRT_ODE23_CHAIN_FIRST=$v timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fma --no-forecast --driver-steps 0 --ode23-steps 16 > $O/ab_${v}_$i.log 2>&1 || exit 1
+    SWRT_ODE23_CHAIN_FIRST=$v timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fma --no-forecast --driver-steps 0 --ode23-steps 16 > $O/ab_${v}_$i.log 2>&1 || exit 1
     python3 -c "
 import json,sys
 d=json.loads([l for l in open('$O/ab_${v}_$i.log') if l.startswith('{')][-1])['driver_step_ode23']

@@ -6,7 +6,7 @@ rc=$?; echo "pytest rc=$rc"; tail -3 $O/pytest.log
 [ $rc -ge 124 ] && exit $rc
 for i in 1 2; do
   for v in 0 1; do
-    SWRT_EVENT_SYSTEM=$v timeout -k 10 400 python bench.py --no-cpu-baseline --no-fma --no-forecast > $O/ab_${v}_$i.log 2>&1 || exit 1
+    SWRT_EVENT_SYSTEM=$v timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-fma --no-forecast > $O/ab_${v}_$i.log 2>&1 || exit 1
     python3 -c "
 import json
 d=json.loads([l for l in open('$O/ab_${v}_$i.log') if l.startswith('{')][-1])

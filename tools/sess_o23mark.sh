@@ -7,7 +7,7 @@ rc=$?; echo "pytest rc=$rc"; tail -4 $O/pytest.log
 [ $rc -ge 124 ] && exit $rc
 for i in 1 2 3; do
   for v in 1 0; do
-    SWRT_ODE23_MARKERS=$v timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fma --no-forecast --driver-steps 0 --ode23-steps 32 > $O/ab_${v}_$i.log 2>&1 || exit 1
+    SWRT_ODE23_MARKERS=$v timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fma --no-forecast --driver-steps 0 --ode23-steps 32 > $O/ab_${v}_$i.log 2>&1 || exit 1
     python3 -c "
 import json,sys
 d=json.loads([l for l in open('$O/ab_${v}_$i.log') if l.startswith('{')][-1])['driver_step_ode23']
@@ -15,7 +15,7 @@ print('markers=$v run $i', round(d['ms_per_pde_step'],4), d.get('clock_ghz_obser
 "
   done
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/tr -o o -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fma --no-forecast --driver-steps 0 --ode23-steps 16 > $O/tr.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/tr -o o -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fma --no-forecast --driver-steps 0 --ode23-steps 16 > $O/tr.log 2>&1 || exit 1
 f=$(find $O/tr -name "o_kernel_trace.csv")
 python3 tools/ode23_timeline.py $f --interval -3 > $O/tl.txt 2>&1
 grep -h "interval_us" $O/tl.txt | tail -8

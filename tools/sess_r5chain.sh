@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 timeout -k 10 300 python -u -m pytest tests/test_gpu_ode23.py tests/test_gpu_qg.py -x -q \
   --timeout 120 --timeout-method thread > $O/pytest.log 2>&1; rc=$?; tail -3 $O/pytest.log
 [ $rc -ne 0 ] && exit $rc
-A="--steps 1 --warmup 0 --no-cpu-baseline --no-forecast --no-fma --driver-steps 0 --ode23-steps ${ODE23_STEPS:-13}"
+A="--full --steps 1 --warmup 0 --no-cpu-baseline --no-forecast --no-fma --driver-steps 0 --ode23-steps ${ODE23_STEPS:-13}"
 for i in 1 2 3; do
   for ch in 0 1; do
     SWRT_ODE23_CHAIN=$ch timeout -k 10 200 python bench.py $A > $O/chain${ch}_$i.json 2> $O/chain${ch}_$i.err || exit $?

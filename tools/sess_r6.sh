@@ -3,7 +3,7 @@
 #   new    the GPU tests this round added or changed (ode23 at scale, hook
 #          refusal, chain rewrite, lost packets, sharded drivers)
 #   test   smoke + the whole GPU suite (no -x: every failure reported)
-#   bench  the default bench.py line (what the driver runs)
+#   bench  the bench.py --full line (the metric and every measurement beside it)
 #   prof   the metric phase under rocprofv3 --kernel-trace --stats
 # Each GPU step has its own time limit; a crash or timeout (rc >= 124) ends
 # the session (no further GPU work); ordinary test failures do not.
@@ -31,7 +31,7 @@ for s in "$@"; do
       step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
       step pytest_gpu 1000 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread ;;
     bench)
-      step bench 700 python bench.py
+      step bench 700 python bench.py --full
       cp "$OUT/bench.log" "$OUT/bench_full.log"
       grep '^{' "$OUT/bench.log" > "$OUT/bench.json" || true ;;
     prof)
