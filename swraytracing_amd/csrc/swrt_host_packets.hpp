@@ -1,0 +1,593 @@
+// swrt_host_packets.hpp — host side of the packet steppers: the leapfrog
+// launches (per-packet and LDS-tiled, split over the packet streams and
+// checked by the hazard model), spatial re-binning, the advance loops and
+// the history buffers.  (debug_spin_kernel and debug_corrupt_count_kernel are
+// defined by swrt_api.hip before it includes this header.)
+#pragma once
+#include <algorithm>
+#include <vector>
+
+#include "swrt_ctx.hpp"
+#include "swrt_host_fields.hpp"
+#include "swrt_bin.hpp"
+#include "swrt_kernels.hpp"
+#include "swrt_tile.hpp"
+#include "swrt_share.hpp"
+#include "swrt_xka.hpp"
+#include "swrt_spectral.hpp"
+
+namespace {
+
+bool use_tile_kernel(const swrt_ctx* c) {
+  if (c->rebin_every <= 0) return false;
+  if (c->kernel == 2) return true;
+  return c->kernel == 0 && c->slot[0].nx >= 2 * kTile;
+}
+
+// the intervals of one multi-interval tile launch (swrt_advance_intervals)
+struct IvLaunch {
+  int nint;
+  FieldView views[kMaxIntervals + 1];
+  double dts[kMaxIntervals];
+  bool div_free;
+};
+
+// Launch a packet kernel on the context stream; inside a timed launch the
+// start/stop events take the kernel's own begin/end timestamps.
+template <typename F, typename... Args>
+void launch_k(swrt_ctx* c, F kernel, dim3 grid, dim3 block, Args... args) {
+  hipEvent_t stop = c->kev1 ? c->kev1 : (slot_events(c) ? c->use_ev.get() : nullptr);
+  hipExtLaunchKernelGGL(kernel, grid, block, 0, c->stream, c->kev0, stop, 0, args...);
+  c->tail_ev = stop;
+}
+
+// Ensembles below this run every tile launch on one stream: the split's
+// fork/join costs more than the overlap returns (profiles/r03_streams_ab:
+// 3e4 packets 3.0 vs 3.4e9, 1e4 at 256^2 1.8 vs 2.8e9; 6.25e4 even; 1.25e5
+// +3 %, 2.5e5 +6 %, 5e5 +4 %, 1e6 +3.7 %).
+constexpr int64_t kMultiStreamFrom = 65536;
+
+// The LDS-tiled launch of TileArgs t: one launch over every tile, or (two
+// packet streams) two part launches, each a share of every XCD band's tiles
+// (swrt_share.hpp), the second on the extra stream after everything queued
+// on the packet stream so far (this call's re-binning, memsets and history
+// growth).  A timed pair brackets the first part's start and the last
+// part's end.
+//
+// Hazard checker: the accesses of the launch's parts (part p on stream p),
+// forked from the packet stream when split, each over the band slots its
+// workgroups take — enumerated with the device's own mapping (share_slot),
+// so a launch whose tile-to-stream mapping differs from the previous
+// launch's is seen to touch the other stream's tiles.  Checked on a copy of
+// the checker state, committed only if every access is ordered: a hazard
+// refuses the launch before anything is queued.
+int hz_tile_launch(swrt_ctx* c, const TileArgs& t, const TileShare* parts, int nparts, bool zero_counts,
+                   bool fork = true) {
+  HazardChecker h = c->hz;
+  if (zero_counts) {  // the next-binning counts' memset, on the packet stream before the parts
+    const uint64_t tm = h.op(0);
+    if (!h.access(0, tm, t.next_counts, kHzWrite, HzRegion::all(), "the next-binning counts' memset"))
+      return fail(c, SWRT_ERR_STATE, h.err);
+  }
+  if (nparts > 1 && fork) {
+    h.record(c->fork_ev.get(), 0);
+    for (int i = 1; i < nparts; ++i) h.wait(i, c->fork_ev.get());
+  }
+  const StepArgs& a = t.s;
+  for (int p = 0; p < nparts; ++p) {
+    const uint64_t tp = h.op(p);
+    const HzRegion r = HzRegion::of_share(h.epoch, parts[p]);
+    const char* what = t.src ? "a part of the sort launch after a re-binning" : "a part launch";
+    // the sort launch after an indirect re-binning gathers its input through
+    // src_idx from any slot of the input buffers
+    const HzRegion rin = t.src ? HzRegion::all() : r;
+    bool ok = h.access(p, tp, a.x, kHzRead, rin, what) && h.access(p, tp, a.k, kHzRead, rin, what) &&
+              h.access(p, tp, a.perm, kHzRead, rin, what) && h.access(p, tp, t.src, kHzRead, r, what) &&
+              h.access(p, tp, t.starts, kHzRead, HzRegion::all(), what) &&
+              h.access(p, tp, t.order, kHzRead, HzRegion::all(), what) &&
+              h.access(p, tp, t.x_out, kHzWrite, r, what) && h.access(p, tp, t.k_out, kHzWrite, r, what) &&
+              h.access(p, tp, t.perm_out, kHzWrite, r, what) &&
+              h.access(p, tp, t.next_keys, kHzWrite, r, what) &&
+              h.access(p, tp, t.next_counts, kHzAtomic, HzRegion::all(), what) &&
+              h.access(p, tp, a.hist_x, kHzWrite, r, what) && h.access(p, tp, a.hist_k, kHzWrite, r, what);
+    if (!ok) return fail(c, SWRT_ERR_STATE, h.err);
+  }
+  c->hz = std::move(h);
+  return SWRT_OK;
+}
+
+// zero_counts: clear t.next_counts (the next binning's counts) first, on the
+// packet stream — after the hazard check, so a refused launch queues nothing.
+template <typename F>
+int launch_tiles(swrt_ctx* c, F kernel, int nt, TileArgs t, bool zero_counts) {
+  const int ntiles = t.ntx * t.ntx;
+  const int S = c->n >= kMultiStreamFrom ? c->packet_streams : 1;
+  // test-only (SWRT_DEBUG_SHARE_SKEW): the launch that ends a re-binning
+  // cycle takes an uneven share — a mapping that differs from the previous
+  // launch's, round 4's race; only ever run with the checker on, which
+  // refuses it (swrt_debug_set enforces that)
+  const bool skew = c->dbg.share_skew && t.next_keys != nullptr;
+  if (skew && !c->hz.on) return fail(c, SWRT_ERR_STATE, "the skewed share runs only under the hazard checker");
+  const bool multi = S == 2 && c->stream == c->stream0.get() && c->sx[0].get() != nullptr &&
+                     (skew ? ntiles % 8 == 0 && ntiles / 8 >= 3 : ntiles % 16 == 0);
+  if (!multi) {
+    // one launch over every tile on the packet stream: it reads and writes
+    // packets that the extra stream's part launch of an earlier call may
+    // still be writing
+    t.sh = TileShare{ntiles, -1, 1, kShareEven};
+    HIPCHK_RC(join_b(c));
+    if (c->hz.on) HIPCHK_RC(hz_tile_launch(c, t, &t.sh, 1, zero_counts));
+    if (zero_counts) HIPCHK(c, hipMemsetAsync(t.next_counts, 0, sizeof(int) * ntiles, c->stream));
+    launch_k(c, kernel, dim3((unsigned)share_grid(t.sh)), dim3(nt), t);
+    c->s0_dirty = true;  // every tile on the packet stream
+    return SWRT_OK;
+  }
+  const TileShare sh[2] = {TileShare{ntiles, 0, 2, skew ? kShareSkew : kShareEven},
+                           TileShare{ntiles, 1, 2, skew ? kShareSkew : kShareEven}};
+  // the fork: only when the packet stream has had other work since the last
+  // split launch (s0_dirty), the counts' memset included; the hazard checker
+  // models exactly the orderings the launch queues
+  const bool fork = c->s0_dirty || zero_counts || skew;
+  if (c->hz.on) HIPCHK_RC(hz_tile_launch(c, t, sh, 2, zero_counts, fork));
+  if (zero_counts) HIPCHK(c, hipMemsetAsync(t.next_counts, 0, sizeof(int) * ntiles, c->stream));
+  // Part p takes the same slots at every launch of a binning (the product
+  // rule, kShareEven): a stream's consecutive part launches own the same
+  // tiles, so stream order alone orders them, and stream 0's next launch may
+  // start while stream 1's previous one still runs.  A launch with another
+  // mapping races it unless joined first — the checker, which enumerates the
+  // slots each part takes, refuses it (round 4's hang, profiles/r04_stream_split).
+  if (fork) {
+    HIPCHK(c, hipEventRecord(c->fork_ev.get(), c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->sx[0].get(), c->fork_ev.get(), 0));
+  }
+  c->s0_dirty = false;
+  t.sh = sh[0];
+  hipExtLaunchKernelGGL(kernel, dim3((unsigned)share_grid(sh[0])), dim3(nt), 0, c->stream, c->kev0, nullptr, 0, t);
+  if (c->dbg.spin_us > 0)
+    hipLaunchKernelGGL(debug_spin_kernel, dim3(1), dim3(64), 0, c->sx[0].get(), (c->dbg.spin_us + 3) / 4);
+  t.sh = sh[1];
+  hipExtLaunchKernelGGL(kernel, dim3((unsigned)share_grid(sh[1])), dim3(nt), 0, c->sx[0].get(), nullptr, c->kev1, 0, t);
+  c->b_pending = 1;
+  c->tail_ev = nullptr;  // slot uses are marked after the join (swrt_advance)
+  return SWRT_OK;
+}
+
+// Longest-first tile order of the LDS-tiled launches, written by every
+// re-binning's scan (bin_scan_kernel) beside the tile starts.
+int* tile_order_of(swrt_ctx* c) { return c->bins.get() + 3 * kMaxBins + 1; }
+
+// The sparse-tile launch shape (kSparseThreads threads, prefetch depth
+// kSparsePrefetch) for the two-snapshot five-sum launches over `ntiles` tiles.
+bool sparse_tiles(const swrt_ctx* c, int64_t ntiles) {
+  if (c->sparse_mode == 1) return false;
+  if (c->sparse_mode == 2) return true;
+  return c->n < (int64_t)kSparseBelow * ntiles;
+}
+
+// Threads per workgroup of the LDS-tiled leapfrog launch over `ntiles` tiles
+// of snapshots that are (v5) two divergence-free slots: ONE decision for the
+// launch (tile_launch) and for the re-binning's longest-first tile order,
+// which ranks tiles by the rounds of this many lanes their workgroup runs.
+int tile_threads(const swrt_ctx* c, bool v5_two, int64_t ntiles) {
+  return v5_two && sparse_tiles(c, ntiles) ? kSparseThreads : kTileThreads;
+}
+
+// slots sa .. sa+nslots-1 are two divergence-free snapshots (the five-sum kernels)
+bool two_v5(const swrt_ctx* c, int nslots, int sa) {
+  bool v5 = nslots >= 2;
+  for (int i = 0; i < nslots && v5; ++i) v5 = c->slot[sa + i].div_free;
+  return v5;
+}
+
+int tile_cells(const swrt_ctx* c, int64_t nx) {
+  if (use_tile_kernel(c)) return kTile;
+  if (c->tile > 0) return (int)std::min<int64_t>(c->tile, nx);
+  // default: 8x8-cell tiles, coarser on big grids so bins stay <= 4096
+  int t = 8;
+  while ((nx + t - 1) / t > 64) t *= 2;
+  return t;
+}
+
+// the per-packet leapfrog kernel blending `nslots` snapshots
+using LeapKernel = void (*)(StepArgs);
+LeapKernel leap_kernel(int nslots) { return nslots == 2 ? leapfrog_kernel<true> : leapfrog_kernel<false>; }
+
+// Counting-sort the packets by spatial tile of slot 0's grid (swrt_bin.hpp).
+// indirect: only build the source index of the binned order (c->src_idx);
+// the tile launch that follows reads through it and writes the packets in
+// binned order (saves moving 36 B per packet twice).  Callers other than the
+// leapfrog loop need the packets moved (indirect = false).  lanes: the
+// workgroup width of the launches this binning serves (tile_threads), by
+// which the scan ranks the tile order.
+int rebin(swrt_ctx* c, bool indirect, int tile = 0, int lanes = kTileThreads) {
+  if (int rc = join_b(c)) return rc;  // the second stream's half launches wrote packets this pass reads
+  c->s0_dirty = true;  // a new binning: the next split launch forks
+  const Slot& s = c->slot[0];
+  const FieldView v = view_of(s);
+  BinGeom g;
+  g.dx = v.dx; g.px = v.px; g.py = v.py; g.inv_px = v.inv_px; g.inv_py = v.inv_py; g.inv_dx = v.inv_dx;
+  g.nx = v.nx;
+  g.tile = tile > 0 ? tile : tile_cells(c, s.nx);
+  g.ntx = (int)((s.nx + g.tile - 1) / g.tile);
+  const int nbins = g.ntx * g.ntx;
+  if (nbins > kMaxBins) return fail(c, SWRT_ERR_ARG, "too many spatial bins (raise tile size)");
+  const int64_t n = c->n;
+  const unsigned grid = nblocks(n, 256 * kBinPerThread);
+  const bool keys_valid = c->keys_fresh && c->bin_valid && nbins == c->nbins && c->key_nx == v.nx && c->key_dx == v.dx;
+  if (c->hz.on) {  // count, scan and scatter on the packet stream
+    HazardChecker& h = c->hz;
+    const uint64_t t = h.op(0);
+    const char* what = "a re-binning";
+    const HzRegion all = HzRegion::all();
+    bool ok = h.access(0, t, c->dx.get(), kHzRead, all, what) && h.access(0, t, c->dk.get(), kHzRead, all, what) &&
+              h.access(0, t, c->perm.get(), kHzRead, all, what) &&
+              h.access(0, t, c->keys.get(), keys_valid ? kHzRead : kHzWrite, all, what) &&
+              h.access(0, t, c->bins.get(), kHzWrite, all, what) && h.access(0, t, c->bins.get() + kMaxBins, kHzWrite,
+                                                                             all, what) &&
+              h.access(0, t, c->bins.get() + 2 * kMaxBins, kHzWrite, all, what) &&
+              h.access(0, t, tile_order_of(c), kHzWrite, all, what);
+    if (indirect)
+      ok = ok && h.access(0, t, c->src_idx.get(), kHzWrite, all, what);
+    else
+      ok = ok && h.access(0, t, c->dx2.get(), kHzWrite, all, what) && h.access(0, t, c->dk2.get(), kHzWrite, all,
+                                                                               what) &&
+           h.access(0, t, c->perm2.get(), kHzWrite, all, what);
+    if (!ok) return fail(c, SWRT_ERR_STATE, h.err);
+    ++h.epoch;  // a new partition of the packets into tiles
+  }
+  if (!keys_valid) {
+    // No memset when the last scan zeroed exactly these counts (the same bin
+    // count, no counting launch since): every second ode23 interval's
+    // re-binning then starts with the count.  Counts past the last scan's
+    // bins may hold an older, larger binning's counting launch
+    // (profiles/r06_ode23/README.md), hence the equal bin count.
+    if (!(c->counts_zero && c->nbins == nbins)) HIPCHK(c, hipMemsetAsync(c->bins.get(), 0, sizeof(int) * nbins,
+                                                                         c->stream));
+    hipLaunchKernelGGL(bin_count_kernel, dim3(grid), dim3(256), sizeof(int) * nbins, c->stream, g, c->dx.get(), n,
+                       nbins, c->keys.get(), c->bins.get());
+    HIPCHK(c, hipGetLastError());
+  }
+  c->keys_fresh = false;
+  if (c->dbg.corrupt_count != 0) {  // test-only: one corrupted count, once
+    hipLaunchKernelGGL(debug_corrupt_count_kernel, dim3(1), dim3(64), 0, c->stream, c->bins.get(), nbins / 2,
+                       c->dbg.corrupt_count);
+    c->dbg.corrupt_count = 0;
+  }
+  hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->bins.get(), nbins, c->bins.get() + kMaxBins,
+                     c->bins.get() + 2 * kMaxBins, n, c->dev_err.dev(), tile_order_of(c), lanes);
+  HIPCHK(c, hipGetLastError());
+  c->counts_zero = true;
+  c->bin_tile = g.tile;
+  c->bin_lanes = lanes;
+  if (indirect) {
+    hipLaunchKernelGGL(bin_scatter_kernel<true>, dim3(grid), dim3(256), 2 * sizeof(int) * nbins, c->stream, c->dx.get(),
+                       c->dk.get(), c->perm.get(), c->keys.get(), n, nbins, c->bins.get() + kMaxBins, c->dx2.get(),
+                       c->dk2.get(), c->perm2.get(), c->src_idx.get());
+  } else {
+    hipLaunchKernelGGL(bin_scatter_kernel<false>, dim3(grid), dim3(256), 2 * sizeof(int) * nbins, c->stream,
+                       c->dx.get(), c->dk.get(), c->perm.get(), c->keys.get(), n, nbins, c->bins.get() + kMaxBins,
+                       c->dx2.get(), c->dk2.get(), c->perm2.get(), nullptr);
+    std::swap(c->dx, c->dx2);
+    std::swap(c->dk, c->dk2);
+    std::swap(c->perm, c->perm2);
+  }
+  HIPCHK(c, hipGetLastError());
+  c->src_pending = indirect;
+  c->o23.order_valid = false;
+  c->o23.sorted = false;
+  c->steps_since_bin = 0;
+  c->bin_valid = true;
+  c->cells_sorted = false;
+  c->nbins = nbins;
+  return SWRT_OK;
+}
+
+int tile_launch(swrt_ctx* c, const StepArgs& a, bool count_next, const IvLaunch* iv = nullptr) {
+  TileArgs t;
+  t.s = a;
+  t.ivmode = iv != nullptr;
+  t.nint = iv ? iv->nint : 1;
+  if (iv) {
+    for (int i = 0; i <= iv->nint; ++i) t.ivn[i] = iv->views[i].nodes;
+    for (int i = 0; i < iv->nint; ++i) t.ivdt[i] = iv->dts[i];
+  }
+  t.x_out = c->dx2.get();
+  t.k_out = c->dk2.get();
+  t.perm_out = c->perm2.get();
+  t.starts = c->bins.get() + 2 * kMaxBins;
+  t.order = tile_order_of(c);
+  if (c->bin_tile != kTile) return fail(c, SWRT_ERR_STATE, "the binning is not the LDS-tiled kernel's");
+  t.ntx = (int)((a.f0.nx + kTile - 1) / kTile);
+  const int ntiles = t.ntx * t.ntx;
+  t.next_keys = nullptr;
+  t.next_counts = nullptr;
+  t.sort_cells = c->cells_sorted ? 0 : 1;
+  t.src = nullptr;
+  // sort keys lead by half the steps until the next sort (swrt_tile.hpp)
+  t.sort_lead = c->sort_lead ? 0.5 * a.dt * (double)std::max<int64_t>(1, c->rebin_every) : 0.0;
+  if (c->src_pending) {  // first launch after an indirect re-binning (always a sort launch)
+    t.src = c->src_idx.get();
+    t.sort_cells = 1;
+  }
+  bool zero = false;  // the counts' memset, queued by launch_tiles after its hazard check
+  if (count_next && ntiles == c->nbins) {
+    zero = !c->counts_zero;
+    t.next_keys = c->keys.get();
+    t.next_counts = c->bins.get();
+  }
+  const bool fma = c->gather_mode == 1;
+  if (a.nslots == 2) {
+    if (iv ? iv->div_free : two_v5(c, 2, 0)) {
+      if (tile_threads(c, true, ntiles) == kSparseThreads) {
+        if (fma)
+          HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<true, kTile, kMargin, kSparseThreads, true, true, kSparsePrefetch, kSparseMinWaves>, kSparseThreads, t, zero));
+        else
+          HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<true, kTile, kMargin, kSparseThreads, true, false, kSparsePrefetch, kSparseMinWaves>, kSparseThreads, t, zero));
+      } else if (fma) {
+        HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<true, kTile, kMargin, kTileThreads, true, true>, kTileThreads, t, zero));
+      } else {
+        HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<true, kTile, kMargin, kTileThreads, true>, kTileThreads, t, zero));
+      }
+    } else {
+      HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<true, kTile, kMargin, kTileThreads>, kTileThreads, t, zero));
+    }
+  } else {
+    if (c->slot[0].div_free && fma)
+      HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<false, kTile, kMargin, kTileThreads, true, true>, kTileThreads, t, zero));
+    else if (c->slot[0].div_free)
+      HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<false, kTile, kMargin, kTileThreads, true>, kTileThreads, t, zero));
+    else
+      HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<false, kTile, kMargin, kTileThreads>, kTileThreads, t, zero));
+  }
+  HIPCHK(c, hipGetLastError());
+  c->src_pending = false;
+  if (t.next_keys != nullptr) {
+    c->counts_zero = false;
+    c->key_nx = a.f0.nx;  // the view this launch bins by (a multi-interval launch: slot i0's)
+    c->key_dx = a.f0.dx;
+  }
+  if (t.src != nullptr && c->b_pending && !c->dbg.legacy_park) {
+    // The first launch after an indirect re-binning reads its input through
+    // src_idx from any slot of dx while its parts run on two streams; the
+    // next launch's parts would overwrite dx at their own tiles' slots before
+    // the other part has read them.  The next launches write the third
+    // buffers instead and dx is parked there until the next re-binning
+    // (which orders every stream's work first).
+    // (dx, dx2, dx3) <- (dx2, dx3, dx)
+    std::swap(c->dx, c->dx2); std::swap(c->dk, c->dk2); std::swap(c->perm, c->perm2);
+    std::swap(c->dx2, c->dx3); std::swap(c->dk2, c->dk3); std::swap(c->perm2, c->perm3);
+  } else {
+    std::swap(c->dx, c->dx2);
+    std::swap(c->dk, c->dk2);
+    std::swap(c->perm, c->perm2);
+  }
+  c->keys_fresh = t.next_keys != nullptr;
+  c->cells_sorted = true;  // written in (the input's or this launch's) cell order
+  return SWRT_OK;
+}
+
+// Before a per-packet leapfrog launch (packets updated in place on the packet
+// stream): order the extra stream's part launches of an earlier call first
+// (swrt_set_locality(0, ..) after split launches lands here), and tell the
+// hazard checker.
+int leap_launch_prep(swrt_ctx* c, const StepArgs& a) {
+  HIPCHK_RC(join_b(c));
+  c->s0_dirty = true;
+  if (!c->hz.on) return SWRT_OK;
+  HazardChecker& h = c->hz;
+  const uint64_t t = h.op(0);
+  const char* what = "the per-packet leapfrog launch";
+  const bool ok = h.access(0, t, a.x, kHzWrite, HzRegion::all(), what) &&
+                  h.access(0, t, a.k, kHzWrite, HzRegion::all(), what) &&
+                  h.access(0, t, a.perm, kHzRead, HzRegion::all(), what) &&
+                  h.access(0, t, a.hist_x, kHzWrite, HzRegion::all(), what) &&
+                  h.access(0, t, a.hist_k, kHzWrite, HzRegion::all(), what);
+  return ok ? SWRT_OK : fail(c, SWRT_ERR_STATE, h.err);
+}
+
+// Time every timing_every-th leapfrog launch with a pair of HIP events.
+int timed_launch(swrt_ctx* c, const StepArgs& a, unsigned grid, bool count_next, const IvLaunch* iv = nullptr) {
+  const bool timed = c->timing_every > 0 && (c->launch_count++ % c->timing_every) == 0;
+  if (!timed) {
+    if (use_tile_kernel(c)) return tile_launch(c, a, count_next, iv);
+    HIPCHK_RC(leap_launch_prep(c, a));
+    c->keys_fresh = false;
+    hipLaunchKernelGGL(leap_kernel(a.nslots), dim3(grid), dim3(256), 0, c->stream, a);
+    c->tail_ev = nullptr;
+    HIPCHK(c, hipGetLastError());
+    return SWRT_OK;
+  }
+  // timing events (pairs), grown on demand; fold into a running sum when full
+  if (c->timing.used + 2 > kMaxEvents) {
+    if (int rc = sync_sx(c)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i + 1 < c->timing.used; i += 2) {
+      float ms = 0.f;
+      HIPCHK(c, hipEventElapsedTime(&ms, c->timing.ev[i].get(), c->timing.ev[i + 1].get()));
+      c->timing.folded_ms += ms;
+      c->timing.folded_n += 1;
+    }
+    c->timing.used = 0;
+  }
+  if (c->timing.used + 2 > c->timing.ev.size()) {
+    for (int e = 0; e < 64; ++e) {
+      Event ev;
+      HIPCHK(c, ev.create(hipEventDefault));
+      c->timing.ev.push_back(std::move(ev));
+    }
+  }
+  c->kev0 = c->timing.ev[c->timing.used].get();
+  c->kev1 = c->timing.ev[c->timing.used + 1].get();
+  c->timing.used += 2;
+  int rc = SWRT_OK;
+  if (use_tile_kernel(c)) {
+    rc = tile_launch(c, a, count_next, iv);
+  } else if ((rc = leap_launch_prep(c, a)) == SWRT_OK) {
+    c->keys_fresh = false;
+    launch_k(c, leap_kernel(a.nslots), dim3(grid), dim3(256), a);
+  }
+  c->kev0 = c->kev1 = nullptr;
+  if (rc) return rc;
+  HIPCHK(c, hipGetLastError());
+  return SWRT_OK;
+}
+
+// the re-binning of a leapfrog call over slots sa .. sa+nslots-1, when due
+int leap_rebin_if_due(swrt_ctx* c, int nslots, int sa) {
+  if (c->rebin_every <= 0) return SWRT_OK;
+  const bool tiled = use_tile_kernel(c);
+  const int64_t ntiles = tiled ? ((c->slot[sa].nx + kTile - 1) / kTile) * ((c->slot[sa].nx + kTile - 1) / kTile) : 0;
+  const int lanes = tiled ? tile_threads(c, two_v5(c, nslots, sa), ntiles) : kTileThreads;
+  if (!c->bin_valid || c->steps_since_bin >= c->rebin_every ||
+      (tiled && (c->bin_tile != kTile || c->bin_lanes != lanes)))
+    return rebin(c, tiled, tiled ? kTile : 0, lanes);
+  return SWRT_OK;
+}
+
+// the arguments every launch of an advance call shares (history frames from the current one)
+StepArgs step_args(swrt_ctx* c, const FieldView& f0, const FieldView& f1, int nslots, double dt, double f, double gH,
+                   double alpha0, double dalpha, double bump, int64_t save_every) {
+  StepArgs a;
+  a.f0 = f0;
+  a.f1 = f1;
+  a.nslots = nslots;
+  a.n = c->n;
+  a.dt = dt;
+  a.half = dt / 2;
+  a.f2 = f * f;
+  a.fastdisp = dispersion_fast(a.f2);
+  a.gH = gH;
+  a.alpha0 = alpha0;
+  a.dalpha = dalpha;
+  a.bump = bump;
+  a.save_every = save_every > 0 ? save_every : 1;
+  a.hist_x = save_every > 0 ? c->hx.get() : nullptr;
+  a.hist_k = save_every > 0 ? c->hk.get() : nullptr;
+  a.frame0 = c->hframes;
+  return a;
+}
+
+int run_advance(swrt_ctx* c, double dt, int64_t nsteps, double f, double gH, int nslots,
+                double alpha0, double dalpha, double bump, int64_t save_every, int sa = 0) {
+  const FieldView f0 = view_of(c->slot[sa]);
+  StepArgs a = step_args(c, f0, nslots == 2 ? view_of(c->slot[sa + 1]) : f0, nslots, dt, f, gH, alpha0, dalpha, bump,
+                         save_every);
+  const unsigned grid = nblocks(c->n, 256);
+  int64_t s0 = 0;
+  while (s0 < nsteps) {
+    int64_t chunk = std::min<int64_t>(kMaxStepsPerLaunch, nsteps - s0);
+    if (c->rebin_every > 0) {
+      if (int rc = leap_rebin_if_due(c, nslots, sa)) return rc;
+      chunk = std::min<int64_t>(chunk, c->rebin_every - c->steps_since_bin);
+    }
+    a.x = c->dx.get();
+    a.k = c->dk.get();
+    a.perm = c->perm.get();
+    a.s0 = s0;
+    a.nsteps = (int)chunk;
+    // the launch that ends at a re-binning point also counts the next bins
+    const bool count_next = c->rebin_every > 0 && c->steps_since_bin + chunk >= c->rebin_every;
+    slot_writes_wait(c);  // after the re-binning: it reads no slot
+    int rc = timed_launch(c, a, grid, count_next);
+    if (rc) return rc;
+    c->steps_since_bin += chunk;
+    s0 += chunk;
+  }
+  return SWRT_OK;
+}
+
+// nint PDE intervals of nsub steps each, interval i blending slots i, i+1 at
+// step size hs[i]: whole intervals per tile launch (up to kMaxIntervals, never
+// across a re-binning), else one interval at a time through run_advance.
+int run_advance_intervals(swrt_ctx* c, int nint, const double* hs, int64_t nsub, double f, double gH,
+                          double alpha0, double dalpha, double bump, int64_t save_every) {
+  const bool fused = use_tile_kernel(c) && c->rebin_every > 0 && c->rebin_every % nsub == 0 &&
+                     nsub <= kMaxStepsPerLaunch;
+  const int64_t fpi = save_every > 0 ? nsub / save_every : 0;  // frames per interval
+  int i0 = 0;
+  while (i0 < nint) {
+    int k = 0;
+    if (fused) {
+      if (int rc = leap_rebin_if_due(c, std::min(nint - i0, kMaxIntervals) + 1, i0)) return rc;
+      k = (int)std::min<int64_t>({(int64_t)(nint - i0), (c->rebin_every - c->steps_since_bin) / nsub,
+                                  (int64_t)kMaxIntervals});
+    }
+    if (k < 1) {  // one interval on its own (it may straddle a re-binning)
+      int rc = run_advance(c, hs[i0], nsub, f, gH, 2, alpha0, dalpha, bump, save_every, i0);
+      if (rc) return rc;
+      c->hframes += fpi;
+      i0 += 1;
+      continue;
+    }
+    IvLaunch iv;
+    iv.nint = k;
+    iv.div_free = true;
+    for (int i = 0; i <= k; ++i) {
+      iv.views[i] = view_of(c->slot[i0 + i]);
+      iv.div_free = iv.div_free && c->slot[i0 + i].div_free;
+    }
+    for (int i = 0; i < k; ++i) iv.dts[i] = hs[i0 + i];
+    StepArgs a = step_args(c, iv.views[0], iv.views[1], 2, hs[i0], f, gH, alpha0, dalpha, bump, save_every);
+    a.x = c->dx.get();
+    a.k = c->dk.get();
+    a.perm = c->perm.get();
+    a.s0 = 0;
+    a.nsteps = (int)nsub;
+    const bool count_next = c->steps_since_bin + k * nsub >= c->rebin_every;
+    slot_writes_wait(c);  // after the re-binning: it reads no slot
+    int rc = timed_launch(c, a, nblocks(c->n, 256), count_next, &iv);
+    if (rc) return rc;
+    c->steps_since_bin += k * nsub;
+    c->hframes += k * fpi;
+    i0 += k;
+  }
+  return SWRT_OK;
+}
+
+// grow the history frames (keeps the existing ones).  The capacity is kept in
+// doubles, not frames: a frame is 2 x n doubles and n changes with every
+// swrt_packets_set, so a frame count sized for a smaller ensemble must not
+// pass the check.
+int ensure_history(swrt_ctx* c, int64_t new_frames) {
+  const int64_t per = 2 * c->n;
+  const int64_t need = (c->hframes + new_frames) * per;
+  if (new_frames <= 0 || need <= c->hcap) return SWRT_OK;
+  if (int rc = join_b(c)) return rc;  // the second stream may still write frames into the old buffers
+  c->s0_dirty = true;
+  const int64_t ncap = std::max<int64_t>(need, 2 * c->hcap);
+  DevBuf<double> nx_, nk_;
+  HIPCHK(c, nx_.alloc(ncap));
+  if (nk_.alloc(ncap) != hipSuccess) return fail(c, SWRT_ERR_ALLOC, "history allocation failed");
+  if (c->hframes > 0) {
+    HIPCHK(c, hipMemcpyAsync(nx_.get(), c->hx.get(), sizeof(double) * per * c->hframes, hipMemcpyDeviceToDevice,
+                             c->stream));
+    HIPCHK(c, hipMemcpyAsync(nk_.get(), c->hk.get(), sizeof(double) * per * c->hframes, hipMemcpyDeviceToDevice,
+                             c->stream));
+  }
+  // the old buffers may still be read or written by queued work
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  hz_synced(c);
+  if (c->hz.on) {
+    c->hz.bufs.erase(c->hx.get());
+    c->hz.bufs.erase(c->hk.get());
+    c->hz.name(nx_.get(), "history x frames");
+    c->hz.name(nk_.get(), "history k frames");
+  }
+  c->hx = std::move(nx_);  // (the old buffers are released here)
+  c->hk = std::move(nk_);
+  c->hcap = ncap;
+  return SWRT_OK;
+}
+
+// the template kernels the wave-action and spectral entry points choose from
+// (8- or 16-cell tiles; sums in fp64 or fp32, precision 64 / 32)
+auto xka_tile_kernel_of(int tile) {
+  return tile == 8 ? xka_tile_kernel<8, kXkaMargin, 256> : xka_tile_kernel<16, kXkaMargin, 256>;
+}
+auto spectral_eval_kernel_of(int precision) {
+  return precision == 64 ? spectral_eval_kernel<double> : spectral_eval_kernel<float>;
+}
+auto spectral_leapfrog_kernel_of(int precision) {
+  return precision == 64 ? spectral_leapfrog_kernel<double> : spectral_leapfrog_kernel<float>;
+}
+}  // namespace

@@ -8,7 +8,7 @@
 //    source, the same IEEE operations on both sides;
 //  * ode23_control (swrt_ode23_ctl.cpp, a plain C++ translation unit): the
 //    controller loop of swraytracing_amd/integrate.py ode23_packets, operation
-//    for operation, driving an O23Exec — the device stages (swrt_api.hip's
+//    for operation, driving an O23Exec — the device stages (swrt_host_ode23.hpp's
 //    DeviceExec) or a scripted error sequence (swrt_ode23_replay, which the
 //    CPU tests compare with the Python controller fed the same sequence).
 #pragma once

@@ -1,6 +1,7 @@
 // CPU test of the packet-buffer hazard checker (swraytracing_amd/csrc/
-// swrt_hazard.hpp): replays the multi-stream launch protocol of swrt_api.hip
-// (tile_launch / launch_tiles / join_b / rebin) in the abstract — buffers are
+// swrt_hazard.hpp): replays the multi-stream launch protocol of the library
+// (swrt_host_packets.hpp tile_launch / launch_tiles / rebin, swrt_ctx.hpp
+// join_b) in the abstract — buffers are
 // tags, launches are accesses over the band slots the device mapping gives
 // each part (swrt_share.hpp share_slot, the same function the kernels run)
 // — and prints one line per scenario: "<name> ok" when the checker's verdict

@@ -1,6 +1,6 @@
 """CPU test of the packet-buffer hazard checker's model (swrt_hazard.hpp):
 tests/hazard_model.cpp replays the multi-stream launch protocol of
-swrt_api.hip abstractly and checks the checker's verdicts — silent on the
+swrt_host_packets.hpp abstractly and checks the checker's verdicts — silent on the
 library's ordering (third buffers, joins before re-binnings and whole
 launches), reporting the pre-third-buffer race, a whole launch or a
 re-binning without a join, and round 4's skewed cycle-end share (its regions
