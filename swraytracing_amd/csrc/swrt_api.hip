@@ -427,47 +427,42 @@ int swrt_packets_set(swrt_ctx* c, const double* x, const double* k, int64_t n) {
   HIPCHK(c, hipSetDevice(c->device));
   if (n > c->cap) {
     c->cap = 0;  // (a failed allocation leaves no capacity behind)
-    for (DevBuf<double>* b : {&c->dx, &c->dk, &c->dx2, &c->dk2, &c->dx3, &c->dk3}) HIPCHK(c, b->alloc(2 * n));
-    for (DevBuf<int>* b : {&c->perm, &c->perm2, &c->perm3, &c->keys, &c->src_idx}) HIPCHK(c, b->alloc(n));
+    for (PacketSet* s : {&c->pk.cur, &c->pk.out, &c->pk.park}) HIPCHK(c, s->alloc(n));
+    for (DevBuf<int>* b : {&c->keys, &c->src_idx}) HIPCHK(c, b->alloc(n));
     c->cap = n;
   }
-  if (!c->bins) HIPCHK(c, c->bins.alloc(4 * kMaxBins + 1));
+  if (!c->bins.buf) HIPCHK(c, c->bins.alloc());
   c->n = n;
   if (n > 0) {
-    HIPCHK(c, hipMemcpyAsync(c->dx.get(), x, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dk.get(), k, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(iota_kernel, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, c->perm.get(), n);
+    HIPCHK(c, hipMemcpyAsync(c->pk.cur.x.get(), x, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->pk.cur.k.get(), k, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(iota_kernel, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, c->pk.cur.perm.get(), n);
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->hz.on) {  // every packet stream's work is complete (joined, then synchronised)
     c->hz.quiesce();
     ++c->hz.epoch;
-    const char* tags[] = {"A", "B", "C"};
-    double* xs[] = {c->dx.get(), c->dx2.get(), c->dx3.get()};
-    double* ks[] = {c->dk.get(), c->dk2.get(), c->dk3.get()};
-    int* ps[] = {c->perm.get(), c->perm2.get(), c->perm3.get()};
-    for (int i = 0; i < 3; ++i) {
-      c->hz.name(xs[i], std::string("packet x buffer ") + tags[i]);
-      c->hz.name(ks[i], std::string("packet k buffer ") + tags[i]);
-      c->hz.name(ps[i], std::string("permutation buffer ") + tags[i]);
+    char tag = 'A';
+    for (const PacketSet* s : {&c->pk.cur, &c->pk.out, &c->pk.park}) {
+      c->hz.name(s->x.get(), std::string("packet x buffer ") + tag);
+      c->hz.name(s->k.get(), std::string("packet k buffer ") + tag);
+      c->hz.name(s->perm.get(), std::string("permutation buffer ") + tag);
+      ++tag;
     }
     c->hz.name(c->keys.get(), "binning keys");
     c->hz.name(c->src_idx.get(), "re-binning source index");
-    c->hz.name(c->bins.get(), "bin counts");
-    c->hz.name(c->bins.get() + kMaxBins, "bin cursors");
-    c->hz.name(c->bins.get() + 2 * kMaxBins, "tile starts");
-    c->hz.name(c->bins.get() + 3 * kMaxBins + 1, "tile order");
+    c->hz.name(c->bins.counts(), "bin counts");
+    c->hz.name(c->bins.cursor(), "bin cursors");
+    c->hz.name(c->bins.starts(), "tile starts");
+    c->hz.name(c->bins.tile_order(), "tile order");
   }
   // a new ensemble starts a new history and needs binning before the next step
   if (c->dev_err) c->dev_err[0] = 0;  // (an error raised over the old ensemble is superseded)
   c->packets_lost = false;
   c->hframes = 0;
   c->steps_done = 0;
-  c->bin_valid = false;
-  c->keys_fresh = false;
-  c->src_pending = false;
-  c->steps_since_bin = 0;
+  c->bin.invalidate();
   return SWRT_OK;
   GUARD_END(c)
 }
@@ -480,11 +475,11 @@ int swrt_packets_get(swrt_ctx* c, double* x, double* k) {
   if (c->packets_lost) return fail(c, SWRT_ERR_STATE, "the packet state was lost to a corrupted binning");
   HIPCHK(c, hipSetDevice(c->device));
   // un-permute into the scatter buffers, then download in original order
-  hipLaunchKernelGGL(unpermute_kernel, dim3(nblocks(c->n, 256)), dim3(256), 0, c->stream, c->dx.get(), c->dk.get(),
-                     c->perm.get(), c->n, c->n, c->dx2.get(), c->dk2.get());
+  hipLaunchKernelGGL(unpermute_kernel, dim3(nblocks(c->n, 256)), dim3(256), 0, c->stream, c->pk.cur.x.get(),
+                     c->pk.cur.k.get(), c->pk.cur.perm.get(), c->n, c->n, c->pk.out.x.get(), c->pk.out.k.get());
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(x, c->dx2.get(), sizeof(double) * 2 * c->n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(k, c->dk2.get(), sizeof(double) * 2 * c->n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(x, c->pk.out.x.get(), sizeof(double) * 2 * c->n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(k, c->pk.out.k.get(), sizeof(double) * 2 * c->n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return dev_err_check(c);
   GUARD_END(c)
@@ -498,8 +493,8 @@ int swrt_packets_get_device(swrt_ctx* c, double* x_dev, double* k_dev, int64_t l
   if (!x_dev || !k_dev) return fail(c, SWRT_ERR_ARG, "NULL buffer");
   if (ld < c->n) return fail(c, SWRT_ERR_ARG, "leading dimension below the packet count");
   HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(unpermute_kernel, dim3(nblocks(c->n, 256)), dim3(256), 0, c->stream, c->dx.get(), c->dk.get(),
-                     c->perm.get(), c->n, ld, x_dev, k_dev);
+  hipLaunchKernelGGL(unpermute_kernel, dim3(nblocks(c->n, 256)), dim3(256), 0, c->stream, c->pk.cur.x.get(),
+                     c->pk.cur.k.get(), c->pk.cur.perm.get(), c->n, ld, x_dev, k_dev);
   HIPCHK(c, hipGetLastError());
   return SWRT_OK;
   GUARD_END(c)
@@ -539,9 +534,7 @@ int swrt_set_sparse_tiles(swrt_ctx* c, int mode) {
   c->s0_dirty = true;  // (conservative: settings and syncs may precede packet-stream work)
   if (mode < 0 || mode > 2) return fail(c, SWRT_ERR_ARG, "sparse tiles must be 0 (auto), 1 (never) or 2 (always)");
   c->sparse_mode = mode;
-  c->bin_valid = false;  // the tile order of the next binning is sized for the launch shape
-  c->keys_fresh = false;
-  c->src_pending = false;
+  c->bin.invalidate();  // the tile order of the next binning is sized for the launch shape
   return SWRT_OK;
 }
 
@@ -550,9 +543,7 @@ int swrt_set_kernel(swrt_ctx* c, int variant) {
   c->s0_dirty = true;  // (conservative: settings and syncs may precede packet-stream work)
   if (variant < 0 || variant > 2) return fail(c, SWRT_ERR_ARG, "kernel variant must be 0..2");
   c->kernel = variant;
-  c->bin_valid = false;
-  c->keys_fresh = false;
-  c->src_pending = false;
+  c->bin.invalidate();
   return SWRT_OK;
 }
 
@@ -562,9 +553,7 @@ int swrt_set_locality(swrt_ctx* c, int64_t rebin_every, int64_t tile) {
   if (rebin_every < 0 || tile < 0) return fail(c, SWRT_ERR_ARG, "negative locality parameter");
   c->rebin_every = rebin_every;
   c->tile = tile;
-  c->bin_valid = false;
-  c->keys_fresh = false;
-  c->src_pending = false;
+  c->bin.invalidate();
   return SWRT_OK;
 }
 
@@ -1071,7 +1060,7 @@ int swrt_omega_histogram(swrt_ctx* c, double f, double Cg, const double* edges, 
   HIPCHK(c, hipMemsetAsync(dcounts, 0, sizeof(unsigned long long) * nbins, c->stream));
   double mean = 0.0;
   if (c->n > 0) {
-    hipLaunchKernelGGL(omega_hist_kernel, dim3(nblk), dim3(kHistThreads), 0, c->stream, c->dk.get(), c->n, f * f,
+    hipLaunchKernelGGL(omega_hist_kernel, dim3(nblk), dim3(kHistThreads), 0, c->stream, c->pk.cur.k.get(), c->n, f * f,
                        Cg * Cg, dedges, (int)nbins, dcounts, partial);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(omega_sum_kernel, dim3(1), dim3(64), 0, c->stream, partial, nblk, partial + nblk);
@@ -1151,8 +1140,7 @@ int swrt_debug_set(swrt_ctx* c, int key, int64_t value) {
     case SWRT_DEBUG_CORRUPT_COUNT:
       if (value < -1000000 || value > 1000000) return fail(c, SWRT_ERR_ARG, "count corruption out of range");
       c->dbg.corrupt_count = (int)value;
-      c->keys_fresh = false;
-      c->bin_valid = false;  // the next call re-bins (and meets the corrupted count)
+      c->bin.invalidate();  // the next call re-bins (and meets the corrupted count)
       return SWRT_OK;
     case SWRT_DEBUG_QG_UPDATE_COLS:
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "QG update/column-pass fusion must be 0 or 1");
@@ -1698,11 +1686,10 @@ int swrt_ode23_accept(swrt_ctx* c) {
   HIPCHK_RC(lost_check(c));
   HIPCHK_RC(chain_drop(c));
   if (!c->o23.ynx) return fail(c, SWRT_ERR_STATE, "no ode23 step attempted");
-  std::swap(c->dx, c->o23.ynx);
-  std::swap(c->dk, c->o23.ynk);
+  std::swap(c->pk.cur.x, c->o23.ynx);
+  std::swap(c->pk.cur.k, c->o23.ynk);
   std::swap(c->o23.F[0], c->o23.F[3]);
-  c->keys_fresh = false;
-  c->cells_sorted = false;
+  c->bin.packets_replaced();
   return SWRT_OK;
 }
 
@@ -1774,9 +1761,7 @@ int swrt_ode23_run_sharded(swrt_ctx* c, double t0, double tfinal, double tmax, d
   // attempt kernel reads device coefficients).
   // (not in a sharded run: the device would take the first step size from
   // this rank's stage-1 max, the controller takes it from every rank's)
-  const int ntx_ = (int)((c->slot[0].nx + kTile - 1) / kTile);
-  const bool dev_first =
-      !reduce && use_tile_kernel(c) && c->bin_valid && !c->src_pending && c->nbins == ntx_ * ntx_;
+  const bool dev_first = !reduce && tile_binned(c);
   // Two part launches per attempt when the binning allows.
   const bool split = ode23_split_ok(c);
   const bool first_chained = taken && first_cand && dev_first && split == ch.split;

@@ -67,7 +67,7 @@ constexpr int kOrderBuckets = 16;  // workgroup rounds told apart by the tile or
 // SWRT_ERR_STATE at its next synchronisation.  So a bad binning is an error,
 // never a launch over foreign packet ranges.
 // order != NULL (nbins % 8 == 0): the tile order of the LDS-tiled launches
-// (tile_order_of).  Each of the 8 XCD bands of nbins/8 consecutive tiles is
+// (BinArrays::tile_order).  Each of the 8 XCD bands of nbins/8 consecutive tiles is
 // listed longest first — by the rounds ceil(count / lanes) its workgroup of
 // `lanes` threads runs (one packet per lane per round), spatial order within
 // a round count — so a band's long tiles start first and its tail is made of

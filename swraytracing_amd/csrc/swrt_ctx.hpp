@@ -20,6 +20,7 @@
 #include "swrt_hazard.hpp"
 #include "swrt_ode23_ctl.hpp"
 #include "swrt_res.hpp"
+#include "swrt_packet_state.hpp"
 
 using namespace swrt;
 
@@ -45,6 +46,7 @@ constexpr int kXkaMargin = 3;           // xka_tile_kernel: drift margin (cells)
 constexpr int kTile = SWRT_TILE;                // LDS tile kernel: cells per tile side
 constexpr int kMargin = SWRT_MARGIN;            // LDS tile kernel: drift margin (cells)
 constexpr int kTileThreads = SWRT_TILE_THREADS;
+inline int tiles_per_side(int64_t nx) { return (int)((nx + kTile - 1) / kTile); }  // of the LDS tile kernel
 // Sparse-tile launches: below SWRT_SPARSE_BELOW packets per 16x16 tile on
 // average (a strong-scaling shard: ~120 at 1.25e5 packets on 512^2) a
 // 512-thread workgroup has one or two busy waves, one per SIMD, each capped
@@ -75,6 +77,29 @@ constexpr int kSparseBelow = SWRT_SPARSE_BELOW;
 constexpr int kSparseThreads = SWRT_SPARSE_THREADS;
 constexpr int kSparsePrefetch = SWRT_SPARSE_PREFETCH;
 constexpr int kSparseMinWaves = SWRT_SPARSE_MINW;  // waves per SIMD the sparse shape's registers are sized for
+
+// one set of packet buffers (device order = spatially binned; perm maps to the original index)
+struct PacketSet {
+  DevBuf<double> x, k;  // 2N each
+  DevBuf<int> perm;     // N
+  hipError_t alloc(size_t n) {
+    if (hipError_t e = x.alloc(2 * n); e != hipSuccess) return e;
+    if (hipError_t e = k.alloc(2 * n); e != hipSuccess) return e;
+    return perm.alloc(n);
+  }
+};
+
+// the binning's four device arrays, one allocation
+struct BinArrays {
+  DevBuf<int> buf;  // counts | cursor | starts (kMaxBins + 1) | tile order
+  hipError_t alloc() { return buf.alloc(4 * kMaxBins + 1); }
+  int* at(int off) const { return buf ? buf.get() + off : nullptr; }
+  int* counts() const { return at(0); }
+  int* cursor() const { return at(kMaxBins); }
+  int* starts() const { return at(2 * kMaxBins); }
+  // longest-first tile order of the LDS-tiled launches (every re-binning's bin_scan_kernel writes it)
+  int* tile_order() const { return at(3 * kMaxBins + 1); }
+};
 
 struct Slot {
   DevBuf<double> nodes;     // padded interleaved records
@@ -196,10 +221,6 @@ struct Ode23State {
   DevBuf<double> F[4];
   DevBuf<int> order;         // ode23 tile kernel: in-tile cell order of the binned slots
   int64_t order_cap = 0;
-  bool order_valid = false;  // computed for the current binning
-  bool sorted = false;       // the packets themselves are in the in-tile cell order of the current binning
-  int since_bin = 0;         // ode23 calls since the last one that re-binned
-                             // (swrt_ode23_f1's tile_cell_sort_kernel): the stages take them in slot order
   DevBuf<double> ynx;
   DevBuf<double> ynk;
   // a third state set (x, k, F) for swrt_ode23_run's speculative attempt
@@ -308,34 +329,18 @@ struct swrt_ctx {
   int qg_jfuse = 1;  // fused mode, 2 layers, no packets beside: the column pass fused with the Jacobian (SWRT_DEBUG_QG_JFUSE)
   int qg_update_cols = 1;  // fused mode, no packets beside: J's last forward pass inside the update (SWRT_DEBUG_QG_UPDATE_COLS)
   std::vector<Slot> spares;
-  // packets (device order = spatially binned; perm maps to the original index)
-  DevBuf<double> dx;  // 2N
-  DevBuf<double> dk;  // 2N
-  DevBuf<int> perm;   // N
-  DevBuf<double> dx2;  // scatter targets of the binning pass
-  DevBuf<double> dk2;
-  DevBuf<int> perm2;
-  // third packet buffers: the output of the launch after a source-gather
-  // sort launch split over several streams (see tile_launch)
-  DevBuf<double> dx3;
-  DevBuf<double> dk3;
-  DevBuf<int> perm3;
+  // packets: the current set, the next output (of a tile launch or the binning's scatter) and a third
+  // set, the output of the launch after a split source-gather sort launch (see tile_launch)
+  SetRing<PacketSet> pk;
   DevBuf<int> keys;   // N
   DevBuf<int> src_idx;   // N: source slot of each binned slot (indirect re-binning)
-  bool src_pending = false;  // the next tile launch reads its packets through src_idx
-  DevBuf<int> bins;   // counts | cursor | starts (kMaxBins + 1) | tile order  (4 * kMaxBins + 1)
+  BinArrays bins;
+  Binning bin;  // the host's picture of the binning (swrt_packet_state.hpp)
   int kernel = 0;        // 0 auto, 1 per-packet global gather, 2 LDS tile kernel
-  int nbins = 0;         // bins of the current binning
   int64_t n = 0;
   int64_t cap = 0;
   int64_t rebin_every = 4;  // steps between spatial re-binning (0: never)
   int64_t tile = 0;         // cells per tile side (0: automatic)
-  int64_t steps_since_bin = 0;
-  bool bin_valid = false;
-  bool keys_fresh = false;  // keys/counts of the current state came from the last tile launch
-  int64_t key_nx = 0;       // ... on the grid the launch read (its first snapshot's nx and dx: the keys
-  double key_dx = 0.0;      //     depend on those only, not on the field values — new snapshots keep them valid)
-  bool counts_zero = false;  // bins' count block is all zero (cleared by the last scan)
   bool sort_lead = SWRT_SORT_LEAD;  // in-tile sort keys lead by the group-velocity drift
   int gather_mode = 0;      // 0: stencil sums mul then add (bit-exact); 1: fused multiply-add (tolerance)
   int sparse_mode = 0;      // sparse-tile launches: 0 auto (below kSparseBelow packets per tile), 1 never, 2 always
@@ -350,9 +355,6 @@ struct swrt_ctx {
   Event jx[kMaxPacketStreams - 1];  // the extra streams' join events
   Event fork_ev;
   int b_pending = 0;              // extra streams holding packet work not yet ordered before stream's
-  int bin_tile = 0;         // cells per tile side of the current binning
-  int bin_lanes = 0;        // ... and the workgroup width its tile order was ranked for (tile_threads)
-  bool cells_sorted = false;  // packets of every tile are in cell order (a tile launch wrote them)
   // history
   DevBuf<double> hx;
   DevBuf<double> hk;
@@ -576,15 +578,11 @@ int chain_drop(swrt_ctx* c) {
   return chain_join(c);
 }
 
-// Hazard checker (swrt_hazard.hpp): the packet-state buffers of the context.
-template <typename F>
-void hz_each_buffer(swrt_ctx* c, F fn) {
-  const int* bins = c->bins.get();
-  for (const void* b : std::initializer_list<const void*>{
-           c->dx.get(), c->dk.get(), c->perm.get(), c->dx2.get(), c->dk2.get(), c->perm2.get(), c->dx3.get(),
-           c->dk3.get(), c->perm3.get(), c->keys.get(), c->src_idx.get(), bins, bins ? bins + kMaxBins : nullptr,
-           bins ? bins + 2 * kMaxBins : nullptr, bins ? bins + 3 * kMaxBins + 1 : nullptr, c->hx.get(), c->hk.get()})
-    if (b) fn(b);
+// operation t of the packet stream accesses each of `bufs` whole, in this order
+inline bool hz_whole(HazardChecker& h, uint64_t t, int kind, const char* what, std::initializer_list<const void*> bufs) {
+  for (const void* b : bufs)
+    if (!h.access(0, t, b, kind, HzRegion::all(), what)) return false;
+  return true;
 }
 
 // Every other API call runs on the packet stream after join_b: to the checker
@@ -593,7 +591,12 @@ void hz_each_buffer(swrt_ctx* c, F fn) {
 void hz_api(swrt_ctx* c) {
   if (!c || !c->hz.on) return;
   const uint64_t t = c->hz.op(0);
-  hz_each_buffer(c, [&](const void* b) { (void)c->hz.access(0, t, b, kHzWrite, HzRegion::all(), "an API call"); });
+  const PacketSet &p0 = c->pk.cur, &p1 = c->pk.out, &p2 = c->pk.park;
+  for (const void* b : std::initializer_list<const void*>{
+           p0.x.get(), p0.k.get(), p0.perm.get(), p1.x.get(), p1.k.get(), p1.perm.get(), p2.x.get(), p2.k.get(),
+           p2.perm.get(), c->keys.get(), c->src_idx.get(), c->bins.counts(), c->bins.cursor(), c->bins.starts(),
+           c->bins.tile_order(), c->hx.get(), c->hk.get()})
+    (void)c->hz.access(0, t, b, kHzWrite, HzRegion::all(), "an API call");  // (a null buffer is no access)
 }
 
 // The host synchronised the packet stream after join_b: everything queued on
@@ -610,11 +613,7 @@ int dev_err_check(swrt_ctx* c) {
   if (!c->dev_err || !c->dev_err[0]) return SWRT_OK;
   c->dev_err[0] = 0;
   c->packets_lost = true;
-  c->bin_valid = false;
-  c->keys_fresh = false;
-  c->src_pending = false;
-  c->o23.order_valid = false;
-  c->o23.sorted = false;
+  c->bin.invalidate();
   return fail(c, SWRT_ERR_STATE,
               "packet binning corrupted: the tile counts do not sum to the packets (device check in "
               "bin_scan_kernel); no packet kernel ran over the bad ranges, but the packet state is lost — "

@@ -24,7 +24,7 @@ constexpr int kOde23RebinEvery = SWRT_ODE23_REBIN;
 
 int ode23_prepare(swrt_ctx* c, int nslots, Ode23Args& a, double tmax, double f, double Cg, double thr,
                   double bump) {
-  if (c->n <= 0 || !c->dx.get()) return fail(c, SWRT_ERR_STATE, "no packets (swrt_packets_set)");
+  if (c->n <= 0 || !c->pk.cur.x) return fail(c, SWRT_ERR_STATE, "no packets (swrt_packets_set)");
   if (nslots != 1 && nslots != 2) return fail(c, SWRT_ERR_ARG, "nslots must be 1 or 2");
   if (!c->slot[0].set || (nslots == 2 && !c->slot[1].set)) return fail(c, SWRT_ERR_STATE, "field slot not set");
   if (nslots == 2 && c->slot[1].nx != c->slot[0].nx) return fail(c, SWRT_ERR_ARG, "slots differ in nx");
@@ -60,8 +60,8 @@ int ode23_prepare(swrt_ctx* c, int nslots, Ode23Args& a, double tmax, double f, 
   a.f1 = nslots == 2 ? view_of(c->slot[1]) : a.f0;
   a.nslots = nslots;
   a.n = c->n;
-  a.yx = c->dx.get();
-  a.yk = c->dk.get();
+  a.yx = c->pk.cur.x.get();
+  a.yk = c->pk.cur.k.get();
   for (int s = 0; s < 4; ++s) a.F[s] = c->o23.F[s].get();
   a.ynx = c->o23.ynx.get();
   a.ynk = c->o23.ynk.get();
@@ -135,10 +135,9 @@ void ode23_tile_launch(swrt_ctx* c, const Ode23Args& a, unsigned grid, const int
 // stream order alone orders each part's attempts; the packets must already be
 // in the tiles' cell order (no order kernel between the parts).
 bool ode23_split_ok(swrt_ctx* c) {
-  const int ntx = (int)((c->slot[0].nx + kTile - 1) / kTile);
-  return use_tile_kernel(c) && c->bin_valid && !c->src_pending && c->nbins == ntx * ntx && c->o23.sorted &&
-         (ntx * ntx) % 16 == 0 && c->n >= kMultiStreamFrom && c->packet_streams == 2 && c->stream == c->stream0.get() &&
-         c->sx[0].get() != nullptr;
+  const int ntx = tiles_per_side(c->slot[0].nx);
+  return tile_binned(c) && c->bin.ode23_is_sorted() && (ntx * ntx) % 16 == 0 && c->n >= kMultiStreamFrom &&
+         c->packet_streams == 2 && c->stream == c->stream0.get() && c->sx[0].get() != nullptr;
 }
 
 // part -1: one launch over every tile on the packet stream; 0 / 1: that part
@@ -153,10 +152,10 @@ int ode23_launch(swrt_ctx* c, const Ode23Args& a0, int part = -1, unsigned* wg_o
                  hipEvent_t stop = nullptr, bool* stop_done = nullptr) {
   if (wg_out) *wg_out = 0;
   if (stop_done) *stop_done = false;
-  const int ntx = (int)((c->slot[0].nx + kTile - 1) / kTile);
+  const int ntx = tiles_per_side(c->slot[0].nx);
   if (part >= 0 && !ode23_split_ok(c)) return fail(c, SWRT_ERR_STATE, "ode23 split attempt without a split binning");
-  if (use_tile_kernel(c) && c->bin_valid && !c->src_pending && c->nbins == ntx * ntx) {
-    const int* starts = c->bins.get() + 2 * kMaxBins;
+  if (tile_binned(c)) {
+    const int* starts = c->bins.starts();
     const unsigned ntiles = (unsigned)(ntx * ntx);
     Ode23Args a = a0;
     a.sh = TileShare{(int)ntiles, part, part < 0 ? 1 : 2, kShareEven};
@@ -165,22 +164,18 @@ int ode23_launch(swrt_ctx* c, const Ode23Args& a0, int part = -1, unsigned* wg_o
     if (wg_out) *wg_out = grid;
     // in-tile cell order of this binning, once (swrt_ode23.hpp): the packets'
     // own order after swrt_ode23_f1's sort, else an order array
-    if (c->o23.sorted) {
-      a.order = nullptr;
-    } else if (!c->o23.order_valid) {
+    if (!c->bin.ode23_is_sorted() && !c->bin.ode23_order()) {
       if (c->o23.order_cap < c->cap) {
         HIPCHK(c, c->o23.order.alloc(c->cap));
         c->o23.order_cap = c->cap;
       }
       const FieldView v = view_of(c->slot[0]);
       hipLaunchKernelGGL((tile_cell_order_kernel<kTile, kTileThreads>), dim3(grid), dim3(kTileThreads), 0,
-                         c->stream, c->dx.get(), c->n, starts, ntx, v.inv_dx, v.nx, c->o23.order.get());
+                         c->stream, c->pk.cur.x.get(), c->n, starts, ntx, v.inv_dx, v.nx, c->o23.order.get());
       HIPCHK(c, hipGetLastError());
-      c->o23.order_valid = true;
-      a.order = c->o23.order.get();
-    } else {
-      a.order = c->o23.order.get();
+      c->bin.ode23_order_built();
     }
+    a.order = c->bin.ode23_is_sorted() ? nullptr : c->o23.order.get();
     if (a.hpart) {
       unsigned long long* hh = c->o23.hpart.get() + (a.hpart - c->o23.hpart.dev());
       std::fill(hh, hh + grid, kHpartEmpty);
@@ -220,26 +215,22 @@ int ode23_f1_queue(swrt_ctx* c, double t, double tmax, double f, double Cg, int 
   // is free: the error norm is a max over all components; a packet that has
   // left its tile's window since takes the global gather, so a skipped
   // re-binning changes speed only)
-  const int ntx0 = (int)((c->slot[0].nx + kTile - 1) / kTile);
-  const bool binned = use_tile_kernel(c) && c->bin_valid && !c->src_pending && c->nbins == ntx0 * ntx0 &&
-                      c->bin_tile == kTile && c->o23.sorted;
-  const bool due = !binned || ++c->o23.since_bin >= kOde23RebinEvery;
+  const bool binned = tile_binned(c) && c->bin.tile() == kTile && c->bin.ode23_is_sorted();
+  const bool due = !binned || c->bin.ode23_call_due(kOde23RebinEvery);
   if (c->rebin_every > 0 && c->slot[0].set && due) {
-    c->o23.since_bin = 0;
     if ((rc = rebin(c, false, use_tile_kernel(c) ? kTile : 0))) return rc;  // the ode23 tile kernel's 16x16 tiles
-    const int ntx = (int)((c->slot[0].nx + kTile - 1) / kTile);
-    if (use_tile_kernel(c) && c->bin_valid && !c->src_pending && c->nbins == ntx * ntx) {
+    if (tile_binned(c)) {
       // the in-tile cell order applied to the packets (swrt_ode23.hpp tile_cell_sort_kernel)
       const FieldView v = view_of(c->slot[0]);
+      const int ntx = tiles_per_side(c->slot[0].nx);
+      const PacketSet &in = c->pk.cur, &out = c->pk.out;
       hipLaunchKernelGGL((tile_cell_sort_kernel<kTile, kTileThreads>), dim3((unsigned)(ntx * ntx)),
-                         dim3(kTileThreads), 0, c->stream, (const double*)c->dx.get(), (const double*)c->dk.get(),
-                         (const int*)c->perm.get(), c->n, (const int*)(c->bins.get() + 2 * kMaxBins), ntx, v.inv_dx,
-                         (int)v.nx, c->dx2.get(), c->dk2.get(), c->perm2.get());
+                         dim3(kTileThreads), 0, c->stream, (const double*)in.x.get(), (const double*)in.k.get(),
+                         (const int*)in.perm.get(), c->n, (const int*)c->bins.starts(), ntx, v.inv_dx, (int)v.nx,
+                         out.x.get(), out.k.get(), out.perm.get());
       HIPCHK(c, hipGetLastError());
-      std::swap(c->dx, c->dx2);
-      std::swap(c->dk, c->dk2);
-      std::swap(c->perm, c->perm2);
-      c->o23.sorted = true;
+      c->pk.flip();
+      c->bin.ode23_sorted();  // (and restarts the count of calls until the next re-binning)
     }
   }
   Ode23Args a;
@@ -285,7 +276,7 @@ class DeviceExec final : public O23Exec {
              void* hook_user_, int (*reduce_)(double*, void*) = nullptr, void* reduce_user_ = nullptr)
       : c(c_), base(base_), split(split_), P(split_ ? 2 : 1), dev_first(dev_first_), sl_f1(sl_f1_), hook(hook_),
         hook_user(hook_user_), reduce(reduce_), reduce_user(reduce_user_),
-        S{{c_->dx.get(), c_->dk.get(), c_->o23.F[0].get()},
+        S{{c_->pk.cur.x.get(), c_->pk.cur.k.get(), c_->o23.F[0].get()},
           {c_->o23.ynx.get(), c_->o23.ynk.get(), c_->o23.F[3].get()},
           {c_->o23.spx.get(), c_->o23.spk.get(), c_->o23.spF.get()}} {}
 
@@ -497,7 +488,7 @@ class DeviceExec final : public O23Exec {
     // the owning handles of the three sets, rotated so that set (cur + i) % 3
     // of this run becomes set i: two swaps of whole sets
     Ode23State& o = c->o23;
-    DevBuf<double>* H[3][3] = {{&c->dx, &c->dk, &o.F[0]}, {&o.ynx, &o.ynk, &o.F[3]}, {&o.spx, &o.spk, &o.spF}};
+    DevBuf<double>* H[3][3] = {{&c->pk.cur.x, &c->pk.cur.k, &o.F[0]}, {&o.ynx, &o.ynk, &o.F[3]}, {&o.spx, &o.spk, &o.spF}};
     auto swap_sets = [&](int i, int j) {
       for (int m = 0; m < 3; ++m) std::swap(*H[i][m], *H[j][m]);
     };
@@ -505,8 +496,7 @@ class DeviceExec final : public O23Exec {
       swap_sets(0, cur);
       swap_sets(1, 2);
     }
-    c->keys_fresh = false;
-    c->cells_sorted = false;
+    c->bin.packets_replaced();
     return SWRT_OK;
   }
 
@@ -542,9 +532,7 @@ int ode23_chain_first(swrt_ctx* c, int sl_f1, double tmax, double f, double Cg, 
                       double rtol) {
   Ode23State::O23Chain& ch = c->o23.chain;
   ch.first_q = false;
-  const int ntx_ = (int)((c->slot[0].nx + kTile - 1) / kTile);
-  if (!c->o23.chain_first || !(use_tile_kernel(c) && c->bin_valid && !c->src_pending && c->nbins == ntx_ * ntx_))
-    return SWRT_OK;
+  if (!c->o23.chain_first || !tile_binned(c)) return SWRT_OK;
   const bool split = ode23_split_ok(c);
   const double t0 = 0.0, tfinal = tmax;
   const double rtol_c = std::max(rtol, 100 * 2.220446049250313e-16);

@@ -24,6 +24,9 @@ bool use_tile_kernel(const swrt_ctx* c) {
   return c->kernel == 0 && c->slot[0].nx >= 2 * kTile;
 }
 
+// a binning of slot 0's grid into the tile kernel's tiles is in force
+bool tile_binned(const swrt_ctx* c) { return use_tile_kernel(c) && c->bin.tiled_for(tiles_per_side(c->slot[0].nx)); }
+
 // the intervals of one multi-interval tile launch (swrt_advance_intervals)
 struct IvLaunch {
   int nint;
@@ -98,8 +101,7 @@ int hz_tile_launch(swrt_ctx* c, const TileArgs& t, const TileShare* parts, int n
 
 // zero_counts: clear t.next_counts (the next binning's counts) first, on the
 // packet stream — after the hazard check, so a refused launch queues nothing.
-template <typename F>
-int launch_tiles(swrt_ctx* c, F kernel, int nt, TileArgs t, bool zero_counts) {
+int launch_tiles(swrt_ctx* c, void (*kernel)(TileArgs), int nt, TileArgs t, bool zero_counts) {
   const int ntiles = t.ntx * t.ntx;
   const int S = c->n >= kMultiStreamFrom ? c->packet_streams : 1;
   // test-only (SWRT_DEBUG_SHARE_SKEW): the launch that ends a re-binning
@@ -151,10 +153,6 @@ int launch_tiles(swrt_ctx* c, F kernel, int nt, TileArgs t, bool zero_counts) {
   c->tail_ev = nullptr;  // slot uses are marked after the join (swrt_advance)
   return SWRT_OK;
 }
-
-// Longest-first tile order of the LDS-tiled launches, written by every
-// re-binning's scan (bin_scan_kernel) beside the tile starts.
-int* tile_order_of(swrt_ctx* c) { return c->bins.get() + 3 * kMaxBins + 1; }
 
 // The sparse-tile launch shape (kSparseThreads threads, prefetch depth
 // kSparsePrefetch) for the two-snapshot five-sum launches over `ntiles` tiles.
@@ -208,78 +206,65 @@ int rebin(swrt_ctx* c, bool indirect, int tile = 0, int lanes = kTileThreads) {
   g.dx = v.dx; g.px = v.px; g.py = v.py; g.inv_px = v.inv_px; g.inv_py = v.inv_py; g.inv_dx = v.inv_dx;
   g.nx = v.nx;
   g.tile = tile > 0 ? tile : tile_cells(c, s.nx);
-  g.ntx = (int)((s.nx + g.tile - 1) / g.tile);
+  g.ntx = (int)((s.nx + g.tile - 1) / g.tile);  // (any tile size: not tiles_per_side)
   const int nbins = g.ntx * g.ntx;
   if (nbins > kMaxBins) return fail(c, SWRT_ERR_ARG, "too many spatial bins (raise tile size)");
   const int64_t n = c->n;
   const unsigned grid = nblocks(n, 256 * kBinPerThread);
-  const bool keys_valid = c->keys_fresh && c->bin_valid && nbins == c->nbins && c->key_nx == v.nx && c->key_dx == v.dx;
+  const bool keys_valid = c->bin.keys_valid_for(nbins, v.nx, v.dx);
+  const PacketSet &in = c->pk.cur, &out = c->pk.out;
   if (c->hz.on) {  // count, scan and scatter on the packet stream
     HazardChecker& h = c->hz;
     const uint64_t t = h.op(0);
     const char* what = "a re-binning";
-    const HzRegion all = HzRegion::all();
-    bool ok = h.access(0, t, c->dx.get(), kHzRead, all, what) && h.access(0, t, c->dk.get(), kHzRead, all, what) &&
-              h.access(0, t, c->perm.get(), kHzRead, all, what) &&
-              h.access(0, t, c->keys.get(), keys_valid ? kHzRead : kHzWrite, all, what) &&
-              h.access(0, t, c->bins.get(), kHzWrite, all, what) && h.access(0, t, c->bins.get() + kMaxBins, kHzWrite,
-                                                                             all, what) &&
-              h.access(0, t, c->bins.get() + 2 * kMaxBins, kHzWrite, all, what) &&
-              h.access(0, t, tile_order_of(c), kHzWrite, all, what);
-    if (indirect)
-      ok = ok && h.access(0, t, c->src_idx.get(), kHzWrite, all, what);
-    else
-      ok = ok && h.access(0, t, c->dx2.get(), kHzWrite, all, what) && h.access(0, t, c->dk2.get(), kHzWrite, all,
-                                                                               what) &&
-           h.access(0, t, c->perm2.get(), kHzWrite, all, what);
+    const bool ok =
+        hz_whole(h, t, kHzRead, what, {in.x.get(), in.k.get(), in.perm.get()}) &&
+        hz_whole(h, t, keys_valid ? kHzRead : kHzWrite, what, {c->keys.get()}) &&
+        hz_whole(h, t, kHzWrite, what, {c->bins.counts(), c->bins.cursor(), c->bins.starts(), c->bins.tile_order()}) &&
+        (indirect ? hz_whole(h, t, kHzWrite, what, {c->src_idx.get()})
+                  : hz_whole(h, t, kHzWrite, what, {out.x.get(), out.k.get(), out.perm.get()}));
     if (!ok) return fail(c, SWRT_ERR_STATE, h.err);
     ++h.epoch;  // a new partition of the packets into tiles
   }
   if (!keys_valid) {
-    // No memset when the last scan zeroed exactly these counts (the same bin
-    // count, no counting launch since): every second ode23 interval's
-    // re-binning then starts with the count.  Counts past the last scan's
-    // bins may hold an older, larger binning's counting launch
-    // (profiles/r06_ode23/README.md), hence the equal bin count.
-    if (!(c->counts_zero && c->nbins == nbins)) HIPCHK(c, hipMemsetAsync(c->bins.get(), 0, sizeof(int) * nbins,
-                                                                         c->stream));
-    hipLaunchKernelGGL(bin_count_kernel, dim3(grid), dim3(256), sizeof(int) * nbins, c->stream, g, c->dx.get(), n,
-                       nbins, c->keys.get(), c->bins.get());
+    // (no memset at every second ode23 interval's re-binning: profiles/r06_ode23/README.md)
+    if (c->bin.needs_count_memset(nbins))
+      HIPCHK(c, hipMemsetAsync(c->bins.counts(), 0, sizeof(int) * nbins, c->stream));
+    hipLaunchKernelGGL(bin_count_kernel, dim3(grid), dim3(256), sizeof(int) * nbins, c->stream, g, in.x.get(), n,
+                       nbins, c->keys.get(), c->bins.counts());
     HIPCHK(c, hipGetLastError());
   }
-  c->keys_fresh = false;
   if (c->dbg.corrupt_count != 0) {  // test-only: one corrupted count, once
-    hipLaunchKernelGGL(debug_corrupt_count_kernel, dim3(1), dim3(64), 0, c->stream, c->bins.get(), nbins / 2,
+    hipLaunchKernelGGL(debug_corrupt_count_kernel, dim3(1), dim3(64), 0, c->stream, c->bins.counts(), nbins / 2,
                        c->dbg.corrupt_count);
     c->dbg.corrupt_count = 0;
   }
-  hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->bins.get(), nbins, c->bins.get() + kMaxBins,
-                     c->bins.get() + 2 * kMaxBins, n, c->dev_err.dev(), tile_order_of(c), lanes);
+  hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->bins.counts(), nbins, c->bins.cursor(),
+                     c->bins.starts(), n, c->dev_err.dev(), c->bins.tile_order(), lanes);
   HIPCHK(c, hipGetLastError());
-  c->counts_zero = true;
-  c->bin_tile = g.tile;
-  c->bin_lanes = lanes;
-  if (indirect) {
-    hipLaunchKernelGGL(bin_scatter_kernel<true>, dim3(grid), dim3(256), 2 * sizeof(int) * nbins, c->stream, c->dx.get(),
-                       c->dk.get(), c->perm.get(), c->keys.get(), n, nbins, c->bins.get() + kMaxBins, c->dx2.get(),
-                       c->dk2.get(), c->perm2.get(), c->src_idx.get());
-  } else {
-    hipLaunchKernelGGL(bin_scatter_kernel<false>, dim3(grid), dim3(256), 2 * sizeof(int) * nbins, c->stream,
-                       c->dx.get(), c->dk.get(), c->perm.get(), c->keys.get(), n, nbins, c->bins.get() + kMaxBins,
-                       c->dx2.get(), c->dk2.get(), c->perm2.get(), nullptr);
-    std::swap(c->dx, c->dx2);
-    std::swap(c->dk, c->dk2);
-    std::swap(c->perm, c->perm2);
-  }
+  hipLaunchKernelGGL(indirect ? bin_scatter_kernel<true> : bin_scatter_kernel<false>, dim3(grid), dim3(256),
+                     2 * sizeof(int) * nbins, c->stream, in.x.get(), in.k.get(), in.perm.get(), c->keys.get(), n, nbins,
+                     c->bins.cursor(), out.x.get(), out.k.get(), out.perm.get(), indirect ? c->src_idx.get() : nullptr);
   HIPCHK(c, hipGetLastError());
-  c->src_pending = indirect;
-  c->o23.order_valid = false;
-  c->o23.sorted = false;
-  c->steps_since_bin = 0;
-  c->bin_valid = true;
-  c->cells_sorted = false;
-  c->nbins = nbins;
+  if (!indirect) c->pk.flip();  // (the packets were moved)
+  c->bin.rebinned(nbins, g.tile, lanes, indirect);
   return SWRT_OK;
+}
+
+// The LDS-tiled leapfrog kernel and its workgroup width: two blended snapshots
+// or one, divergence-free (v5: the five-sum gather), its sums as fused
+// multiply-adds (v5 only), the sparse launch shape (two v5 snapshots only).
+struct TileKernel { void (*fn)(TileArgs); int threads; };
+TileKernel tile_kernel_of(bool two, bool v5, bool fma, bool sparse) {
+  constexpr int T = kTile, M = kMargin, NT = kTileThreads, ST = kSparseThreads, PF = kSparsePrefetch;
+  constexpr int MW = kSparseMinWaves;
+  if (two && v5 && sparse)
+    return {fma ? tile_leapfrog_kernel<true, T, M, ST, true, true, PF, MW>
+                : tile_leapfrog_kernel<true, T, M, ST, true, false, PF, MW>, ST};
+  if (two && v5) return {fma ? tile_leapfrog_kernel<true, T, M, NT, true, true> : tile_leapfrog_kernel<true, T, M, NT, true>, NT};
+  if (two) return {tile_leapfrog_kernel<true, T, M, NT>, NT};
+  if (v5) return {fma ? tile_leapfrog_kernel<false, T, M, NT, true, true> : tile_leapfrog_kernel<false, T, M, NT, true>, NT};
+  return {tile_leapfrog_kernel<false, T, M, NT>, NT};
 }
 
 int tile_launch(swrt_ctx* c, const StepArgs& a, bool count_next, const IvLaunch* iv = nullptr) {
@@ -291,112 +276,83 @@ int tile_launch(swrt_ctx* c, const StepArgs& a, bool count_next, const IvLaunch*
     for (int i = 0; i <= iv->nint; ++i) t.ivn[i] = iv->views[i].nodes;
     for (int i = 0; i < iv->nint; ++i) t.ivdt[i] = iv->dts[i];
   }
-  t.x_out = c->dx2.get();
-  t.k_out = c->dk2.get();
-  t.perm_out = c->perm2.get();
-  t.starts = c->bins.get() + 2 * kMaxBins;
-  t.order = tile_order_of(c);
-  if (c->bin_tile != kTile) return fail(c, SWRT_ERR_STATE, "the binning is not the LDS-tiled kernel's");
-  t.ntx = (int)((a.f0.nx + kTile - 1) / kTile);
+  t.x_out = c->pk.out.x.get();
+  t.k_out = c->pk.out.k.get();
+  t.perm_out = c->pk.out.perm.get();
+  t.starts = c->bins.starts();
+  t.order = c->bins.tile_order();
+  if (c->bin.tile() != kTile) return fail(c, SWRT_ERR_STATE, "the binning is not the LDS-tiled kernel's");
+  t.ntx = tiles_per_side(a.f0.nx);
   const int ntiles = t.ntx * t.ntx;
   t.next_keys = nullptr;
   t.next_counts = nullptr;
-  t.sort_cells = c->cells_sorted ? 0 : 1;
+  t.sort_cells = c->bin.cells_sorted() ? 0 : 1;
   t.src = nullptr;
   // sort keys lead by half the steps until the next sort (swrt_tile.hpp)
   t.sort_lead = c->sort_lead ? 0.5 * a.dt * (double)std::max<int64_t>(1, c->rebin_every) : 0.0;
-  if (c->src_pending) {  // first launch after an indirect re-binning (always a sort launch)
+  if (c->bin.src_pending()) {  // first launch after an indirect re-binning (always a sort launch)
     t.src = c->src_idx.get();
     t.sort_cells = 1;
   }
   bool zero = false;  // the counts' memset, queued by launch_tiles after its hazard check
-  if (count_next && ntiles == c->nbins) {
-    zero = !c->counts_zero;
+  if (count_next && ntiles == c->bin.nbins()) {
+    zero = !c->bin.counts_zero();
     t.next_keys = c->keys.get();
-    t.next_counts = c->bins.get();
+    t.next_counts = c->bins.counts();
   }
-  const bool fma = c->gather_mode == 1;
-  if (a.nslots == 2) {
-    if (iv ? iv->div_free : two_v5(c, 2, 0)) {
-      if (tile_threads(c, true, ntiles) == kSparseThreads) {
-        if (fma)
-          HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<true, kTile, kMargin, kSparseThreads, true, true, kSparsePrefetch, kSparseMinWaves>, kSparseThreads, t, zero));
-        else
-          HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<true, kTile, kMargin, kSparseThreads, true, false, kSparsePrefetch, kSparseMinWaves>, kSparseThreads, t, zero));
-      } else if (fma) {
-        HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<true, kTile, kMargin, kTileThreads, true, true>, kTileThreads, t, zero));
-      } else {
-        HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<true, kTile, kMargin, kTileThreads, true>, kTileThreads, t, zero));
-      }
-    } else {
-      HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<true, kTile, kMargin, kTileThreads>, kTileThreads, t, zero));
-    }
-  } else {
-    if (c->slot[0].div_free && fma)
-      HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<false, kTile, kMargin, kTileThreads, true, true>, kTileThreads, t, zero));
-    else if (c->slot[0].div_free)
-      HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<false, kTile, kMargin, kTileThreads, true>, kTileThreads, t, zero));
-    else
-      HIPCHK_RC(launch_tiles(c, tile_leapfrog_kernel<false, kTile, kMargin, kTileThreads>, kTileThreads, t, zero));
-  }
+  const bool two = a.nslots == 2;
+  const bool v5 = two ? (iv ? iv->div_free : two_v5(c, 2, 0)) : c->slot[0].div_free;
+  const TileKernel tk = tile_kernel_of(two, v5, c->gather_mode == 1,
+                                       two && v5 && tile_threads(c, true, ntiles) == kSparseThreads);
+  HIPCHK_RC(launch_tiles(c, tk.fn, tk.threads, t, zero));
   HIPCHK(c, hipGetLastError());
-  c->src_pending = false;
-  if (t.next_keys != nullptr) {
-    c->counts_zero = false;
-    c->key_nx = a.f0.nx;  // the view this launch bins by (a multi-interval launch: slot i0's)
-    c->key_dx = a.f0.dx;
-  }
+  // (a.f0: the view this launch bins by; a multi-interval launch: slot i0's)
+  c->bin.tile_launched(t.next_keys != nullptr, a.f0.nx, a.f0.dx);
   if (t.src != nullptr && c->b_pending && !c->dbg.legacy_park) {
     // The first launch after an indirect re-binning reads its input through
-    // src_idx from any slot of dx while its parts run on two streams; the
-    // next launch's parts would overwrite dx at their own tiles' slots before
-    // the other part has read them.  The next launches write the third
-    // buffers instead and dx is parked there until the next re-binning
-    // (which orders every stream's work first).
-    // (dx, dx2, dx3) <- (dx2, dx3, dx)
-    std::swap(c->dx, c->dx2); std::swap(c->dk, c->dk2); std::swap(c->perm, c->perm2);
-    std::swap(c->dx2, c->dx3); std::swap(c->dk2, c->dk3); std::swap(c->perm2, c->perm3);
+    // src_idx from any slot of the packets while its parts run on two streams;
+    // the next launch's parts would overwrite them at their own tiles' slots
+    // before the other part has read them.  The next launches write the third
+    // set instead and the old packets are parked there until the next
+    // re-binning (which orders every stream's work first).
+    c->pk.park_cur();
   } else {
-    std::swap(c->dx, c->dx2);
-    std::swap(c->dk, c->dk2);
-    std::swap(c->perm, c->perm2);
+    c->pk.flip();
   }
-  c->keys_fresh = t.next_keys != nullptr;
-  c->cells_sorted = true;  // written in (the input's or this launch's) cell order
   return SWRT_OK;
 }
 
-// Before a per-packet leapfrog launch (packets updated in place on the packet
+// The per-packet leapfrog launch (packets updated in place on the packet
 // stream): order the extra stream's part launches of an earlier call first
 // (swrt_set_locality(0, ..) after split launches lands here), and tell the
 // hazard checker.
-int leap_launch_prep(swrt_ctx* c, const StepArgs& a) {
+int leap_launch(swrt_ctx* c, const StepArgs& a, unsigned grid) {
   HIPCHK_RC(join_b(c));
   c->s0_dirty = true;
-  if (!c->hz.on) return SWRT_OK;
-  HazardChecker& h = c->hz;
-  const uint64_t t = h.op(0);
-  const char* what = "the per-packet leapfrog launch";
-  const bool ok = h.access(0, t, a.x, kHzWrite, HzRegion::all(), what) &&
-                  h.access(0, t, a.k, kHzWrite, HzRegion::all(), what) &&
-                  h.access(0, t, a.perm, kHzRead, HzRegion::all(), what) &&
-                  h.access(0, t, a.hist_x, kHzWrite, HzRegion::all(), what) &&
-                  h.access(0, t, a.hist_k, kHzWrite, HzRegion::all(), what);
-  return ok ? SWRT_OK : fail(c, SWRT_ERR_STATE, h.err);
+  if (c->hz.on) {
+    HazardChecker& h = c->hz;
+    const uint64_t t = h.op(0);
+    const char* what = "the per-packet leapfrog launch";
+    if (!(hz_whole(h, t, kHzWrite, what, {a.x, a.k}) && hz_whole(h, t, kHzRead, what, {a.perm}) &&
+          hz_whole(h, t, kHzWrite, what, {a.hist_x, a.hist_k})))
+      return fail(c, SWRT_ERR_STATE, h.err);
+  }
+  c->bin.per_packet_launched();
+  if (c->kev1) {  // a timed launch: the dispatch stamps the events
+    launch_k(c, leap_kernel(a.nslots), dim3(grid), dim3(256), a);
+  } else {
+    hipLaunchKernelGGL(leap_kernel(a.nslots), dim3(grid), dim3(256), 0, c->stream, a);
+    c->tail_ev = nullptr;
+  }
+  HIPCHK(c, hipGetLastError());
+  return SWRT_OK;
 }
 
 // Time every timing_every-th leapfrog launch with a pair of HIP events.
 int timed_launch(swrt_ctx* c, const StepArgs& a, unsigned grid, bool count_next, const IvLaunch* iv = nullptr) {
   const bool timed = c->timing_every > 0 && (c->launch_count++ % c->timing_every) == 0;
-  if (!timed) {
-    if (use_tile_kernel(c)) return tile_launch(c, a, count_next, iv);
-    HIPCHK_RC(leap_launch_prep(c, a));
-    c->keys_fresh = false;
-    hipLaunchKernelGGL(leap_kernel(a.nslots), dim3(grid), dim3(256), 0, c->stream, a);
-    c->tail_ev = nullptr;
-    HIPCHK(c, hipGetLastError());
-    return SWRT_OK;
-  }
+  const auto launch = [&] { return use_tile_kernel(c) ? tile_launch(c, a, count_next, iv) : leap_launch(c, a, grid); };
+  if (!timed) return launch();
   // timing events (pairs), grown on demand; fold into a running sum when full
   if (c->timing.used + 2 > kMaxEvents) {
     if (int rc = sync_sx(c)) return rc;
@@ -419,27 +375,18 @@ int timed_launch(swrt_ctx* c, const StepArgs& a, unsigned grid, bool count_next,
   c->kev0 = c->timing.ev[c->timing.used].get();
   c->kev1 = c->timing.ev[c->timing.used + 1].get();
   c->timing.used += 2;
-  int rc = SWRT_OK;
-  if (use_tile_kernel(c)) {
-    rc = tile_launch(c, a, count_next, iv);
-  } else if ((rc = leap_launch_prep(c, a)) == SWRT_OK) {
-    c->keys_fresh = false;
-    launch_k(c, leap_kernel(a.nslots), dim3(grid), dim3(256), a);
-  }
+  const int rc = launch();
   c->kev0 = c->kev1 = nullptr;
-  if (rc) return rc;
-  HIPCHK(c, hipGetLastError());
-  return SWRT_OK;
+  return rc;
 }
 
 // the re-binning of a leapfrog call over slots sa .. sa+nslots-1, when due
 int leap_rebin_if_due(swrt_ctx* c, int nslots, int sa) {
   if (c->rebin_every <= 0) return SWRT_OK;
   const bool tiled = use_tile_kernel(c);
-  const int64_t ntiles = tiled ? ((c->slot[sa].nx + kTile - 1) / kTile) * ((c->slot[sa].nx + kTile - 1) / kTile) : 0;
+  const int64_t ntx = tiles_per_side(c->slot[sa].nx), ntiles = tiled ? ntx * ntx : 0;
   const int lanes = tiled ? tile_threads(c, two_v5(c, nslots, sa), ntiles) : kTileThreads;
-  if (!c->bin_valid || c->steps_since_bin >= c->rebin_every ||
-      (tiled && (c->bin_tile != kTile || c->bin_lanes != lanes)))
+  if (c->bin.due(c->rebin_every) || (tiled && (c->bin.tile() != kTile || c->bin.lanes() != lanes)))
     return rebin(c, tiled, tiled ? kTile : 0, lanes);
   return SWRT_OK;
 }
@@ -467,30 +414,32 @@ StepArgs step_args(swrt_ctx* c, const FieldView& f0, const FieldView& f1, int ns
   return a;
 }
 
+// One leapfrog launch over the current packets, nsteps steps (iv: per interval) from step s0, `steps` in all.
+// The launch that ends at a re-binning point also counts the next bins.
+int advance_launch(swrt_ctx* c, StepArgs& a, int64_t s0, int64_t nsteps, int64_t steps, const IvLaunch* iv = nullptr) {
+  a.x = c->pk.cur.x.get();
+  a.k = c->pk.cur.k.get();
+  a.perm = c->pk.cur.perm.get();
+  a.s0 = s0;
+  a.nsteps = (int)nsteps;
+  const bool count_next = c->rebin_every > 0 && steps >= c->bin.steps_left(c->rebin_every);
+  slot_writes_wait(c);  // after the re-binning: it reads no slot
+  HIPCHK_RC(timed_launch(c, a, nblocks(c->n, 256), count_next, iv));
+  c->bin.stepped(steps);
+  return SWRT_OK;
+}
+
 int run_advance(swrt_ctx* c, double dt, int64_t nsteps, double f, double gH, int nslots,
                 double alpha0, double dalpha, double bump, int64_t save_every, int sa = 0) {
   const FieldView f0 = view_of(c->slot[sa]);
   StepArgs a = step_args(c, f0, nslots == 2 ? view_of(c->slot[sa + 1]) : f0, nslots, dt, f, gH, alpha0, dalpha, bump,
                          save_every);
-  const unsigned grid = nblocks(c->n, 256);
   int64_t s0 = 0;
   while (s0 < nsteps) {
     int64_t chunk = std::min<int64_t>(kMaxStepsPerLaunch, nsteps - s0);
-    if (c->rebin_every > 0) {
-      if (int rc = leap_rebin_if_due(c, nslots, sa)) return rc;
-      chunk = std::min<int64_t>(chunk, c->rebin_every - c->steps_since_bin);
-    }
-    a.x = c->dx.get();
-    a.k = c->dk.get();
-    a.perm = c->perm.get();
-    a.s0 = s0;
-    a.nsteps = (int)chunk;
-    // the launch that ends at a re-binning point also counts the next bins
-    const bool count_next = c->rebin_every > 0 && c->steps_since_bin + chunk >= c->rebin_every;
-    slot_writes_wait(c);  // after the re-binning: it reads no slot
-    int rc = timed_launch(c, a, grid, count_next);
-    if (rc) return rc;
-    c->steps_since_bin += chunk;
+    HIPCHK_RC(leap_rebin_if_due(c, nslots, sa));
+    if (c->rebin_every > 0) chunk = std::min<int64_t>(chunk, c->bin.steps_left(c->rebin_every));
+    HIPCHK_RC(advance_launch(c, a, s0, chunk, chunk));
     s0 += chunk;
   }
   return SWRT_OK;
@@ -508,13 +457,12 @@ int run_advance_intervals(swrt_ctx* c, int nint, const double* hs, int64_t nsub,
   while (i0 < nint) {
     int k = 0;
     if (fused) {
-      if (int rc = leap_rebin_if_due(c, std::min(nint - i0, kMaxIntervals) + 1, i0)) return rc;
-      k = (int)std::min<int64_t>({(int64_t)(nint - i0), (c->rebin_every - c->steps_since_bin) / nsub,
+      HIPCHK_RC(leap_rebin_if_due(c, std::min(nint - i0, kMaxIntervals) + 1, i0));
+      k = (int)std::min<int64_t>({(int64_t)(nint - i0), c->bin.steps_left(c->rebin_every) / nsub,
                                   (int64_t)kMaxIntervals});
     }
     if (k < 1) {  // one interval on its own (it may straddle a re-binning)
-      int rc = run_advance(c, hs[i0], nsub, f, gH, 2, alpha0, dalpha, bump, save_every, i0);
-      if (rc) return rc;
+      HIPCHK_RC(run_advance(c, hs[i0], nsub, f, gH, 2, alpha0, dalpha, bump, save_every, i0));
       c->hframes += fpi;
       i0 += 1;
       continue;
@@ -528,16 +476,7 @@ int run_advance_intervals(swrt_ctx* c, int nint, const double* hs, int64_t nsub,
     }
     for (int i = 0; i < k; ++i) iv.dts[i] = hs[i0 + i];
     StepArgs a = step_args(c, iv.views[0], iv.views[1], 2, hs[i0], f, gH, alpha0, dalpha, bump, save_every);
-    a.x = c->dx.get();
-    a.k = c->dk.get();
-    a.perm = c->perm.get();
-    a.s0 = 0;
-    a.nsteps = (int)nsub;
-    const bool count_next = c->steps_since_bin + k * nsub >= c->rebin_every;
-    slot_writes_wait(c);  // after the re-binning: it reads no slot
-    int rc = timed_launch(c, a, nblocks(c->n, 256), count_next, &iv);
-    if (rc) return rc;
-    c->steps_since_bin += k * nsub;
+    HIPCHK_RC(advance_launch(c, a, 0, nsub, k * nsub, &iv));
     c->hframes += k * fpi;
     i0 += k;
   }

@@ -5,13 +5,16 @@
 // tags, launches are accesses over the band slots the device mapping gives
 // each part (swrt_share.hpp share_slot, the same function the kernels run)
 // — and prints one line per scenario: "<name> ok" when the checker's verdict
-// is the expected one.  Built (hipcc, host code only) and run by
+// is the expected one.  The rotation of the three packet sets is the library's
+// own (swrt_packet_state.hpp SetRing), and a last block drives its Binning
+// through the transitions the library makes.  Built (hipcc, host code only) and run by
 // tests/test_hazard_model.py; no GPU.
 #include <cstdio>
 #include <string>
 #include <vector>
 
 #include "../swraytracing_amd/csrc/swrt_hazard.hpp"
+#include "../swraytracing_amd/csrc/swrt_packet_state.hpp"
 
 using namespace swrt;
 
@@ -19,8 +22,7 @@ namespace {
 
 struct Proto {
   HazardChecker h;
-  int bufX[3] = {0, 1, 2};  // the three packet buffers (x stands for x, k, perm)
-  int in = 0, out = 1, park = 2;
+  SetRing<int> pk{0, 1, 2};  // the three packet sets (one tag stands for x, k, perm)
   int src = 10, counts = 11, fork = 20, join[3] = {21, 22, 23};
   int pending = 0;
   bool legacy = false;
@@ -39,7 +41,7 @@ struct Proto {
   bool rebin(bool do_join = true) {
     if (do_join) join_b();
     const uint64_t t = h.op(0);
-    bool ok = h.access(0, t, B(bufX[in]), kHzRead, HzRegion::all(), "rebin") &&
+    bool ok = h.access(0, t, B(pk.cur), kHzRead, HzRegion::all(), "rebin") &&
               h.access(0, t, B(counts), kHzWrite, HzRegion::all(), "rebin") &&
               h.access(0, t, B(src), kHzWrite, HzRegion::all(), "rebin");
     ++h.epoch;
@@ -55,35 +57,27 @@ struct Proto {
     for (int p = 0; p < S; ++p) {
       const uint64_t t = h.op(p);
       const HzRegion r = HzRegion::of_share(h.epoch, S > 1 ? TileShare{ntiles, p, S, rule} : TileShare{ntiles, -1, 1, 0});
-      bool ok = h.access(p, t, B(bufX[in]), kHzRead, sort ? HzRegion::all() : r, "part") &&
+      bool ok = h.access(p, t, B(pk.cur), kHzRead, sort ? HzRegion::all() : r, "part") &&
                 (!sort || h.access(p, t, B(src), kHzRead, r, "part")) &&
-                h.access(p, t, B(bufX[out]), kHzWrite, r, "part") &&
+                h.access(p, t, B(pk.out), kHzWrite, r, "part") &&
                 (!count_next || h.access(p, t, B(counts), kHzAtomic, HzRegion::all(), "part"));
       if (!ok) return false;
     }
     pending = S - 1;
-    if (sort && pending && !legacy) {  // park the gathered-from buffer
-      const int x = in;
-      in = out;
-      out = park;
-      park = x;
-    } else {
-      const int x = in;
-      in = out;
-      out = x;
-    }
+    if (sort && pending && !legacy) pk.park_cur();  // park the gathered-from buffer
+    else pk.flip();
     return true;
   }
   // a per-packet launch over every packet on the packet stream
   bool whole(bool do_join) {
     if (do_join) join_b();
     const uint64_t t = h.op(0);
-    return h.access(0, t, B(bufX[in]), kHzWrite, HzRegion::all(), "whole launch");
+    return h.access(0, t, B(pk.cur), kHzWrite, HzRegion::all(), "whole launch");
   }
 };
 
 int fails = 0;
-void expect(const char* name, bool got, bool want, const Proto& p) {
+void expect(const char* name, bool got, bool want, const Proto& p = Proto()) {
   if (got == want) {
     std::printf("%s ok\n", name);
   } else {
@@ -173,6 +167,61 @@ int main() {
     for (int s = 0; s < kHzStreams; ++s) p.h.sync(s);
     p.pending = 0;
     expect("whole_launch_after_host_sync", ok && p.whole(false), true, p);
+  }
+  {  // Binning: the host's picture of the device's binning (nx = 64: 16 tiles of 16 cells, 512 lanes)
+    const int64_t nx = 64;
+    const double dx = 0.1;
+    Binning b;
+    b.rebinned(16, 16, 512, true);
+    expect("binning_source_gather_pending_not_tiled", b.tiled_for(4), false);
+    b.tile_launched(true, nx, dx);
+    expect("binning_tiled_after_launch", b.tiled_for(4) && !b.tiled_for(3), true);
+    expect("binning_keys_valid_after_counting_launch", b.keys_valid_for(16, nx, dx), true);
+    expect("binning_keys_other_grid_or_bins",
+           b.keys_valid_for(16, 2 * nx, dx) || b.keys_valid_for(16, nx, 2 * dx) || b.keys_valid_for(9, nx, dx), false);
+    for (int how = 0; how < 4; ++how) {  // each of these makes the keys stale
+      Binning k = b;
+      if (how == 0) k.per_packet_launched();
+      if (how == 1) k.packets_replaced();
+      if (how == 2) k.invalidate();
+      if (how == 3) k.tile_launched(false, nx, dx);
+      expect(("binning_keys_stale_" + std::to_string(how)).c_str(), k.keys_valid_for(16, nx, dx), false);
+    }
+    // the count-memset guard: counts 4..15 still hold the 16-bin counting launch
+    b.invalidate();
+    b.rebinned(4, 32, 512, false);
+    expect("binning_memset_guard_larger_count", b.needs_count_memset(9) && !b.needs_count_memset(4), true);
+    b.rebinned(9, 22, 512, false);
+    expect("binning_memset_guard_after_rebin", !b.needs_count_memset(9) && b.needs_count_memset(16), true);
+    b.invalidate();  // (the device's counts are as the scan left them: the skip stays legitimate)
+    expect("binning_memset_skip_survives_invalidate", b.needs_count_memset(9), false);
+    // invalidate(): the queries about the binning answer as for a new context
+    b.rebinned(16, 16, 512, false);
+    b.tile_launched(true, nx, dx);
+    b.stepped(3);
+    b.ode23_sorted();
+    b.ode23_order_built();
+    b.invalidate();
+    const Binning fresh;
+    bool same = b.tiled_for(4) == fresh.tiled_for(4) && b.keys_valid_for(16, nx, dx) == fresh.keys_valid_for(16, nx, dx);
+    same = same && b.due(4) == fresh.due(4) && b.steps_left(4) == fresh.steps_left(4);
+    same = same && b.src_pending() == fresh.src_pending() && b.ode23_order() == fresh.ode23_order();
+    same = same && b.ode23_is_sorted() == fresh.ode23_is_sorted() && !b.tiled_for(4) && b.due(4);
+    expect("binning_invalidate_as_constructed", same, true);
+    // the re-binning cadence
+    b.rebinned(16, 16, 512, true);
+    b.stepped(3);
+    expect("binning_cadence", !b.due(4) && b.steps_left(4) == 1, true);
+    b.stepped(1);
+    expect("binning_due_after_cycle", b.due(4), true);
+  }
+  {  // SetRing: the two rotations
+    SetRing<int> r{0, 1, 2};
+    r.flip();
+    bool ok = r.cur == 1 && r.out == 0 && r.park == 2;
+    r.park_cur();
+    ok = ok && r.cur == 0 && r.out == 2 && r.park == 1;
+    expect("set_ring_rotations", ok, true);
   }
   std::printf("%s\n", fails ? "FAILED" : "ALL OK");
   return fails ? 1 : 0;

@@ -402,6 +402,39 @@ def test_spatial_binning_is_invisible(ctx, oracle_lib, qg_case, rebin_every, til
     np.testing.assert_array_equal(hkg, hko)
 
 
+def test_rebinning_clears_stale_counts(fresh_ctx, oracle_lib, qg_case):
+    """The re-binning's count memset is skipped only over counts the last scan
+    zeroed.  One ensemble through binnings of 16, 4, 9, 9 and 16 bins: the
+    16-tile launch that ends the first cycle writes the next counts, which
+    nothing consumes; the 9-bin re-binning after the 4-bin one would count on
+    top of its entries 4..8 without the memset (the scan's device check then
+    reports a corrupted binning); the second 9-bin re-binning skips the memset
+    legitimately; the last meets the stale entries 9..15."""
+    c = qg_case
+    nx, L, ctx = c["nx"], c["L"], fresh_ctx
+    pl = _planes(c["flow"])
+    # every one of the forced tile kernel's 4 x 4 tiles holds packets, so the stale counts are non-zero
+    cell = np.floor(np.mod(c["x"], L) / (L / nx)).astype(int) // 16
+    assert np.bincount(cell[:, 0] * 4 + cell[:, 1], minlength=16).min() >= 1
+    ctx.set_field_grid(0, pl, nx, L)
+    ctx.packets_set(c["x"], c["k"])
+    try:
+        for kernel, tile in [(2, 0), (1, 32), (None, 22), (None, 22), (2, 0)]:
+            if kernel is not None:
+                ctx.set_kernel(kernel)
+            ctx.set_locality(4, tile)
+            ctx.advance(c["dt"], 4, c["f"], 1.0, bump=orc.BUMP_SW)
+        ctx.synchronize()
+        xg, kg = ctx.packets_get()
+    finally:
+        ctx.set_kernel(0)
+        ctx.set_locality(4, 0)
+    xo, ko, _, _ = oracle_lib.leapfrog(pl, None, 0, 0, nx, nx, L / nx, orc.BUMP_SW, c["x"], c["k"], c["dt"], 20,
+                                       c["f"], 1.0)
+    np.testing.assert_array_equal(xg, xo)
+    np.testing.assert_array_equal(kg, ko)
+
+
 @pytest.mark.parametrize("variant", [1, 2])
 @pytest.mark.parametrize("nslots", [1, 2])
 @pytest.mark.parametrize("dt_scale", [1.0, 40.0])

@@ -25,3 +25,11 @@ def test_hazard_checker_model(tmp_path):
     assert "skewed_cycle_end_reported ok" in r.stdout and "consistent_skew_silent ok" in r.stdout
     assert "share_partitions_slots ok" in r.stdout
     assert "sort launch" in r.stdout or "part" in r.stdout
+    # the library's own packet-set rotation and Binning transitions (swrt_packet_state.hpp)
+    for name in ("set_ring_rotations", "binning_source_gather_pending_not_tiled", "binning_tiled_after_launch",
+                 "binning_keys_valid_after_counting_launch", "binning_keys_other_grid_or_bins",
+                 "binning_keys_stale_0", "binning_keys_stale_1", "binning_keys_stale_2", "binning_keys_stale_3",
+                 "binning_memset_guard_larger_count", "binning_memset_guard_after_rebin",
+                 "binning_memset_skip_survives_invalidate", "binning_invalidate_as_constructed",
+                 "binning_cadence", "binning_due_after_cycle"):
+        assert name + " ok" in r.stdout, r.stdout
