@@ -305,6 +305,64 @@ int swrt_omega_histogram(swrt_ctx* ctx, double f, double Cg, const double* edges
                          int64_t* counts_inout, double* mean_omega_out);
 
 /* ---------------------------------------------------------------------------
+ * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
+ * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)
+ * ------------------------------------------------------------------------ */
+
+/* One pass over the device-resident packets, no trajectory download.  Per
+ * packet, with U and grad U at x the bits swrt_eval gives there (slot 0, or
+ * (1-alpha)*slot 0 + alpha*slot 1 when nslots == 2; bump: Lagrange bump), in
+ * this operation order:
+ *   Omega = sqrt(f^2 + gH*(k*k + l*l)) + (u*k + v*l)   omega(k) + dot(U, k)
+ *                                                     (symplectic_full_fourier.m:41,55)
+ *   zeta  = v_x - u_y                                  (RaytracingScheme.m:20)
+ *   sigma = sqrt((u_x - v_y)^2 + (v_x + u_y)^2)        (RaytracingScheme.m:25)
+ *   D     = v_y^2 + v_x*u_y                            (RaytracingScheme.m:30, as written there)
+ * Both square roots are IEEE correctly rounded for every argument, zero and
+ * subnormals included.
+ * A frame is eight doubles [n, max|r|, sum r, sum r^2, sum omega, sum zeta,
+ * sum sigma, sum D], omega = sqrt(f^2 + gH*|k|^2) and r = (Omega - Omega_0) /
+ * Omega_0 (symplectic_full_fourier.m:56): sums, not means, so the frames of
+ * shards combine by adding the sums and taking the max of entry 1.  Omega_0
+ * and everything a packet leaves are kept by the original packet index, and
+ * the sums run over that index (per-workgroup partials of a fixed grid,
+ * combined in block order): a frame depends on the packets alone, not on the
+ * binning's storage order, so two calls on the same state, two contexts
+ * holding the same packets, or a re-binning between the mark and a sample
+ * all give the same bits.
+ * Every call is ordered after whatever last wrote the packets (both packet
+ * streams, the ode23 attempts) and after the snapshot writes of the slots it
+ * reads.  Errors: nslots not 1 or 2, an unset slot, two grids, no packets, a
+ * NULL buffer where one is required: SWRT_ERR_ARG with a message.
+ * swrt_packets_set with a different N drops the mark and the series. */
+
+/* Omega_0 of every packet at the current state (Omega_0 of
+ * symplectic_full_fourier.m:41, SW_zero_background_raytracing.m:57).  Queued on
+ * the packet stream; reserves the buffers the later calls use. */
+int swrt_raydiag_mark(swrt_ctx* ctx, double f, double gH, int nslots, double alpha, double bump);
+
+/* Sample the current state, synchronously.  sample4_out (may be NULL): N x 4
+ * column-major [Omega zeta sigma D] in the original packet order.  frame8_out
+ * (may be NULL): the frame.  Without a mark r and frame entries 1..3 are 0. */
+int swrt_raydiag_sample(swrt_ctx* ctx, double f, double gH, int nslots, double alpha, double bump,
+                        double* sample4_out, double* frame8_out);
+
+/* Append the frame of the current state to a series kept on the device
+ * (solver_error against time, symplectic_full_fourier.m:54-57): queued on the
+ * packet stream, the host does not wait for it.  Capacity: swrt_raydiag_mark
+ * (or the first record of an ensemble without one) reserves the per-packet
+ * buffers and 4096 frames; a record that finds the series full doubles it,
+ * and only those calls may wait for the stream. */
+int swrt_raydiag_record(swrt_ctx* ctx, double f, double gH, int nslots, double alpha, double bump);
+
+/* Frames recorded since the last reset; frames [first, first + count) into
+ * frames8_out (8 doubles each, frame-major; waits for them); empty the series.
+ * As swrt_history_frames / _get / _reset. */
+int64_t swrt_raydiag_frames(const swrt_ctx* ctx);
+int swrt_raydiag_series_get(swrt_ctx* ctx, int64_t first, int64_t count, double* frames8_out);
+int swrt_raydiag_series_reset(swrt_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * ode23 packet integrator (the drivers' integrator)
  * ------------------------------------------------------------------------ */
 

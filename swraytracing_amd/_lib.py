@@ -84,6 +84,12 @@ SIGNATURES = {
     "swrt_spectral_eval": (_INT, [_VP, _P, _P, _I, _INT, _P]),
     "swrt_spectral_leapfrog": (_INT, [_VP, _P, _P, _I, _D, _I, _D, _D, _INT]),
     "swrt_omega_histogram": (_INT, [_VP, _D, _D, _P, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_D)]),
+    "swrt_raydiag_mark": (_INT, [_VP, _D, _D, _INT, _D, _D]),
+    "swrt_raydiag_sample": (_INT, [_VP, _D, _D, _INT, _D, _D, _P, _P]),
+    "swrt_raydiag_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
+    "swrt_raydiag_frames": (_I, [_VP]),
+    "swrt_raydiag_series_get": (_INT, [_VP, _I, _I, _P]),
+    "swrt_raydiag_series_reset": (_INT, [_VP]),
     "swrt_ode23_f1": (_INT, [_VP, _D, _D, _D, _D, _INT, _D, _D, ctypes.POINTER(_D)]),
     "swrt_ode23_attempt": (_INT, [_VP, _D, _D, _D, _D, _D, _D, _INT, _D, _D, ctypes.POINTER(_D)]),
     "swrt_ode23_accept": (_INT, [_VP]),
@@ -492,6 +498,43 @@ class Context:
                                                counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                                ctypes.byref(mean)), "swrt_omega_histogram")
         return counts, mean.value
+
+    # ---- the invariant and the flow along the rays (swrt_raydiag_*) ----------
+    def raydiag_mark(self, f, gH, nslots=1, alpha=0.0, bump=1e-13):
+        """Keep Omega_0 = omega(k) + U(x).k of every packet at the current state
+        (symplectic_full_fourier.m:41)."""
+        self._chk(self._L.swrt_raydiag_mark(self._h, float(f), float(gH), int(nslots), float(alpha), float(bump)),
+                  "swrt_raydiag_mark")
+
+    def raydiag_sample(self, f, gH, nslots=1, alpha=0.0, bump=1e-13, values=True):
+        """-> (N x 4 [Omega zeta sigma D] in the original packet order, or None
+        without ``values``; the frame [n, max|r|, sum r, sum r^2, sum omega,
+        sum zeta, sum sigma, sum D]).  Synchronous."""
+        n = self.packets_count()
+        s4 = np.empty((n, 4), order="F") if values else None
+        fr = np.empty(8)
+        self._chk(self._L.swrt_raydiag_sample(self._h, float(f), float(gH), int(nslots), float(alpha), float(bump),
+                                              _p(s4), _p(fr)), "swrt_raydiag_sample")
+        return s4, fr
+
+    def raydiag_record(self, f, gH, nslots=1, alpha=0.0, bump=1e-13):
+        """Append the current state's frame to the device-side series (queued; no host wait)."""
+        self._chk(self._L.swrt_raydiag_record(self._h, float(f), float(gH), int(nslots), float(alpha), float(bump)),
+                  "swrt_raydiag_record")
+
+    def raydiag_frames(self):
+        return int(self._L.swrt_raydiag_frames(self._h))
+
+    def raydiag_series(self, first=0, count=None):
+        """Recorded frames [first, first + count) as a (count, 8) array."""
+        count = self.raydiag_frames() - first if count is None else count
+        out = np.empty((max(count, 0), 8))
+        self._chk(self._L.swrt_raydiag_series_get(self._h, int(first), int(count), _p(out)),
+                  "swrt_raydiag_series_get")
+        return out
+
+    def raydiag_series_reset(self):
+        self._chk(self._L.swrt_raydiag_series_reset(self._h), "swrt_raydiag_series_reset")
 
     # ---- ode23 device stages (swrt_ode23_*) --------------------------------
     def ode23_f1(self, t, tmax, f, Cg, nslots, thr, bump):

@@ -27,6 +27,7 @@
 #include "swrt_spectral.hpp"
 #include "swrt_hazard.hpp"
 #include "swrt_diag.hpp"
+#include "swrt_raydiag.hpp"
 #include "swrt_res.hpp"
 
 using namespace swrt;
@@ -432,6 +433,7 @@ int swrt_packets_set(swrt_ctx* c, const double* x, const double* k, int64_t n) {
     c->cap = n;
   }
   if (!c->bins.buf) HIPCHK(c, c->bins.alloc());
+  if (n != c->n) c->rd.drop();  // Omega_0 and the frame series belong to an ensemble of the old size
   c->n = n;
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(c->pk.cur.x.get(), x, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
@@ -1077,6 +1079,159 @@ int swrt_omega_histogram(swrt_ctx* c, double f, double Cg, const double* edges, 
   if (mean_omega_out) *mean_omega_out = mean;
   return SWRT_OK;
   GUARD_END(c)
+}
+
+// ---- ray diagnostics (swrt_raydiag.hpp) ----
+// The three calls' common checks: SWRT_ERR_ARG with a message, as the header says.
+static int raydiag_check(swrt_ctx* c, int nslots) {
+  HIPCHK_RC(lost_check(c));
+  if (nslots != 1 && nslots != 2) return fail(c, SWRT_ERR_ARG, "nslots must be 1 or 2");
+  for (int s = 0; s < nslots; ++s)
+    if (!c->slot[s].set) return fail(c, SWRT_ERR_ARG, "field slot not set");
+  if (nslots == 2 && (c->slot[1].nx != c->slot[0].nx || c->slot[1].L != c->slot[0].L ||
+                      c->slot[1].ny_period != c->slot[0].ny_period))
+    return fail(c, SWRT_ERR_ARG, "slots 0 and 1 have different grids");
+  if (c->n == 0) return fail(c, SWRT_ERR_ARG, "no packets (swrt_packets_set first)");
+  return SWRT_OK;
+}
+
+constexpr int64_t kRayDiagSeriesMin = 4096;  // frames reserved by the mark or the first record (256 KiB)
+
+// The per-packet buffers for the current ensemble and room for `extra` more
+// frames.  Growing the series keeps the recorded frames and waits for the
+// stream (the old buffer may still be written by a queued record).
+static int raydiag_reserve(swrt_ctx* c, int64_t extra) {
+  RayDiagState& rd = c->rd;
+  if (!rd.partial) HIPCHK(c, rd.partial.alloc(kRayDiagStats * kRayDiagBlocks + kRayDiagFrame));
+  if (c->n > rd.pcap) {  // (a larger ensemble: swrt_packets_set dropped the mark; releasing waits for queued readers)
+    rd.pcap = 0;
+    rd.marked = false;
+    HIPCHK(c, rd.omega0.alloc(c->n));
+    HIPCHK(c, rd.rec.alloc(kRayDiagRec * c->n));
+    rd.pcap = c->n;
+  }
+  if (rd.frames + extra <= rd.cap) return SWRT_OK;
+  const int64_t ncap = std::max<int64_t>({kRayDiagSeriesMin, 2 * rd.cap, rd.frames + extra});
+  DevBuf<double> ns;
+  HIPCHK(c, ns.alloc(kRayDiagFrame * ncap));
+  if (rd.frames > 0)
+    HIPCHK(c, hipMemcpyAsync(ns.get(), rd.series.get(), sizeof(double) * kRayDiagFrame * rd.frames,
+                             hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  hz_synced(c);
+  rd.series = std::move(ns);
+  rd.cap = ncap;
+  return SWRT_OK;
+}
+
+// One pass over the packets on the context's stream: the mark, or a sample
+// (then the reduction over its records) whose frame goes to `frame` (device)
+// and whose N x 4 values go to `sample4` (device, may be NULL).
+static int raydiag_launch(swrt_ctx* c, bool mark, double f, double gH, int nslots, double alpha, double bump,
+                          double* sample4, double* frame) {
+  RayDiagState& rd = c->rd;
+  RayDiagArgs a;
+  a.f0 = view_of(c->slot[0]);
+  a.f1 = nslots == 2 ? view_of(c->slot[1]) : a.f0;
+  a.nslots = nslots;
+  a.alpha = alpha;
+  a.bump = bump;
+  a.x = c->pk.cur.x.get();
+  a.k = c->pk.cur.k.get();
+  a.perm = c->pk.cur.perm.get();
+  a.n = c->n;
+  a.f2 = f * f;
+  a.gH = gH;
+  a.omega0 = (mark || rd.marked) ? rd.omega0.get() : nullptr;
+  a.sample4 = sample4;
+  a.rec = rd.rec.get();
+  const dim3 grid(nblocks(c->n, kRayDiagThreads)), block(kRayDiagThreads);
+  hipLaunchKernelGGL(mark ? ray_diag_kernel<true> : ray_diag_kernel<false>, grid, block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  if (mark) return SWRT_OK;
+  const int nblk = (int)std::min<int64_t>(kRayDiagBlocks, grid.x);
+  hipLaunchKernelGGL(ray_diag_reduce_kernel, dim3(nblk), block, 0, c->stream, rd.rec.get(), c->n, rd.partial.get());
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(ray_diag_frame_kernel, dim3(1), dim3(64), 0, c->stream, rd.partial.get(), nblk, c->n, frame);
+  HIPCHK(c, hipGetLastError());
+  return SWRT_OK;
+}
+
+int swrt_raydiag_mark(swrt_ctx* c, double f, double gH, int nslots, double alpha, double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c);
+  HIPCHK_RC(raydiag_check(c, nslots));
+  HIPCHK(c, hipSetDevice(c->device));
+  RayDiagState& rd = c->rd;
+  rd.marked = false;
+  HIPCHK_RC(raydiag_reserve(c, 1));
+  HIPCHK_RC(raydiag_launch(c, true, f, gH, nslots, alpha, bump, nullptr, nullptr));
+  rd.marked = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_raydiag_sample(swrt_ctx* c, double f, double gH, int nslots, double alpha, double bump,
+                        double* sample4_out, double* frame8_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c);
+  HIPCHK_RC(raydiag_check(c, nslots));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(raydiag_reserve(c, 0));
+  double* dsample = nullptr;
+  if (sample4_out) {
+    HIPCHK_RC(ensure_scratch(c, sizeof(double) * 4 * c->n));
+    dsample = (double*)c->scratch.get();
+  }
+  double* dframe = c->rd.partial.get() + kRayDiagStats * kRayDiagBlocks;
+  HIPCHK_RC(raydiag_launch(c, false, f, gH, nslots, alpha, bump, dsample, dframe));
+  if (sample4_out)
+    HIPCHK(c, hipMemcpyAsync(sample4_out, dsample, sizeof(double) * 4 * c->n, hipMemcpyDeviceToHost, c->stream));
+  if (frame8_out)
+    HIPCHK(c, hipMemcpyAsync(frame8_out, dframe, sizeof(double) * kRayDiagFrame, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return dev_err_check(c);
+  GUARD_END(c)
+}
+
+int swrt_raydiag_record(swrt_ctx* c, double f, double gH, int nslots, double alpha, double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c);
+  HIPCHK_RC(raydiag_check(c, nslots));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(raydiag_reserve(c, 1));
+  HIPCHK_RC(raydiag_launch(c, false, f, gH, nslots, alpha, bump, nullptr,
+                           c->rd.series.get() + kRayDiagFrame * c->rd.frames));
+  ++c->rd.frames;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int64_t swrt_raydiag_frames(const swrt_ctx* c) { return c ? c->rd.frames : -1; }
+
+int swrt_raydiag_series_get(swrt_ctx* c, int64_t first, int64_t count, double* frames8_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  if (first < 0 || count < 0 || first + count > c->rd.frames)
+    return fail(c, SWRT_ERR_ARG, "frame range out of bounds");
+  if (count == 0) return SWRT_OK;
+  if (!frames8_out) return fail(c, SWRT_ERR_ARG, "NULL buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(frames8_out, c->rd.series.get() + kRayDiagFrame * first,
+                           sizeof(double) * kRayDiagFrame * count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return dev_err_check(c);
+  GUARD_END(c)
+}
+
+int swrt_raydiag_series_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (conservative: settings and syncs may precede packet-stream work)
+  c->rd.frames = 0;
+  return SWRT_OK;
 }
 
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {

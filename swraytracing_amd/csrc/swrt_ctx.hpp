@@ -294,6 +294,24 @@ struct SnapshotImport {
   Event ev[2];
 };
 
+// ray diagnostics (swrt_raydiag.hpp): the mark and the recorded frame series.
+// Buffers of their own, not the context's scratch: a recorded frame is queued
+// without a host wait, and a later call may reallocate the scratch.
+struct RayDiagState {
+  DevBuf<double> omega0;   // Omega_0 by original packet index (swrt_raydiag_mark)
+  DevBuf<double> rec;      // kRayDiagRec doubles per packet, original order: what a sample's reduction reads
+  int64_t pcap = 0;        // packets omega0 and rec are sized for
+  bool marked = false;
+  DevBuf<double> partial;  // kRayDiagStats x kRayDiagBlocks workgroup partials, then one frame
+  DevBuf<double> series;   // recorded frames, kRayDiagFrame doubles each
+  int64_t frames = 0;
+  int64_t cap = 0;         // frames allocated
+  void drop() {            // the ensemble changed size: the mark and the series describe another one
+    marked = false;
+    frames = 0;
+  }
+};
+
 // debug knobs (swrt_debug_set): a spin kernel queued on every extra packet
 // stream before each of its part launches (adversarial overlap of consecutive
 // calls), and the pre-third-buffer ordering after a source-gather sort
@@ -370,6 +388,7 @@ struct swrt_ctx {
   SpectralState spec;
   QGState qg;
   Ode23State o23;
+  RayDiagState rd;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an
   // event marker, ~7 us of idle on each stream).  Only consecutive split

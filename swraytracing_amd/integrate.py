@@ -23,11 +23,31 @@ def _omega(k, f, gH):
     return np.sqrt(f ** 2 + gH * np.sum(k * k, axis=1, keepdims=True))
 
 
-def ode_symplectic(x0, k0, dt, T, f, gH, scheme):
+def combine_frames(frames):
+    """The frame of an ensemble from its shards' frames (swrt_raydiag_*:
+    [n, max|r|, sum r, sum r^2, sum omega, sum zeta, sum sigma, sum D]): the
+    sums add, entry 1 is the max.  ``frames``: a sequence of (8,) frames or of
+    (T, 8) series, one per shard; a shard without packets (n = 0, all zeros)
+    changes nothing."""
+    fr = np.asarray(frames, dtype=np.float64)
+    if fr.ndim < 2 or fr.shape[-1] != 8:
+        raise ValueError("frames must be (shards, 8) or (shards, T, 8)")
+    out = fr.sum(axis=0)
+    out[..., 1] = fr[..., 1].max(axis=0)
+    return out
+
+
+def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False):
     """[x, k, t] = ode_symplectic(x0, k0, dt, T, f, gH, scheme).
 
     x0, k0: 1 x 2 x P.  Returns x, k: Nsteps x 2 x P (row 1 = initial state)
-    and t: (Nsteps,) with t(i) = (i-1)*dt (ode_symplectic.m:2-8,23-28)."""
+    and t: (Nsteps,) with t(i) = (i-1)*dt (ode_symplectic.m:2-8,23-28).
+
+    ``diagnostics`` (GPU-backed schemes): a fourth value, the (Nsteps x 8)
+    series of swrt_raydiag frames — row i belongs to x[i], k[i]; row 0 is the
+    initial state, where Omega_0 is marked (symplectic_full_fourier.m:41,54-57:
+    solver_error against t).  The packets then advance one step per call with
+    a frame recorded on the device after each; x, k and t are the same bits."""
     x0 = np.asarray(x0, dtype=np.float64)
     k0 = np.asarray(k0, dtype=np.float64)
     if x0.ndim == 2:
@@ -38,21 +58,37 @@ def ode_symplectic(x0, k0, dt, T, f, gH, scheme):
     x = np.zeros((Nsteps, 2, P))
     k = np.zeros((Nsteps, 2, P))
     t = np.arange(Nsteps, dtype=np.float64) * dt
+    gpu = isinstance(scheme, (SpectralScheme, SnapshotPairScheme))
+    if diagnostics and not gpu:
+        raise ValueError("diagnostics needs a GPU-backed scheme (SpectralScheme / SnapshotPairScheme)")
     if Nsteps == 0:
-        return x, k, t
+        return (x, k, t, np.zeros((0, 8))) if diagnostics else (x, k, t)
     x[0] = x0[0]
     k[0] = k0[0]
-    if Nsteps == 1:
+    if Nsteps == 1 and not diagnostics:
         return x, k, t
-    if isinstance(scheme, (SpectralScheme, SnapshotPairScheme)):
+    if gpu:
         nslots = 1 if isinstance(scheme, SpectralScheme) else 2
         xs = np.asfortranarray(x0[0].T)  # P x 2
         ks = np.asfortranarray(k0[0].T)
-        _, _, hx, hk = scheme.ctx.leapfrog(xs, ks, dt, Nsteps - 1, f, gH, nslots=nslots, alpha0=0.0,
-                                           dalpha=0.0, bump=scheme.bump, save_every=1)
-        x[1:] = hx
-        k[1:] = hk
-        return x, k, t
+        ctx = scheme.ctx
+        if not diagnostics:
+            _, _, hx, hk = ctx.leapfrog(xs, ks, dt, Nsteps - 1, f, gH, nslots=nslots, alpha0=0.0,
+                                        dalpha=0.0, bump=scheme.bump, save_every=1)
+            x[1:] = hx
+            k[1:] = hk
+            return x, k, t
+        phys = dict(nslots=nslots, alpha=0.0, bump=scheme.bump)
+        ctx.packets_set(xs, ks)  # (starts a new history)
+        ctx.raydiag_series_reset()
+        ctx.raydiag_mark(f, gH, **phys)
+        ctx.raydiag_record(f, gH, **phys)
+        for _ in range(Nsteps - 1):
+            ctx.advance(dt, 1, f, gH, nslots=nslots, alpha0=0.0, dalpha=0.0, bump=scheme.bump, save_every=1)
+            ctx.raydiag_record(f, gH, **phys)
+        if Nsteps > 1:
+            x[1:], k[1:] = ctx.history()
+        return x, k, t, ctx.raydiag_series()
     # generic host path (arbitrary RaytracingScheme)
     xc, kc = x0.copy(), k0.copy()
 
@@ -278,6 +314,21 @@ class PacketEnsemble:
         return ode23_packets(ctx, (0.0, dt), dt, self.f, self.Cg, nslots=2, rtol=rtol, atol=atol,
                              bump=self.bump, allreduce_max=allreduce_max, stats=stats, controller=controller,
                              hook=hook)
+
+    def mark_invariant(self, alpha=0.0):
+        """Keep Omega_0 = omega(k) + U(x).k of this shard's packets at the
+        current state, U from the snapshot pair at ``alpha``
+        (symplectic_full_fourier.m:41)."""
+        if self.n > 0:
+            self.ctx.raydiag_mark(self.f, self.gH, nslots=2, alpha=alpha, bump=self.bump)
+
+    def record_diagnostics(self, alpha):
+        """Append this shard's frame at the current state to the device-side
+        series (Context.raydiag_series; queued, no host wait).  The ensemble's
+        frames are combine_frames() of the shards' series; an empty shard
+        records nothing and stands there as zeros (n = 0)."""
+        if self.n > 0:
+            self.ctx.raydiag_record(self.f, self.gH, nslots=2, alpha=alpha, bump=self.bump)
 
     def state(self):
         return self.ctx.packets_get()
