@@ -355,6 +355,15 @@ int swrt_raydiag_sample(swrt_ctx* ctx, double f, double gH, int nslots, double a
  * and only those calls may wait for the stream. */
 int swrt_raydiag_record(swrt_ctx* ctx, double f, double gH, int nslots, double alpha, double bump);
 
+/* swrt_raydiag_record for history frames [first, first + count) instead of
+ * the current state (the frames of swrt_advance or swrt_ode23_run_at): one
+ * series frame per history frame, frame i with the snapshot blend alphas[i]
+ * (alphas may be NULL when nslots == 1) — solver_error at every output time
+ * (SW_zero_background_raytracing.m:85-87) without a download.  The same bits
+ * as swrt_raydiag_sample on packets set to that frame. */
+int swrt_raydiag_record_history(swrt_ctx* ctx, int64_t first, int64_t count, double f, double gH, int nslots,
+                                const double* alphas, double bump);
+
 /* Frames recorded since the last reset; frames [first, first + count) into
  * frames8_out (8 doubles each, frame-major; waits for them); empty the series.
  * As swrt_history_frames / _get / _reset. */
@@ -382,6 +391,28 @@ int swrt_ode23_f1(swrt_ctx* ctx, double t, double tmax, double f, double Cg, int
 int swrt_ode23_attempt(swrt_ctx* ctx, double t, double h, double tnew, double tmax, double f, double Cg,
                        int nslots, double thr, double bump, double* err_raw_out);
 int swrt_ode23_accept(swrt_ctx* ctx);
+/* Output at requested times (MATLAB ode23 with numel(tspan) > 2: the steps are
+ * chosen as ever, the solution at the requested times is ntrp23 inside the
+ * accepted steps).
+ * swrt_ode23_set_dense: on = 1 makes swrt_ode23_attempt keep the stage
+ *   derivatives F2 and F3 in device memory (the fused attempt otherwise never
+ *   writes them); default 0.  swrt_ode23_run* ignore it.
+ * swrt_ode23_ntrp: between such an attempt of the step from t to tnew and
+ *   swrt_ode23_accept, appends nout history frames (swrt_history_*: the layout
+ *   of swrt_advance's frames, original packet order), frame i the solution at
+ *   tout[i], each within [t, tnew].  A time equal to tnew bit for bit gives
+ *   ynew itself; any other, per component and in this operation order with
+ *   h = tnew - t, s = (tout[i] - t)/h, s2 = s*s, s3 = s2*s,
+ *     c1 = F1*(h*1)
+ *     c2 = ((F1*(h*(-4/3)) + F2*(h*1))      + F3*(h*(4/3)))  + F4*(h*(-1))
+ *     c3 = ((F1*(h*(5/9))  + F2*(h*(-2/3))) + F3*(h*(-8/9))) + F4*(h*1)
+ *     yi = y + ((c1*s + c2*s2) + c3*s3)
+ *   (ntrp23's BI; MATLAB's own BLAS order is unpinned, as its ode23 is).
+ *   Without a dense attempt in the buffers — none made, already accepted, or
+ *   another call that may touch the packets since — SWRT_ERR_STATE with a
+ *   message.  Queued on the packet stream; may grow the history. */
+int swrt_ode23_set_dense(swrt_ctx* ctx, int on);
+int swrt_ode23_ntrp(swrt_ctx* ctx, double t, double tnew, const double* tout, int64_t nout);
 /* [~, y] = ode23(odefun, [t0 tfinal], y) for the device-resident packets with
  * MATLAB's controller (RelTol rtol, AbsTol atol, MaxStep 0.1*|tfinal - t0|,
  * max-norm error, initial-step heuristic, step update) in the library: the
@@ -396,6 +427,25 @@ int swrt_ode23_accept(swrt_ctx* ctx);
 int swrt_ode23_run(swrt_ctx* ctx, double t0, double tfinal, double tmax, double f, double Cg, int nslots,
                    double rtol, double atol, double bump, double* ts_out, int64_t ts_cap, int64_t* nts_out,
                    int64_t* stats3_out);
+/* [t, y] = ode23(odefun, tspan, y) for a tspan of nt >= 2 times, strictly
+ * increasing or strictly decreasing (SW_zero_background_raytracing.m:69-87):
+ * the whole call in the library.  t0 = tspan[0], tfinal = tspan[nt-1], MaxStep
+ * 0.1*|tfinal - t0|; the first output gap |tspan[1] - tspan[0]| bounds the
+ * initial step only (odearguments' htspan), and the output times influence
+ * nothing else.  After each accepted step the solution at every tspan entry
+ * it reaches is appended to the history (swrt_ode23_ntrp's frames): nt - 1
+ * frames, for tspan[1..], their capacity reserved up front.  The packets are
+ * left at y(tfinal), the last frame.  Plain launches on the packet stream, one
+ * attempt at a time; the packets are re-binned every few accepted steps (stage
+ * 1 recomputed at the current time gives the FSAL derivative bit for bit, so
+ * the results do not depend on that cadence).  ts_out / ts_cap / nts_out /
+ * stats3_out as in swrt_ode23_run.  Below hmin: SWRT_ERR_STATE, the packets at
+ * the last accepted time, the frames emitted so far kept and counted.  Errors:
+ * nt < 2, a tspan that is not strictly monotonic or not finite, NULL buffers:
+ * SWRT_ERR_ARG with a message.  Single rank (no reduce callback). */
+int swrt_ode23_run_at(swrt_ctx* ctx, const double* tspan, int64_t nt, double tmax, double f, double Cg, int nslots,
+                      double rtol, double atol, double bump, double* ts_out, int64_t ts_cap, int64_t* nts_out,
+                      int64_t* stats3_out);
 /* swrt_ode23_run with a host hook: hook(hook_user) is called once, after
  * stage 1 and the first attempt are queued and before the host first waits
  * on the device — host work placed there (the drivers queue the next QG step,
@@ -673,7 +723,12 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
  *   ran as two part launches on the two packet streams.
  * SWRT_DEBUG_ODE23_FIRST_CHAINED (get only): ode23 calls that took the first
  *   step size and first attempt the previous call queued behind their chained
- *   stage 1 (t0 = 0, tfinal = tmax and RelTol as that call assumed). */
+ *   stage 1 (t0 = 0, tfinal = tmax and RelTol as that call assumed).
+ * SWRT_DEBUG_ODE23_DENSE_REBIN n (default 8): swrt_ode23_run_at re-bins the
+ *   packets every n accepted steps (0: never inside a run); speed only, the
+ *   same bits for every n.
+ * SWRT_DEBUG_ODE23_DENSE_REBINS (get only): the re-binnings swrt_ode23_run_at
+ *   made inside its runs. */
 #define SWRT_DEBUG_HAZARD_CHECK 1
 #define SWRT_DEBUG_SPIN_US 2
 #define SWRT_DEBUG_LEGACY_PARK 3
@@ -687,6 +742,8 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
 #define SWRT_DEBUG_ODE23_GUESSES_TAKEN 12
 #define SWRT_DEBUG_ODE23_SPLIT_RUNS 13
 #define SWRT_DEBUG_ODE23_FIRST_CHAINED 14
+#define SWRT_DEBUG_ODE23_DENSE_REBIN 15
+#define SWRT_DEBUG_ODE23_DENSE_REBINS 16
 int swrt_debug_set(swrt_ctx* ctx, int key, int64_t value);
 int swrt_debug_get(swrt_ctx* ctx, int key, int64_t* value_out);
 

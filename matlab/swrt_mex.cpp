@@ -33,6 +33,9 @@
 //   rh  = swrt_mex('ode23_f1', h, t, tmax, f, Cg, nslots, thr, bump)       % ode23_packets_gpu.m
 //   err = swrt_mex('ode23_attempt', h, t, hstep, tnew, tmax, f, Cg, nslots, thr, bump)
 //   swrt_mex('ode23_accept', h)
+//   swrt_mex('ode23_set_dense', h, on)                        % ode23_attempt keeps F2, F3 (vector tspan)
+//   swrt_mex('ode23_ntrp', h, t, tnew, tout)                  % history frames at tout inside the step
+//   [hx, hk] = swrt_mex('history', h);  swrt_mex('history_reset', h)   % N x 2 x frames each
 //   swrt_mex('qg_init', h, params_struct, qk)   % qk (2kmax+1) x (kmax+1) [x 2], complex
 //   swrt_mex('qg_step', h, dt, nsteps);  U0 = swrt_mex('qg_max_speed', h);
 //   [qk, t, steps] = swrt_mex('qg_get', h, nx, nlayers);  q = swrt_mex('qg_get_q', h, nx, nlayers);
@@ -310,6 +313,30 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   if (!strcmp(cmd, "ode23_accept")) {
     check(c, swrt_ode23_accept(c), "swrt_ode23_accept");
+    return;
+  }
+  if (!strcmp(cmd, "ode23_set_dense")) {  // (on)
+    need(na, 2, cmd);
+    check(c, swrt_ode23_set_dense(c, (int)scalar(a[1])), "swrt_ode23_set_dense");
+    return;
+  }
+  if (!strcmp(cmd, "ode23_ntrp")) {  // (t, tnew, tout): one history frame per time in tout
+    need(na, 4, cmd);
+    check(c, swrt_ode23_ntrp(c, scalar(a[1]), scalar(a[2]), reals(a[3], "tout"),
+                             (int64_t)mxGetNumberOfElements(a[3])),
+          "swrt_ode23_ntrp");
+    return;
+  }
+  if (!strcmp(cmd, "history")) {  // -> hx, hk: N x 2 x frames
+    const int64_t n = swrt_packets_count(c), nf = swrt_history_frames(c);
+    const mwSize dims[3] = {(mwSize)n, 2, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    plhs[1] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    check(c, swrt_history_get(c, 0, nf, mxGetDoubles(plhs[0]), mxGetDoubles(plhs[1])), "swrt_history_get");
+    return;
+  }
+  if (!strcmp(cmd, "history_reset")) {
+    check(c, swrt_history_reset(c), "swrt_history_reset");
     return;
   }
   if (!strcmp(cmd, "qg_init")) {  // (params struct, qk complex (2kmax+1) x (kmax+1) [x nlayers])

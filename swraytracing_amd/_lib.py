@@ -87,14 +87,19 @@ SIGNATURES = {
     "swrt_raydiag_mark": (_INT, [_VP, _D, _D, _INT, _D, _D]),
     "swrt_raydiag_sample": (_INT, [_VP, _D, _D, _INT, _D, _D, _P, _P]),
     "swrt_raydiag_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
+    "swrt_raydiag_record_history": (_INT, [_VP, _I, _I, _D, _D, _INT, _P, _D]),
     "swrt_raydiag_frames": (_I, [_VP]),
     "swrt_raydiag_series_get": (_INT, [_VP, _I, _I, _P]),
     "swrt_raydiag_series_reset": (_INT, [_VP]),
     "swrt_ode23_f1": (_INT, [_VP, _D, _D, _D, _D, _INT, _D, _D, ctypes.POINTER(_D)]),
     "swrt_ode23_attempt": (_INT, [_VP, _D, _D, _D, _D, _D, _D, _INT, _D, _D, ctypes.POINTER(_D)]),
     "swrt_ode23_accept": (_INT, [_VP]),
+    "swrt_ode23_set_dense": (_INT, [_VP, _INT]),
+    "swrt_ode23_ntrp": (_INT, [_VP, _D, _D, _P, _I]),
     "swrt_ode23_run": (_INT, [_VP, _D, _D, _D, _D, _D, _INT, _D, _D, _D, _P, _I, ctypes.POINTER(_I),
                               ctypes.POINTER(_I)]),
+    "swrt_ode23_run_at": (_INT, [_VP, _P, _I, _D, _D, _D, _INT, _D, _D, _D, _P, _I, ctypes.POINTER(_I),
+                                 ctypes.POINTER(_I)]),
     "swrt_ode23_run_hooked": (_INT, [_VP, _D, _D, _D, _D, _D, _INT, _D, _D, _D, _P, _I, ctypes.POINTER(_I),
                                      ctypes.POINTER(_I), _HOOK, _VP]),
     "swrt_ode23_run_sharded": (_INT, [_VP, _D, _D, _D, _D, _D, _INT, _D, _D, _D, _P, _I, ctypes.POINTER(_I),
@@ -147,6 +152,8 @@ DEBUG_ODE23_FIRST_TAKEN = 11
 DEBUG_ODE23_GUESSES_TAKEN = 12
 DEBUG_ODE23_SPLIT_RUNS = 13
 DEBUG_ODE23_FIRST_CHAINED = 14
+DEBUG_ODE23_DENSE_REBIN = 15
+DEBUG_ODE23_DENSE_REBINS = 16
 
 _lib = None
 
@@ -522,6 +529,18 @@ class Context:
         self._chk(self._L.swrt_raydiag_record(self._h, float(f), float(gH), int(nslots), float(alpha), float(bump)),
                   "swrt_raydiag_record")
 
+    def raydiag_record_history(self, first, count, f, gH, nslots=1, alphas=None, bump=1e-13):
+        """swrt_raydiag_record_history: one series frame per history frame
+        [first, first + count) (queued; no host wait), frame i with the
+        snapshot blend ``alphas[i]`` (None with one snapshot: 0)."""
+        if alphas is not None:
+            alphas = np.ascontiguousarray(alphas, dtype=np.float64)
+            if alphas.shape != (int(count),):
+                raise ValueError("alphas must hold one value per frame")
+        self._chk(self._L.swrt_raydiag_record_history(self._h, int(first), int(count), float(f), float(gH),
+                                                      int(nslots), _p(alphas), float(bump)),
+                  "swrt_raydiag_record_history")
+
     def raydiag_frames(self):
         return int(self._L.swrt_raydiag_frames(self._h))
 
@@ -552,6 +571,38 @@ class Context:
 
     def ode23_accept(self):
         self._chk(self._L.swrt_ode23_accept(self._h), "swrt_ode23_accept")
+
+    def ode23_set_dense(self, on):
+        """swrt_ode23_set_dense: ode23_attempt keeps F2 and F3 for ode23_ntrp."""
+        self._chk(self._L.swrt_ode23_set_dense(self._h, int(on)), "swrt_ode23_set_dense")
+
+    def ode23_ntrp(self, t, tnew, tout):
+        """swrt_ode23_ntrp: between a dense attempt of the step from t to tnew
+        and ode23_accept, append one history frame per time in ``tout``
+        (ntrp23 inside the step; a time equal to tnew is ynew itself)."""
+        tout = np.ascontiguousarray(tout, dtype=np.float64).reshape(-1)
+        self._chk(self._L.swrt_ode23_ntrp(self._h, float(t), float(tnew), _p(tout), int(tout.size)),
+                  "swrt_ode23_ntrp")
+
+    def ode23_run_at(self, tspan, tmax, f, Cg, nslots, rtol, atol, bump, ts_cap=10_000):
+        """swrt_ode23_run_at: ode23 over a vector ``tspan`` with the controller
+        in the library; the solution at tspan[1:] is appended to the history
+        (len(tspan) - 1 frames) and the packets are left at the last one.
+        Returns (accepted times, {steps, failed, attempts, accepted}) as
+        ode23_run."""
+        tspan = np.ascontiguousarray(tspan, dtype=np.float64).reshape(-1)
+        ts = np.empty(ts_cap)
+        nts = _I()
+        st = (_I * 3)()
+        self._chk(self._L.swrt_ode23_run_at(self._h, _p(tspan), int(tspan.size), float(tmax), float(f), float(Cg),
+                                            int(nslots), float(rtol), float(atol), float(bump), _p(ts),
+                                            int(ts_cap), ctypes.byref(nts), st), "swrt_ode23_run_at")
+        if nts.value > ts_cap:
+            import warnings
+            warnings.warn(f"swrt_ode23_run_at accepted {nts.value} times; only the first ts_cap={ts_cap} are returned",
+                          RuntimeWarning, stacklevel=2)
+        return ts[:min(nts.value, ts_cap)].copy(), {"steps": st[0], "failed": st[1], "attempts": st[2],
+                                                    "accepted": nts.value}
 
     def ode23_run(self, t0, tfinal, tmax, f, Cg, nslots, rtol, atol, bump, ts_cap=10_000, hook=None, reduce=None):
         """swrt_ode23_run: the whole ode23 call with the controller in the

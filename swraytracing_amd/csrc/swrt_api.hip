@@ -1128,7 +1128,8 @@ static int raydiag_reserve(swrt_ctx* c, int64_t extra) {
 // (then the reduction over its records) whose frame goes to `frame` (device)
 // and whose N x 4 values go to `sample4` (device, may be NULL).
 static int raydiag_launch(swrt_ctx* c, bool mark, double f, double gH, int nslots, double alpha, double bump,
-                          double* sample4, double* frame) {
+                          double* sample4, double* frame, const double* hist_x = nullptr,
+                          const double* hist_k = nullptr) {
   RayDiagState& rd = c->rd;
   RayDiagArgs a;
   a.f0 = view_of(c->slot[0]);
@@ -1139,6 +1140,11 @@ static int raydiag_launch(swrt_ctx* c, bool mark, double f, double gH, int nslot
   a.x = c->pk.cur.x.get();
   a.k = c->pk.cur.k.get();
   a.perm = c->pk.cur.perm.get();
+  if (hist_x) {  // a history frame: the same layout in the original packet order
+    a.x = hist_x;
+    a.k = hist_k;
+    a.perm = nullptr;
+  }
   a.n = c->n;
   a.f2 = f * f;
   a.gH = gH;
@@ -1206,6 +1212,29 @@ int swrt_raydiag_record(swrt_ctx* c, double f, double gH, int nslots, double alp
   HIPCHK_RC(raydiag_launch(c, false, f, gH, nslots, alpha, bump, nullptr,
                            c->rd.series.get() + kRayDiagFrame * c->rd.frames));
   ++c->rd.frames;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_raydiag_record_history(swrt_ctx* c, int64_t first, int64_t count, double f, double gH, int nslots,
+                                const double* alphas, double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c);
+  HIPCHK_RC(raydiag_check(c, nslots));
+  if (first < 0 || count < 0 || first + count > c->hframes)
+    return fail(c, SWRT_ERR_ARG, "history frame range out of bounds");
+  if (nslots == 2 && !alphas && count > 0) return fail(c, SWRT_ERR_ARG, "NULL buffer (alphas, two snapshots)");
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(raydiag_reserve(c, count));
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t off = (first + i) * 2 * c->n;
+    HIPCHK_RC(raydiag_launch(c, false, f, gH, nslots, alphas ? alphas[i] : 0.0, bump, nullptr,
+                             c->rd.series.get() + kRayDiagFrame * c->rd.frames, c->hx.get() + off,
+                             c->hk.get() + off));
+    ++c->rd.frames;
+  }
   return SWRT_OK;
   GUARD_END(c)
 }
@@ -1297,6 +1326,10 @@ int swrt_debug_set(swrt_ctx* c, int key, int64_t value) {
       c->dbg.corrupt_count = (int)value;
       c->bin.invalidate();  // the next call re-bins (and meets the corrupted count)
       return SWRT_OK;
+    case SWRT_DEBUG_ODE23_DENSE_REBIN:
+      if (value < 0 || value > 1000000) return fail(c, SWRT_ERR_ARG, "ode23 run_at re-binning cadence out of range");
+      c->o23.dense_rebin = value;
+      return SWRT_OK;
     case SWRT_DEBUG_QG_UPDATE_COLS:
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "QG update/column-pass fusion must be 0 or 1");
       if (c->qg.spec) return fail(c, SWRT_ERR_STATE, "a speculative QG step is pending (swrt_qg_resolve first)");
@@ -1331,6 +1364,8 @@ int swrt_debug_get(swrt_ctx* c, int key, int64_t* value_out) {
     case SWRT_DEBUG_ODE23_GUESSES_TAKEN: *value_out = c->o23.guesses_taken; return SWRT_OK;
     case SWRT_DEBUG_ODE23_SPLIT_RUNS: *value_out = c->o23.split_runs; return SWRT_OK;
     case SWRT_DEBUG_ODE23_FIRST_CHAINED: *value_out = c->o23.chain.first_taken; return SWRT_OK;
+    case SWRT_DEBUG_ODE23_DENSE_REBIN: *value_out = c->o23.dense_rebin; return SWRT_OK;
+    case SWRT_DEBUG_ODE23_DENSE_REBINS: *value_out = c->o23.dense_rebins; return SWRT_OK;
     default: return fail(c, SWRT_ERR_ARG, "unknown debug key");
   }
 }
@@ -1822,15 +1857,8 @@ int swrt_ode23_attempt(swrt_ctx* c, double t, double h, double tnew, double tmax
   HIPCHK_RC(lost_check(c));
   SlotUse slot_use(c, false, kSlots01);
   HIPCHK(c, hipSetDevice(c->device));
-  int rc;
-  Ode23Args a;
-  if ((rc = ode23_prepare(c, nslots, a, tmax, f, Cg, thr, bump))) return rc;
-  // ode23: f(:,2) at t + h*A(1), y + f*hB(:,1); f(:,3) at t + h*A(2), y + f*hB(:,2);
-  // h = tnew - t; ynew = y + f*hB(:,3); f(:,4) at tnew — one launch (stage 0:
-  // the tile kernel runs the three stages per packet, registers between them)
-  attempt_coeffs(a, t, h, tnew);
-  if ((rc = ode23_launch<0>(c, a))) return rc;
-  return read_max(c, err_raw_out);
+  // (swrt_ode23_set_dense: the tile kernel also stores F2 and F3)
+  return ode23_attempt(c, t, h, tnew, tmax, f, Cg, nslots, thr, bump, c->o23.dense, err_raw_out);
   GUARD_END(c)
 }
 
@@ -1841,11 +1869,76 @@ int swrt_ode23_accept(swrt_ctx* c) {
   HIPCHK_RC(lost_check(c));
   HIPCHK_RC(chain_drop(c));
   if (!c->o23.ynx) return fail(c, SWRT_ERR_STATE, "no ode23 step attempted");
-  std::swap(c->pk.cur.x, c->o23.ynx);
-  std::swap(c->pk.cur.k, c->o23.ynk);
-  std::swap(c->o23.F[0], c->o23.F[3]);
-  c->bin.packets_replaced();
+  ode23_accept_sets(c);
   return SWRT_OK;
+}
+
+int swrt_ode23_set_dense(swrt_ctx* c, int on) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (conservative: settings and syncs may precede packet-stream work)
+  if (on != 0 && on != 1) return fail(c, SWRT_ERR_ARG, "dense must be 0 or 1");
+  c->o23.dense = on != 0;
+  c->o23.dense_ready = false;
+  return SWRT_OK;
+}
+
+int swrt_ode23_ntrp(swrt_ctx* c, double t, double tnew, const double* tout, int64_t nout) {
+  if (!c) return SWRT_ERR_ARG;
+  HOOK_REFUSE
+  // (reads the packets and the stage buffers only: whatever dropped the chain
+  // since the attempt also ended the attempt's validity)
+  GUARD_BEGIN_KEEP_CHAIN
+  HIPCHK_RC(lost_check(c));
+  if (nout < 0) return fail(c, SWRT_ERR_ARG, "nout < 0");
+  if (nout > 0 && !tout) return fail(c, SWRT_ERR_ARG, "NULL buffer");
+  if (!c->o23.dense_ready)
+    return fail(c, SWRT_ERR_STATE,
+                "ode23 ntrp: no dense attempt in the stage buffers (swrt_ode23_set_dense 1, then "
+                "swrt_ode23_attempt; valid until swrt_ode23_accept or any other packet call)");
+  const double tdir = std::copysign(1.0, tnew - t);
+  if (!(tnew != t) || !std::isfinite(t) || !std::isfinite(tnew)) return fail(c, SWRT_ERR_ARG, "ode23 ntrp: empty step");
+  for (int64_t i = 0; i < nout; ++i)
+    if (!(tdir * (tout[i] - t) >= 0 && tdir * (tnew - tout[i]) >= 0))
+      return fail(c, SWRT_ERR_ARG, "ode23 ntrp: an output time lies outside the step");
+  if (nout == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(ensure_history(c, nout));
+  return ode23_ntrp_queue(c, t, tnew, tout, nout);
+  GUARD_END(c)
+}
+
+int swrt_ode23_run_at(swrt_ctx* c, const double* tspan, int64_t nt, double tmax, double f, double Cg, int nslots,
+                      double rtol, double atol, double bump, double* ts_out, int64_t ts_cap, int64_t* nts_out,
+                      int64_t* stats3_out) {
+  if (!c) return SWRT_ERR_ARG;
+  if (!tspan) return fail(c, SWRT_ERR_ARG, "tspan is NULL");
+  if (nt < 2) return fail(c, SWRT_ERR_ARG, "tspan needs at least two times");
+  if (!ts_out || ts_cap < 1 || !nts_out) return fail(c, SWRT_ERR_ARG, "ts_out / ts_cap / nts_out");
+  for (int64_t i = 0; i < nt; ++i)
+    if (!std::isfinite(tspan[i])) return fail(c, SWRT_ERR_ARG, "tspan must be finite");
+  {
+    const double tdir = std::copysign(1.0, tspan[nt - 1] - tspan[0]);
+    for (int64_t i = 1; i < nt; ++i)
+      if (!(tdir * (tspan[i] - tspan[i - 1]) > 0))
+        return fail(c, SWRT_ERR_ARG, "tspan must be strictly increasing or strictly decreasing");
+  }
+  GUARD_BEGIN
+  HIPCHK_RC(lost_check(c));
+  SlotUse slot_use(c, false, kSlots01);
+  O23Stats st;
+  int64_t nts = 0;
+  const int rc = ode23_run_at(c, tspan, nt, tmax, f, Cg, nslots, rtol, atol, bump, ts_out, ts_cap, &nts, &st);
+  if (rc == kO23BelowHmin) return fail(c, SWRT_ERR_STATE, "ode23: step size below hmin");
+  if (rc) return rc;
+  *nts_out = nts;
+  if (stats3_out) {
+    stats3_out[0] = st.steps;
+    stats3_out[1] = st.failed;
+    stats3_out[2] = st.attempts;
+  }
+  c->o23.last = st;
+  return SWRT_OK;
+  GUARD_END(c)
 }
 
 int swrt_ode23_chain_next(swrt_ctx* c, int slot_a, int slot_b) {

@@ -281,6 +281,12 @@ struct Ode23State {
   O23Stats last;            // the last swrt_ode23_run's controller counts
   int64_t first_taken = 0, guesses_taken = 0;  // ... summed over runs (SWRT_DEBUG_ODE23_*)
   int64_t split_runs = 0;  // runs whose attempts ran as two part launches (SWRT_DEBUG_ODE23_SPLIT_RUNS)
+  // output at requested times (swrt_ode23_set_dense / _ntrp / _run_at)
+  bool dense = false;        // swrt_ode23_attempt keeps F2 and F3
+  bool dense_ready = false;  // y, F1..F4 and ynew of a dense attempt sit in the buffers: until the accept, or
+                             // any call that may touch the packets (chain_drop)
+  int64_t dense_rebin = 8;   // swrt_ode23_run_at: accepted steps per re-binning (SWRT_DEBUG_ODE23_DENSE_REBIN; 0: none)
+  int64_t dense_rebins = 0;  // ... and the re-binnings it made inside runs (SWRT_DEBUG_ODE23_DENSE_REBINS)
 };
 
 // swrt_snapshot_qk (snapshots from a half plane another context exported):
@@ -592,6 +598,7 @@ int chain_join(swrt_ctx* c) {
 
 // A queued ode23 chain dropped (the packets may change).
 int chain_drop(swrt_ctx* c) {
+  c->o23.dense_ready = false;  // (a dense attempt's stage buffers describe the packets before this call)
   c->o23.chain.queued = false;
   c->o23.chain.first_q = false;
   return chain_join(c);

@@ -116,8 +116,13 @@ int read_max(swrt_ctx* c, double* out) {
 // binned by the tile kernel's 16x16-cell tiles, else one lane per packet
 template <int STAGE, bool TWO, bool V5>
 void ode23_tile_launch(swrt_ctx* c, const Ode23Args& a, unsigned grid, const int* starts, int ntx, hipStream_t st,
-                       hipEvent_t stop) {
+                       hipEvent_t stop, bool dense) {
   if constexpr (STAGE == 0) {
+    if (dense) {  // F2 and F3 kept for ode23_ntrp_kernel (never with device coefficients)
+      hipExtLaunchKernelGGL((tile_ode23_kernel<0, TWO, kTile, kMargin, kTileThreads, V5, false, true>), dim3(grid),
+                            dim3(kTileThreads), 0, st, nullptr, stop, 0, a, starts, ntx);
+      return;
+    }
     if (a.coef) {  // coefficients from device memory (swrt_ode23_run's first attempt)
       hipExtLaunchKernelGGL((tile_ode23_kernel<0, TWO, kTile, kMargin, kTileThreads, V5, true>), dim3(grid),
                             dim3(kTileThreads), 0, st, nullptr, stop, 0, a, starts, ntx);
@@ -147,9 +152,11 @@ bool ode23_split_ok(swrt_ctx* c) {
 // itself completes (*stop_done = true) — no marker between consecutive
 // attempts (a separate event record cost ~7 us of idle stream per launch,
 // profiles/r06_ode23); the per-packet kernels leave it to the caller.
+// `dense` (STAGE 0): the tile kernel also stores F2 and F3, as the per-packet
+// stage kernels always do.
 template <int STAGE>
 int ode23_launch(swrt_ctx* c, const Ode23Args& a0, int part = -1, unsigned* wg_out = nullptr,
-                 hipEvent_t stop = nullptr, bool* stop_done = nullptr) {
+                 hipEvent_t stop = nullptr, bool* stop_done = nullptr, bool dense = false) {
   if (wg_out) *wg_out = 0;
   if (stop_done) *stop_done = false;
   const int ntx = tiles_per_side(c->slot[0].nx);
@@ -182,11 +189,11 @@ int ode23_launch(swrt_ctx* c, const Ode23Args& a0, int part = -1, unsigned* wg_o
     }
     const bool v5 = c->slot[0].div_free && (a.nslots == 1 || c->slot[1].div_free);
     if (a.nslots == 2) {
-      if (v5) ode23_tile_launch<STAGE, true, true>(c, a, grid, starts, ntx, st, stop);
-      else ode23_tile_launch<STAGE, true, false>(c, a, grid, starts, ntx, st, stop);
+      if (v5) ode23_tile_launch<STAGE, true, true>(c, a, grid, starts, ntx, st, stop, dense);
+      else ode23_tile_launch<STAGE, true, false>(c, a, grid, starts, ntx, st, stop, dense);
     } else {
-      if (v5) ode23_tile_launch<STAGE, false, true>(c, a, grid, starts, ntx, st, stop);
-      else ode23_tile_launch<STAGE, false, false>(c, a, grid, starts, ntx, st, stop);
+      if (v5) ode23_tile_launch<STAGE, false, true>(c, a, grid, starts, ntx, st, stop, dense);
+      else ode23_tile_launch<STAGE, false, false>(c, a, grid, starts, ntx, st, stop, dense);
     }
     if (stop_done) *stop_done = stop != nullptr;
   } else if constexpr (STAGE == 0) {  // one lane per packet: the three stage launches
@@ -210,6 +217,7 @@ int ode23_launch(swrt_ctx* c, const Ode23Args& a0, int part = -1, unsigned* wg_o
 // launch queued (its max in slot o_dmax_cur, not yet advanced)
 int ode23_f1_queue(swrt_ctx* c, double t, double tmax, double f, double Cg, int nslots, double thr, double bump) {
   HIPCHK(c, hipSetDevice(c->device));
+  c->o23.dense_ready = false;  // (F1 is rewritten, perhaps in another packet order)
   int rc;
   // a spatial re-binning per kOde23RebinEvery ode23 calls (the packet order
   // is free: the error norm is a max over all components; a packet that has
@@ -645,5 +653,170 @@ bool ode23_chain_take(swrt_ctx* c, double t0, double tmax, double f, double Cg, 
     if (!c->slot[i].set || c->slot[i].nodes.get() != ch.nodes[i] || c->slot[i].wgen != ch.wgen[i]) return false;
   return same_bits(o23_alpha(t0, tmax), ch.alpha) && same_bits(f, ch.f) && same_bits(Cg, ch.Cg) &&
          same_bits(thr, ch.thr) && same_bits(bump, ch.bump);
+}
+
+// ---------------------------------------------------------------------------
+// Output at requested times (MATLAB ode23 with numel(tspan) > 2): the steps are
+// chosen as ever, and the solution at every tspan entry an accepted step
+// passes is ntrp23 inside that step (ode23_ntrp_kernel), appended to the
+// history as a frame.
+// ---------------------------------------------------------------------------
+
+// accept: y = ynew, F1 = F4 (FSAL)
+void ode23_accept_sets(swrt_ctx* c) {
+  std::swap(c->pk.cur.x, c->o23.ynx);
+  std::swap(c->pk.cur.k, c->o23.ynk);
+  std::swap(c->o23.F[0], c->o23.F[3]);
+  c->bin.packets_replaced();
+  c->o23.dense_ready = false;
+}
+
+// One attempt on the packet stream and its raw error max (the host waits for
+// it; raw NULL: queued only).  ode23: f(:,2) at t + h*A(1), y + f*hB(:,1);
+// f(:,3) at t + h*A(2), y + f*hB(:,2); h = tnew - t; ynew = y + f*hB(:,3);
+// f(:,4) at tnew — one launch (stage 0: the tile kernel runs the three stages
+// per packet, registers between them).  dense: F2 and F3 are kept in memory
+// for ode23_ntrp_queue.
+int ode23_attempt(swrt_ctx* c, double t, double h, double tnew, double tmax, double f, double Cg, int nslots,
+                  double thr, double bump, bool dense, double* raw) {
+  Ode23Args a;
+  HIPCHK_RC(ode23_prepare(c, nslots, a, tmax, f, Cg, thr, bump));
+  attempt_coeffs(a, t, h, tnew);
+  HIPCHK_RC(ode23_launch<0>(c, a, -1, nullptr, nullptr, nullptr, dense));
+  HIPCHK_RC(read_max(c, raw));
+  c->o23.dense_ready = dense;
+  return SWRT_OK;
+}
+
+// The frames at tout[0 .. nout) of the step from t to tnew whose dense attempt
+// sits in the stage buffers (before the accept): kNtrpFrames per launch,
+// appended to the history, whose capacity the caller has reserved.
+int ode23_ntrp_queue(swrt_ctx* c, double t, double tnew, const double* tout, int64_t nout) {
+  if (nout <= 0) return SWRT_OK;
+  const int64_t n = c->n;
+  if ((c->hframes + nout) * 2 * n > c->hcap) return fail(c, SWRT_ERR_STATE, "ode23 ntrp: history capacity not reserved");
+  const double h = tnew - t;
+  NtrpArgs a;
+  a.yx = c->pk.cur.x.get();
+  a.yk = c->pk.cur.k.get();
+  for (int s = 0; s < 4; ++s) a.F[s] = c->o23.F[s].get();
+  a.ynx = c->o23.ynx.get();
+  a.ynk = c->o23.ynk.get();
+  a.perm = c->pk.cur.perm.get();
+  a.n = n;
+  // h*BI, BI = [1 -4/3 5/9; 0 1 -2/3; 0 4/3 -8/9; 0 -1 1] (ntrp23.m), column by column
+  const double hb[9] = {h * 1.0,         h * (-4.0 / 3.0), h * 1.0,          h * (4.0 / 3.0), h * (-1.0),
+                        h * (5.0 / 9.0), h * (-2.0 / 3.0), h * (-8.0 / 9.0), h * 1.0};
+  for (int i = 0; i < 9; ++i) a.hb[i] = hb[i];
+  for (int64_t i0 = 0; i0 < nout; i0 += kNtrpFrames) {
+    a.nf = (int)std::min<int64_t>(kNtrpFrames, nout - i0);
+    a.exact = 0u;
+    for (int j = 0; j < kNtrpFrames; ++j) {
+      const double ti = j < a.nf ? tout[i0 + j] : tnew;
+      if (j < a.nf && same_bits(ti, tnew)) a.exact |= 1u << j;
+      const double s = (ti - t) / h;
+      const double s2 = s * s;
+      a.s[j] = s;
+      a.s2[j] = s2;
+      a.s3[j] = s2 * s;
+    }
+    a.hx = c->hx.get() + c->hframes * 2 * n;
+    a.hk = c->hk.get() + c->hframes * 2 * n;
+    hipLaunchKernelGGL(ode23_ntrp_kernel, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    c->hframes += a.nf;
+  }
+  return SWRT_OK;
+}
+
+// swrt_ode23_run_at: MATLAB ode23's loop (integrate.py ode23_packets,
+// operation for operation, the arithmetic of swrt_ode23_ctl.hpp) over the
+// plain sequence stage 1 -> dense attempt -> max -> ntrp -> accept on the
+// packet stream: no guessed attempts, no part launches, no chaining.  hmax
+// comes from the whole span, the initial step's bound from the first output
+// gap (odearguments' htspan); the output times enter nothing else.  Every
+// c->o23.dense_rebin accepted steps stage 1 is queued again at the current t
+// with a fresh binning: F1 = odefun(t, y) recomputed is the FSAL F4 bit for
+// bit, so the cadence changes the speed only.
+int ode23_run_at(swrt_ctx* c, const double* tspan, int64_t nt, double tmax, double f, double Cg, int nslots,
+                 double rtol, double atol, double bump, double* ts_out, int64_t ts_cap, int64_t* nts_out,
+                 O23Stats* st_out) {
+  const double t0 = tspan[0], tfinal = tspan[nt - 1];
+  const double tdir = std::copysign(1.0, tfinal - t0);
+  const double pw = 1.0 / 3.0;
+  rtol = std::max(rtol, 100 * 2.220446049250313e-16);
+  const double thr = atol / rtol;
+  const double hmax = 0.1 * std::fabs(tfinal - t0);
+  const double htspan = std::fabs(tspan[1] - tspan[0]);
+  const double c0 = 0.8 * std::pow(rtol, pw);
+  O23Stats st;
+  int64_t nts = 0;
+  auto leave = [&](int rc) {
+    st.steps = nts > 0 ? nts - 1 : 0;
+    *st_out = st;
+    *nts_out = nts;
+    return rc;
+  };
+  HIPCHK_RC(ensure_history(c, nt - 1));
+  HIPCHK_RC(ode23_f1_queue(c, t0, tmax, f, Cg, nslots, thr, bump));
+  double raw = 0.0;
+  HIPCHK_RC(read_max(c, &raw));
+  double t = t0;
+  double absh = o23_initial_absh(raw, c0, hmax, htspan, 16 * o23_spacing(t));
+  if (ts_cap > 0) ts_out[0] = t;
+  ++nts;
+  int64_t next = 1, since_rebin = 0;
+  bool done = false;
+  while (!done) {
+    const double hmin = 16 * o23_spacing(t);
+    double h, tnew;
+    done = o23_step_head(absh, hmax, hmin, tdir, t, tfinal, h, tnew);
+    bool nofailed = true;
+    double err;
+    while (true) {
+      tnew = t + h * 1.0;
+      if (done) tnew = tfinal;
+      ++st.attempts;
+      if (int rc = ode23_attempt(c, t, h, tnew, tmax, f, Cg, nslots, thr, bump, true, &raw)) return leave(rc);
+      err = absh * raw;
+      h = tnew - t;
+      if (err > rtol) {
+        ++st.failed;
+        if (absh <= hmin) return leave(kO23BelowHmin);
+        if (nofailed) {
+          nofailed = false;
+          absh = std::max(hmin, absh * std::max(0.5, 0.8 * std::pow(rtol / err, pw)));
+        } else {
+          absh = std::max(hmin, 0.5 * absh);
+        }
+        h = tdir * absh;
+        done = false;
+      } else {
+        break;
+      }
+    }
+    // the frames of every requested time this step reaches, in order
+    int64_t cnt = 0;
+    while (next + cnt < nt && tdir * (tnew - tspan[next + cnt]) >= 0) ++cnt;
+    if (int rc = ode23_ntrp_queue(c, t, tnew, tspan + next, cnt)) return leave(rc);
+    next += cnt;
+    ode23_accept_sets(c);
+    t = tnew;
+    if (nts < ts_cap) ts_out[nts] = t;
+    ++nts;
+    if (done) break;
+    if (nofailed) {
+      const double temp = 1.25 * std::pow(err / rtol, pw);
+      absh = temp > 0.2 ? absh / temp : 5.0 * absh;
+    }
+    if (c->o23.dense_rebin > 0 && c->rebin_every > 0 && ++since_rebin >= c->o23.dense_rebin) {
+      since_rebin = 0;
+      c->bin.invalidate();
+      if (int rc = ode23_f1_queue(c, t, tmax, f, Cg, nslots, thr, bump)) return leave(rc);
+      if (int rc = read_max(c, nullptr)) return leave(rc);
+      ++c->o23.dense_rebins;
+    }
+  }
+  return leave(SWRT_OK);
 }
 }  // namespace

@@ -367,7 +367,10 @@ __device__ __forceinline__ void tile_rhs(const Ode23Args& a, const double2* win,
 // DC (STAGE 0): the attempt's coefficients from a.coef (a separate
 // instantiation: the first attempt of swrt_ode23_run only, so the others keep
 // their coefficients in the kernel arguments' scalar registers)
-template <int STAGE, bool TWO, int T, int M, int NT, bool V5, bool DC = false>
+// DENSE (STAGE 0): stages 2 and 3 also store their derivatives to a.F[1] and
+// a.F[2], as the separate stage kernels do, for ode23_ntrp_kernel (output at
+// requested times); every other instantiation is the code it was.
+template <int STAGE, bool TWO, int T, int M, int NT, bool V5, bool DC = false, bool DENSE = false>
 __global__ void __launch_bounds__(NT, 4) tile_ode23_kernel(Ode23Args a, const int* starts, int ntx) {
   constexpr int W = T + 5 + 2 * M;
   constexpr int WS = W + ((12 - W % 16) + 16) % 16;  // LDS row stride (nodes)
@@ -469,6 +472,13 @@ __global__ void __launch_bounds__(NT, 4) tile_ode23_kernel(Ode23Args a, const in
           ts = cf[4];
         }
         tile_rhs<TWO, T, M, WS, WNP, V5>(a, win, ox, oy, nx, alpha_of(a, ts), ys, fo);
+        if constexpr (DENSE) {
+          if (sg < 2) {  // F2, F3 for the interpolant (q: this stage's re-materialised index)
+            double* Fd = sg == 0 ? a.F[1] : a.F[2];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) Fd[c * n + q] = fo[c];
+          }
+        }
         if (sg == 0) {
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
@@ -520,6 +530,71 @@ __global__ void __launch_bounds__(NT, 4) tile_ode23_kernel(Ode23Args a, const in
       // system scope: the host reads it after the launch's own completion event
       if (a.hpart) __hip_atomic_store(a.hpart + blockIdx.x, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+  }
+}
+
+// ntrp23 (MATLAB ode23's interpolant inside an accepted step from t to tnew,
+// h = tnew - t): the solution at up to kNtrpFrames requested times per launch,
+// written as history frames (swrt_advance's layout: N x 2 x, then N x 2 k, by
+// the original packet index).  One lane per packet in storage order reads y
+// and F1..F4 once.  Per component, in this operation order (no contraction):
+//   c1 = F1*hb[0]
+//   c2 = ((F1*hb[1] + F2*hb[2]) + F3*hb[3]) + F4*hb[4]
+//   c3 = ((F1*hb[5] + F2*hb[6]) + F3*hb[7]) + F4*hb[8]
+//   yi = y + ((c1*s + c2*s2) + c3*s3)
+// hb = h*BI's nine nonzero entries and s = (ti - t)/h, s2 = s*s, s3 = s2*s come
+// from the host (uniform: kernel arguments, scalar registers).  A frame whose
+// time is tnew itself (`exact` bit) is a copy of ynew.
+constexpr int kNtrpFrames = 8;
+
+struct NtrpArgs {
+  const double* yx;    // y at t: x, y (2N), k, l (2N), storage order
+  const double* yk;
+  const double* F[4];  // F1..F4 of the accepted attempt, 4N each
+  const double* ynx;   // ynew
+  const double* ynk;
+  const int* perm;     // storage slot -> original packet index
+  int64_t n;
+  double* hx;          // the launch's first frame (x) ...
+  double* hk;          // ... and (k); frame j follows at j * 2N
+  int nf;              // frames of this launch, 1..kNtrpFrames
+  unsigned exact;      // bit j: frame j is ynew
+  double hb[9];
+  double s[kNtrpFrames], s2[kNtrpFrames], s3[kNtrpFrames];
+};
+
+__global__ void __launch_bounds__(256) ode23_ntrp_kernel(NtrpArgs a) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t n = a.n;
+  if (p >= n) return;
+  const int64_t o = a.perm[p];
+  double y[4], yn[4], c1[4], c2[4], c3[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int64_t i = (c & 1) * n + p;
+    y[c] = c < 2 ? a.yx[i] : a.yk[i];
+    yn[c] = c < 2 ? a.ynx[i] : a.ynk[i];
+    const double f1 = a.F[0][c * n + p], f2 = a.F[1][c * n + p], f3 = a.F[2][c * n + p], f4 = a.F[3][c * n + p];
+    c1[c] = f1 * a.hb[0];
+    c2[c] = ((f1 * a.hb[1] + f2 * a.hb[2]) + f3 * a.hb[3]) + f4 * a.hb[4];
+    c3[c] = ((f1 * a.hb[5] + f2 * a.hb[6]) + f3 * a.hb[7]) + f4 * a.hb[8];
+  }
+#pragma unroll
+  for (int j = 0; j < kNtrpFrames; ++j) {
+    if (j >= a.nf) break;
+    double v[4];
+    if (a.exact >> j & 1u) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = yn[c];
+    } else {
+      const double s = a.s[j], s2 = a.s2[j], s3 = a.s3[j];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = y[c] + ((c1[c] * s + c2[c] * s2) + c3[c] * s3);
+    }
+    double* hx = a.hx + (int64_t)j * 2 * n;
+    double* hk = a.hk + (int64_t)j * 2 * n;
+    hx[o] = v[0]; hx[n + o] = v[1];
+    hk[o] = v[2]; hk[n + o] = v[3];
   }
 }
 

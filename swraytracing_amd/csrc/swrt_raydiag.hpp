@@ -47,7 +47,7 @@ struct RayDiagArgs {
   double alpha, bump;
   const double* x;   // N x 2 column-major, storage order
   const double* k;
-  const int* perm;   // storage slot -> original packet index
+  const int* perm;   // storage slot -> original packet index (NULL: the identity, a history frame)
   int64_t n;
   double f2, gH;     // f2 = f*f
   double* omega0;    // by original index.  MARK: written; else read (NULL: no mark, r = 0)
@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(kRayDiagThreads) ray_diag_kernel(RayDiagArgs a
   eval_flow(a.f0, a.f1, a.nslots, a.alpha, a.x[p], a.x[a.n + p], a.bump, I);
   const double w = sqrt(a.f2 + a.gH * (k1 * k1 + k2 * k2));
   const double Om = w + (I[0] * k1 + I[1] * k2);
-  const int64_t o = a.perm[p];
+  const int64_t o = a.perm ? a.perm[p] : p;
   if constexpr (MARK) {
     a.omega0[o] = Om;
   } else {

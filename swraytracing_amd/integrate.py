@@ -130,9 +130,36 @@ def ode23_packets(ctx: Context, tspan, tmax, f, Cg, nslots=2, rtol=1e-3, atol=1e
     ``hook``: a callable (QG calls only, never the packets) run once while
     the interval's first launches run — the library controller calls it
     after stage 1 and the first attempt are queued (swrt_ode23_run_hooked),
-    the Python loop after stage 1."""
+    the Python loop after stage 1.
+
+    A ``tspan`` of more than two times (strictly monotonic) is MATLAB's
+    output at requested times: the steps are chosen as for [tspan[0],
+    tspan[-1]] — only the initial step is also bounded by the first gap
+    |tspan[1] - tspan[0]| (odearguments' htspan) — and the solution at
+    tspan[1:], ntrp23 inside the accepted steps, is appended to the context's
+    history (len(tspan) - 1 frames, Context.history()).  "library" runs
+    swrt_ode23_run_at, "python" the loop below with ode23_ntrp; the same
+    steps and frame bits either way.  Single rank, no hook."""
+    tspan = [float(v) for v in tspan]
+    dense = len(tspan) > 2
+    if dense:
+        if allreduce_max is not None or hook is not None:
+            raise ValueError("a tspan of more than two times takes neither allreduce_max nor a hook")
+        d = np.diff(tspan)
+        if not (np.all(d > 0) or np.all(d < 0)):
+            raise ValueError("tspan must be strictly increasing or strictly decreasing")
     if controller is None:
         controller = "library" if hasattr(ctx, "ode23_run") else "python"
+    if controller == "library" and dense:
+        try:
+            ts, st = ctx.ode23_run_at(tspan, tmax, f, Cg, nslots, rtol, atol, bump)
+        except SwrtError as e:
+            if "below hmin" in str(e):
+                raise RuntimeError(str(e)) from e
+            raise
+        if stats is not None:
+            stats.update(**st)
+        return ts
     if controller == "library":
         try:
             ts, st = ctx.ode23_run(float(tspan[0]), float(tspan[1]), tmax, f, Cg, nslots, rtol, atol, bump,
@@ -145,13 +172,26 @@ def ode23_packets(ctx: Context, tspan, tmax, f, Cg, nslots=2, rtol=1e-3, atol=1e
             stats.update(**st)
         return ts
     red = allreduce_max or (lambda v: v)
-    t0, tfinal = float(tspan[0]), float(tspan[1])
+    if dense:
+        ctx.ode23_set_dense(1)
+        try:
+            return _ode23_loop(ctx, tspan, tmax, f, Cg, nslots, rtol, atol, bump, red, stats, hook)
+        finally:
+            ctx.ode23_set_dense(0)
+    return _ode23_loop(ctx, tspan, tmax, f, Cg, nslots, rtol, atol, bump, red, stats, hook)
+
+
+def _ode23_loop(ctx, tspan, tmax, f, Cg, nslots, rtol, atol, bump, red, stats, hook):
+    """ode23_packets' controller in Python (the library's ode23_control and
+    swrt_ode23_run_at restate it operation for operation)."""
+    t0, tfinal = tspan[0], tspan[-1]
     tdir = math.copysign(1.0, tfinal - t0)
     pw = 1.0 / 3.0
     rtol = max(rtol, 100 * np.finfo(float).eps)
     thr = atol / rtol
-    htspan = abs(tfinal - t0)
-    hmax = 0.1 * htspan
+    htspan = abs(tspan[1] - tspan[0])  # the first output gap: bounds the initial step only
+    hmax = 0.1 * abs(tfinal - t0)
+    nxt = 1  # the next requested time (a tspan of more than two)
     t = t0
     rh = red(ctx.ode23_f1(t, tmax, f, Cg, nslots, thr, bump)) / (0.8 * rtol ** pw)
     if hook is not None:
@@ -193,6 +233,13 @@ def ode23_packets(ctx: Context, tspan, tmax, f, Cg, nslots=2, rtol=1e-3, atol=1e
                 done = False
             else:
                 break
+        if len(tspan) > 2:
+            # every requested time this step reaches, in order (ntrp23; tnew itself: ynew)
+            n0 = nxt
+            while nxt < len(tspan) and tdir * (tnew - tspan[nxt]) >= 0:
+                nxt += 1
+            if nxt > n0:
+                ctx.ode23_ntrp(t, tnew, tspan[n0:nxt])
         ctx.ode23_accept()
         t = tnew
         ts.append(t)
@@ -204,6 +251,64 @@ def ode23_packets(ctx: Context, tspan, tmax, f, Cg, nslots=2, rtol=1e-3, atol=1e
     if stats is not None:
         stats.update(steps=len(ts) - 1, failed=nfailed, attempts=attempts, accepted=len(ts))
     return np.array(ts)
+
+
+def ode23_trajectory(x0, k0, t_hist, f, Cg, scheme, rtol=1e-3, atol=1e-6, diagnostics=False):
+    """[t_hist, solver_y] = ode23(rayfun, t_hist, y0, opts) with the packet
+    layout of ode_symplectic (SW_zero_background_raytracing.m:69-83): x0, k0
+    are 1 x 2 x P, ``t_hist`` the strictly monotonic output times; returns
+    (solver_x, solver_k) of shape len(t_hist) x 2 x P, row 0 the initial state
+    and row i the ode23 solution at t_hist[i] (ntrp23 inside the accepted
+    steps, the whole call on the device: ode23_packets with the library
+    controller).
+
+    The right-hand side is the drivers' (qgsw_raytrace.m:259-265): dx/dt =
+    U + Cg*k/omega, dk/dt = -(grad U)^T k with omega = sqrt(f^2 + Cg^2|k|^2).
+    SW_zero_background_raytracing.m:183 uses scheme.grad_omega instead, which
+    is this one when Cg = 1.
+
+    ``scheme``: a SpectralScheme (steady) or a SnapshotPairScheme (two
+    snapshots blended at t / scheme.tmax).  ``diagnostics``: a third value,
+    the (len(t_hist) x 8) swrt_raydiag series — row i belongs to row i of the
+    outputs; Omega_0 is marked at the initial state, so row 0 has r = 0
+    (solver_error of :85-87 against t_hist), computed on the device from the
+    frames."""
+    if not isinstance(scheme, (SpectralScheme, SnapshotPairScheme)):
+        raise ValueError("ode23_trajectory needs a GPU-backed scheme (SpectralScheme / SnapshotPairScheme)")
+    x0 = np.asarray(x0, dtype=np.float64)
+    k0 = np.asarray(k0, dtype=np.float64)
+    if x0.ndim == 2:
+        x0 = x0[None]
+        k0 = k0[None]
+    t_hist = np.asarray(t_hist, dtype=np.float64).reshape(-1)
+    if t_hist.size < 3:
+        # (two times are MATLAB's every-step output: not this function's; ode23_packets leaves y(tfinal))
+        raise ValueError("t_hist needs at least three times")
+    P = x0.shape[2]
+    nt = t_hist.size
+    steady = isinstance(scheme, SpectralScheme)
+    nslots = 1 if steady else 2
+    tmax = 0.0 if steady else scheme.tmax
+    ctx = scheme.ctx
+    x = np.zeros((nt, 2, P))
+    k = np.zeros((nt, 2, P))
+    x[0] = x0[0]
+    k[0] = k0[0]
+    ctx.packets_set(np.asfortranarray(x0[0].T), np.asfortranarray(k0[0].T))  # (starts a new history)
+    alphas = None if steady else t_hist / tmax
+    if diagnostics:
+        gH = float(Cg) ** 2
+        ctx.raydiag_series_reset()
+        ctx.raydiag_mark(f, gH, nslots=nslots, alpha=0.0 if steady else alphas[0], bump=scheme.bump)
+        ctx.raydiag_record(f, gH, nslots=nslots, alpha=0.0 if steady else alphas[0], bump=scheme.bump)
+    ode23_packets(ctx, t_hist, tmax, f, Cg, nslots=nslots, rtol=rtol, atol=atol, bump=scheme.bump,
+                  controller="library")
+    x[1:], k[1:] = ctx.history()
+    if diagnostics:
+        ctx.raydiag_record_history(0, nt - 1, f, gH, nslots=nslots, alphas=None if steady else alphas[1:],
+                                   bump=scheme.bump)
+        return x, k, ctx.raydiag_series()
+    return x, k
 
 
 class _EmptyShard:
