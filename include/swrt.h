@@ -304,6 +304,70 @@ int swrt_spectral_leapfrog(swrt_ctx* ctx, double* x, double* k, int64_t n, doubl
 int swrt_omega_histogram(swrt_ctx* ctx, double f, double Cg, const double* edges, int64_t nbins,
                          int64_t* counts_inout, double* mean_omega_out);
 
+/* The energy-vs-omega series of a run, kept on the device: what load_data.m
+ * computes from every saved packet frame (load_data.m:33-52,63), without the
+ * frames.  omega = sqrt(f^2 + Cg^2*(k*k + l*l)) in that operation order, as
+ * swrt_omega_histogram.  A frame is
+ *   a row of nbins + 2 int64 counts [below, bin 0 .. bin nbins-1, above]:
+ *     bin i holds edges[i] <= omega < edges[i+1], the last bin also omega ==
+ *     edges[nbins] (histcounts, load_data.m:47); below counts omega <
+ *     edges[0], above omega > edges[nbins]; a NaN omega is counted nowhere, so
+ *     n - sum(row) is the number of NaN packets;
+ *   four doubles [n, sum omega, min omega, max omega]: the mean of
+ *     load_data.m:63 and the value load_data.m:39 builds its edges from.  min
+ *     and max ignore NaN (+inf and -inf if there is nothing else); the sum is
+ *     a plain sum.
+ * A frame depends on the packets alone: counts, min and max by nature, and
+ * the sum runs over the original packet index (the set's perm; per-workgroup
+ * partials of a fixed grid, combined in an order their number fixes).  Two
+ * contexts holding the same packets, a re-binning between two records, or
+ * swrt_advance against swrt_advance_intervals all give the same bits.  Frames
+ * are self-contained: swrt_packets_set with another N keeps the series. */
+
+/* Open a series: 1 <= nbins <= 4096, nbins + 1 finite increasing edges
+ * (SWRT_ERR_ARG otherwise).  Uploads the edges, keeps f^2 and Cg^2, empties
+ * the series.  The edges of load_data.m:39-40. */
+int swrt_omega_series_begin(swrt_ctx* ctx, double f, double Cg, const double* edges, int64_t nbins);
+
+/* Append the frame of the current packets (one iteration of load_data.m:44-50
+ * with a window of one frame): queued on the packet stream after whatever last
+ * wrote the packets (both packet streams, the ode23 attempts); the host does
+ * not wait.  Reads no field slot.  Capacity: 4096 frames, doubled when full,
+ * and only a growing call may wait for the stream.  SWRT_ERR_STATE before
+ * swrt_omega_series_begin, SWRT_ERR_ARG without packets. */
+int swrt_omega_series_record(swrt_ctx* ctx);
+
+/* One frame per history frame in [first, first + count) (the frames of
+ * swrt_advance(save_every) or swrt_ode23_run_at): load_data.m:33's omega of
+ * the stored frames without a download.  The same bits as
+ * swrt_omega_series_record on packets set to that frame.  A range out of
+ * bounds: SWRT_ERR_ARG. */
+int swrt_omega_series_record_history(swrt_ctx* ctx, int64_t first, int64_t count);
+
+/* Frames recorded since begin or the last reset (the frame count of
+ * load_data.m:32); nbins of the open series, 0 if none. */
+int64_t swrt_omega_series_frames(const swrt_ctx* ctx);
+int64_t swrt_omega_series_bins(const swrt_ctx* ctx);
+
+/* Frames [first, first + count): counts_out count x (nbins + 2) and stats4_out
+ * count x 4 (may be NULL), frame-major.  Waits for them.  The rows
+ * load_data.m:45-49 sums over its window, and load_data.m:63's sum and n. */
+int swrt_omega_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* counts_out,
+                          double* stats4_out);
+
+/* Empty the series; f, Cg and the edges stay (load_data.m:44, a new window). */
+int swrt_omega_series_reset(swrt_ctx* ctx);
+
+/* ideal_omega_distribution.m:3-11: Omega = omega0 + (u_g*kx_j + v_g*ky_j), in
+ * that operation order, for every node g of slot's nx x nx grid (layer 1 of a
+ * slot with a 2*nx y-period) and every ring vector j, binned into counts_out
+ * [below, bins, above] (nbins + 2) over `edges` by the rule above: nx^2*m
+ * samples.  ring_k: m x 2 column-major, k_0*[cos t, sin t]
+ * (ideal_omega_distribution.m:3-5); omega0 = sqrt(f^2 + Cg^2*k_0^2) (:9).
+ * Synchronous.  An unset slot, m < 1 or bad edges: SWRT_ERR_ARG. */
+int swrt_omega_ideal(swrt_ctx* ctx, int slot, const double* ring_k, int64_t m, double omega0,
+                     const double* edges, int64_t nbins, int64_t* counts_out);
+
 /* ---------------------------------------------------------------------------
  * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
  * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)

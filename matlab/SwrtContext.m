@@ -31,5 +31,34 @@ classdef SwrtContext < handle
         function delete(obj)
             obj.release();
         end
+
+        % The energy-vs-omega series of the device-resident packets
+        % (analysis/load_data.m:33-52,63) and the ideal distribution
+        % (ideal_omega_distribution.m:3-11): thin calls into swrt_mex.
+        function omega_series_begin(obj, f, Cg, edges)
+            swrt_mex('omega_series_begin', obj.id(), f, Cg, edges);
+        end
+
+        function omega_series_record(obj)
+            swrt_mex('omega_series_record', obj.id());
+        end
+
+        function omega_series_record_history(obj, first, count)
+            % history frames first .. first+count-1, 0-based
+            swrt_mex('omega_series_record_history', obj.id(), first, count);
+        end
+
+        function [counts, stats] = omega_series_get(obj)
+            % counts: (nbins+2) x frames [below; bins; above]; stats: 4 x frames [n; sum; min; max]
+            [counts, stats] = swrt_mex('omega_series_get', obj.id());
+        end
+
+        function omega_series_reset(obj)
+            swrt_mex('omega_series_reset', obj.id());
+        end
+
+        function counts = omega_ideal(obj, slot, ring, omega0, edges)
+            counts = swrt_mex('omega_ideal', obj.id(), slot, ring, omega0, edges);
+        end
     end
 end

@@ -41,6 +41,11 @@
 //   [qk, t, steps] = swrt_mex('qg_get', h, nx, nlayers);  q = swrt_mex('qg_get_q', h, nx, nlayers);
 //   swrt_mex('qg_snapshot', h, slot, which, layer, ny_period);  swrt_mex('swap_slots', h, a, b)
 //   tf = swrt_mex('field_div_free', h, slot)   % v_y == -u_x exactly (five-sum kernels)
+//   swrt_mex('omega_series_begin', h, f, Cg, edges)           % load_data.m:33-52,63 on the device
+//   swrt_mex('omega_series_record', h);  swrt_mex('omega_series_record_history', h, first, count)
+//   [counts, stats] = swrt_mex('omega_series_get', h)         % (nbins+2) x frames, 4 x frames
+//   swrt_mex('omega_series_reset', h)
+//   counts = swrt_mex('omega_ideal', h, slot, ring, omega0, edges)   % ideal_omega_distribution.m:3-11
 #include <cstring>
 #include <string>
 #include <vector>
@@ -413,6 +418,50 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     const int rc = swrt_field_div_free(c, (int)scalar(a[1]));
     if (rc < 0) check(c, rc, "swrt_field_div_free");
     plhs[0] = mxCreateDoubleScalar(rc == 1 ? 1.0 : 0.0);
+    return;
+  }
+  if (!strcmp(cmd, "omega_series_begin")) {  // (f, Cg, edges)
+    need(na, 4, cmd);
+    check(c, swrt_omega_series_begin(c, scalar(a[1]), scalar(a[2]), reals(a[3], "edges"),
+                                     (int64_t)mxGetNumberOfElements(a[3]) - 1),
+          "swrt_omega_series_begin");
+    return;
+  }
+  if (!strcmp(cmd, "omega_series_record")) {
+    check(c, swrt_omega_series_record(c), "swrt_omega_series_record");
+    return;
+  }
+  if (!strcmp(cmd, "omega_series_record_history")) {  // (first, count): 0-based history frames
+    need(na, 3, cmd);
+    check(c, swrt_omega_series_record_history(c, (int64_t)scalar(a[1]), (int64_t)scalar(a[2])),
+          "swrt_omega_series_record_history");
+    return;
+  }
+  if (!strcmp(cmd, "omega_series_get")) {  // -> counts (nbins+2) x frames (double, exact), stats 4 x frames
+    const int64_t nf = swrt_omega_series_frames(c), ns = swrt_omega_series_bins(c) + 2;
+    std::vector<int64_t> counts((size_t)(nf * ns));
+    plhs[0] = mxCreateDoubleMatrix((mwSize)ns, (mwSize)nf, mxREAL);
+    mxArray* stats = mxCreateDoubleMatrix(4, (mwSize)nf, mxREAL);
+    check(c, swrt_omega_series_get(c, 0, nf, counts.data(), mxGetDoubles(stats)), "swrt_omega_series_get");
+    double* d = mxGetDoubles(plhs[0]);
+    for (size_t i = 0; i < counts.size(); ++i) d[i] = (double)counts[i];
+    if (nlhs > 1) plhs[1] = stats; else mxDestroyArray(stats);
+    return;
+  }
+  if (!strcmp(cmd, "omega_series_reset")) {
+    check(c, swrt_omega_series_reset(c), "swrt_omega_series_reset");
+    return;
+  }
+  if (!strcmp(cmd, "omega_ideal")) {  // (slot, ring m x 2, omega0, edges) -> counts (nbins+2) x 1
+    need(na, 5, cmd);
+    if (mxGetN(a[2]) != 2) mexErrMsgIdAndTxt("swrt:arg", "ring must be m x 2");
+    const int64_t nb = (int64_t)mxGetNumberOfElements(a[4]) - 1;
+    std::vector<int64_t> counts((size_t)(nb > 0 ? nb + 2 : 2));
+    check(c, swrt_omega_ideal(c, (int)scalar(a[1]), reals(a[2], "ring"), (int64_t)mxGetM(a[2]), scalar(a[3]),
+                              reals(a[4], "edges"), nb, counts.data()),
+          "swrt_omega_ideal");
+    plhs[0] = mxCreateDoubleMatrix((mwSize)counts.size(), 1, mxREAL);
+    for (size_t i = 0; i < counts.size(); ++i) mxGetDoubles(plhs[0])[i] = (double)counts[i];
     return;
   }
   mexErrMsgIdAndTxt("swrt:arg", "unknown command '%s'", cmd);

@@ -84,6 +84,14 @@ SIGNATURES = {
     "swrt_spectral_eval": (_INT, [_VP, _P, _P, _I, _INT, _P]),
     "swrt_spectral_leapfrog": (_INT, [_VP, _P, _P, _I, _D, _I, _D, _D, _INT]),
     "swrt_omega_histogram": (_INT, [_VP, _D, _D, _P, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_D)]),
+    "swrt_omega_series_begin": (_INT, [_VP, _D, _D, _P, _I]),
+    "swrt_omega_series_record": (_INT, [_VP]),
+    "swrt_omega_series_record_history": (_INT, [_VP, _I, _I]),
+    "swrt_omega_series_frames": (_I, [_VP]),
+    "swrt_omega_series_bins": (_I, [_VP]),
+    "swrt_omega_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), _P]),
+    "swrt_omega_series_reset": (_INT, [_VP]),
+    "swrt_omega_ideal": (_INT, [_VP, _INT, _P, _I, _D, _P, _I, ctypes.POINTER(ctypes.c_int64)]),
     "swrt_raydiag_mark": (_INT, [_VP, _D, _D, _INT, _D, _D]),
     "swrt_raydiag_sample": (_INT, [_VP, _D, _D, _INT, _D, _D, _P, _P]),
     "swrt_raydiag_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
@@ -505,6 +513,55 @@ class Context:
                                                counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                                ctypes.byref(mean)), "swrt_omega_histogram")
         return counts, mean.value
+
+    # ---- the spectrum series (swrt_omega_series_*, load_data.m:33-52,63) -------
+    def omega_series_begin(self, f, Cg, edges):
+        """Open a series over ``edges`` (nbins + 1 increasing values); empties it."""
+        edges = _f64(np.asarray(edges, dtype=np.float64).ravel())
+        self._chk(self._L.swrt_omega_series_begin(self._h, float(f), float(Cg), _p(edges), edges.size - 1),
+                  "swrt_omega_series_begin")
+
+    def omega_series_record(self):
+        """Append the current packets' frame to the device-side series (queued; no host wait)."""
+        self._chk(self._L.swrt_omega_series_record(self._h), "swrt_omega_series_record")
+
+    def omega_series_record_history(self, first, count):
+        """One series frame per history frame [first, first + count) (queued; no host wait)."""
+        self._chk(self._L.swrt_omega_series_record_history(self._h, int(first), int(count)),
+                  "swrt_omega_series_record_history")
+
+    def omega_series_frames(self):
+        return int(self._L.swrt_omega_series_frames(self._h))
+
+    def omega_series(self, first=0, count=None):
+        """Recorded frames [first, first + count) -> (counts (count, nbins + 2)
+        int64 [below, bins, above]; stats (count, 4) [n, sum omega, min, max])."""
+        count = self.omega_series_frames() - first if count is None else count
+        nslot = int(self._L.swrt_omega_series_bins(self._h)) + 2
+        counts = np.zeros((max(count, 0), nslot), dtype=np.int64)
+        stats = np.zeros((max(count, 0), 4))
+        self._chk(self._L.swrt_omega_series_get(self._h, int(first), int(count),
+                                                counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _p(stats)),
+                  "swrt_omega_series_get")
+        return counts, stats
+
+    def omega_series_reset(self):
+        self._chk(self._L.swrt_omega_series_reset(self._h), "swrt_omega_series_reset")
+
+    def omega_ideal(self, slot, ring_k, omega0, edges):
+        """ideal_omega_distribution.m:3-11: counts [below, bins, above] of
+        omega0 + U_g . k_j over every node g of ``slot`` and every row j of
+        ``ring_k`` (m x 2).  Synchronous."""
+        ring = np.asarray(ring_k, dtype=np.float64)
+        if ring.ndim != 2 or ring.shape[1] != 2:
+            raise ValueError("ring_k must be m x 2")
+        ring = _f64(np.asfortranarray(ring).ravel(order="F"))
+        edges = _f64(np.asarray(edges, dtype=np.float64).ravel())
+        counts = np.zeros(edges.size + 1, dtype=np.int64)
+        self._chk(self._L.swrt_omega_ideal(self._h, int(slot), _p(ring), ring.size // 2, float(omega0), _p(edges),
+                                           edges.size - 1, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+                  "swrt_omega_ideal")
+        return counts
 
     # ---- the invariant and the flow along the rays (swrt_raydiag_*) ----------
     def raydiag_mark(self, f, gH, nslots=1, alpha=0.0, bump=1e-13):

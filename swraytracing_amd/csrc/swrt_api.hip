@@ -1263,6 +1263,208 @@ int swrt_raydiag_series_reset(swrt_ctx* c) {
   return SWRT_OK;
 }
 
+// ---- the spectrum series (swrt_diag.hpp) ----
+// swrt_omega_histogram's checks on the edges, finite as well.
+static int omega_edges_check(swrt_ctx* c, const double* edges, int64_t nbins) {
+  if (nbins <= 0 || nbins > kMaxHistBins) return fail(c, SWRT_ERR_ARG, "nbins must be 1..4096");
+  if (!edges) return fail(c, SWRT_ERR_ARG, "NULL buffer");
+  for (int64_t i = 0; i <= nbins; ++i)
+    if (!std::isfinite(edges[i])) return fail(c, SWRT_ERR_ARG, "edges must be finite");
+  for (int64_t i = 0; i < nbins; ++i)
+    if (!(edges[i] < edges[i + 1])) return fail(c, SWRT_ERR_ARG, "edges must increase");
+  return SWRT_OK;
+}
+
+inline size_t omega_lds_bytes(int nb) { return sizeof(double) * (nb + 1) + sizeof(unsigned int) * (nb + 2); }
+
+constexpr int64_t kOmegaSeriesMin = 4096;  // frames reserved by the first record
+
+// omega's per-packet buffer for the current ensemble and room for `extra` more
+// frames, as raydiag_reserve: growing keeps the recorded frames and waits for
+// the stream.  The rows are zeroed by the launches that fill them.
+static int omega_reserve(swrt_ctx* c, int64_t extra, bool need_w) {
+  OmegaSeriesState& om = c->om;
+  if (!om.partial) HIPCHK(c, om.partial.alloc((size_t)kOmegaHistoryChunk * kOmegaPartials * kOmegaBlocks));
+  if (need_w && c->n > om.pcap) {  // (releasing the old buffer waits for queued readers)
+    om.pcap = 0;
+    HIPCHK(c, om.w.alloc(c->n));
+    om.pcap = c->n;
+  }
+  if (om.frames + extra <= om.cap) return SWRT_OK;
+  const int64_t ncap = std::max<int64_t>({kOmegaSeriesMin, 2 * om.cap, om.frames + extra});
+  const size_t nslot = (size_t)om.nb + 2;
+  DevBuf<unsigned long long> nc;
+  DevBuf<double> ns;
+  HIPCHK(c, nc.alloc(nslot * ncap));
+  HIPCHK(c, ns.alloc((size_t)kOmegaStats * ncap));
+  if (om.frames > 0) {
+    HIPCHK(c, hipMemcpyAsync(nc.get(), om.counts.get(), sizeof(unsigned long long) * nslot * om.frames,
+                             hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ns.get(), om.stats.get(), sizeof(double) * kOmegaStats * om.frames,
+                             hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  hz_synced(c);
+  om.counts = std::move(nc);
+  om.stats = std::move(ns);
+  om.cap = ncap;
+  return SWRT_OK;
+}
+
+// `count` frames from the series' end on: omega_frame_kernel over src (omega
+// by original index, or the k of consecutive history frames), then their stats.
+static int omega_frames_launch(swrt_ctx* c, bool from_k, const double* src, int64_t src_stride, int64_t count) {
+  OmegaSeriesState& om = c->om;
+  OmegaFrameArgs a;
+  a.src = src;
+  a.src_stride = src_stride;
+  a.n = c->n;
+  a.f2 = om.f2;
+  a.Cg2 = om.Cg2;
+  a.edges = om.edges.get();
+  a.nb = om.nb;
+  a.counts = om.counts.get() + (size_t)(om.nb + 2) * om.frames;
+  a.partial = om.partial.get();
+  const int nblk = (int)std::min<int64_t>(kOmegaBlocks, nblocks(c->n, kOmegaThreads));
+  const dim3 grid(nblk, (unsigned)count), block(kOmegaThreads);
+  hipLaunchKernelGGL(from_k ? omega_frame_kernel<true> : omega_frame_kernel<false>, grid, block,
+                     omega_lds_bytes(om.nb), c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(omega_stats_kernel, dim3((unsigned)count), dim3(kOmegaThreads), 0, c->stream, om.partial.get(), nblk, c->n,
+                     om.stats.get() + (size_t)kOmegaStats * om.frames);
+  HIPCHK(c, hipGetLastError());
+  om.frames += count;
+  return SWRT_OK;
+}
+
+int swrt_omega_series_begin(swrt_ctx* c, double f, double Cg, const double* edges, int64_t nbins) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(omega_edges_check(c, edges, nbins));
+  HIPCHK(c, hipSetDevice(c->device));
+  OmegaSeriesState& om = c->om;
+  // (queued records may still write the old series: wait before releasing it)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  hz_synced(c);
+  om.open = false;
+  om.frames = 0;
+  om.cap = 0;
+  om.counts.reset();
+  om.stats.reset();
+  HIPCHK(c, om.edges.alloc(nbins + 1));
+  HIPCHK(c, hipMemcpyAsync(om.edges.get(), edges, sizeof(double) * (nbins + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  om.nb = (int)nbins;
+  om.f2 = f * f;
+  om.Cg2 = Cg * Cg;
+  om.open = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+static int omega_series_check(swrt_ctx* c) {
+  if (!c->om.open) return fail(c, SWRT_ERR_STATE, "call swrt_omega_series_begin first");
+  HIPCHK_RC(lost_check(c));
+  if (c->n == 0) return fail(c, SWRT_ERR_ARG, "no packets (swrt_packets_set first)");
+  return SWRT_OK;
+}
+
+int swrt_omega_series_record(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(omega_series_check(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(omega_reserve(c, 1, true));
+  OmegaSeriesState& om = c->om;
+  hipLaunchKernelGGL(omega_scatter_kernel, dim3(nblocks(c->n, kOmegaThreads)), dim3(kOmegaThreads), 0, c->stream,
+                     c->pk.cur.k.get(), c->pk.cur.perm.get(), c->n, om.f2, om.Cg2, om.w.get(),
+                     om.counts.get() + (size_t)(om.nb + 2) * om.frames, om.nb + 2);
+  HIPCHK(c, hipGetLastError());
+  return omega_frames_launch(c, false, om.w.get(), 0, 1);
+  GUARD_END(c)
+}
+
+int swrt_omega_series_record_history(swrt_ctx* c, int64_t first, int64_t count) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(omega_series_check(c));
+  if (first < 0 || count < 0 || first + count > c->hframes)
+    return fail(c, SWRT_ERR_ARG, "history frame range out of bounds");
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(omega_reserve(c, count, false));
+  OmegaSeriesState& om = c->om;
+  HIPCHK(c, hipMemsetAsync(om.counts.get() + (size_t)(om.nb + 2) * om.frames, 0,
+                           sizeof(unsigned long long) * (om.nb + 2) * count, c->stream));
+  for (int64_t i = 0; i < count; i += kOmegaHistoryChunk) {
+    const int64_t m = std::min<int64_t>(kOmegaHistoryChunk, count - i);
+    HIPCHK_RC(omega_frames_launch(c, true, c->hk.get() + (first + i) * 2 * c->n, 2 * c->n, m));
+  }
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int64_t swrt_omega_series_frames(const swrt_ctx* c) { return c ? c->om.frames : -1; }
+
+int64_t swrt_omega_series_bins(const swrt_ctx* c) { return c ? (c->om.open ? c->om.nb : 0) : -1; }
+
+int swrt_omega_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, double* stats4_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  if (first < 0 || count < 0 || first + count > c->om.frames)
+    return fail(c, SWRT_ERR_ARG, "frame range out of bounds");
+  if (count == 0) return SWRT_OK;
+  if (!counts_out) return fail(c, SWRT_ERR_ARG, "NULL buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nslot = (size_t)c->om.nb + 2;
+  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "a count row is copied out as it is");
+  HIPCHK(c, hipMemcpyAsync(counts_out, c->om.counts.get() + nslot * first, sizeof(int64_t) * nslot * count,
+                           hipMemcpyDeviceToHost, c->stream));
+  if (stats4_out)
+    HIPCHK(c, hipMemcpyAsync(stats4_out, c->om.stats.get() + (size_t)kOmegaStats * first,
+                             sizeof(double) * kOmegaStats * count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return dev_err_check(c);
+  GUARD_END(c)
+}
+
+int swrt_omega_series_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
+  c->om.frames = 0;
+  return SWRT_OK;
+}
+
+int swrt_omega_ideal(swrt_ctx* c, int slot, const double* ring_k, int64_t m, double omega0, const double* edges,
+                     int64_t nbins, int64_t* counts_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c);
+  if (slot < 0 || slot >= SWRT_MAX_SLOTS || !c->slot[slot].set) return fail(c, SWRT_ERR_ARG, "field slot not set");
+  if (m < 1 || m > (1 << 20)) return fail(c, SWRT_ERR_ARG, "m must be 1..2^20");
+  HIPCHK_RC(omega_edges_check(c, edges, nbins));
+  if (!ring_k || !counts_out) return fail(c, SWRT_ERR_ARG, "NULL buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const Slot& s = c->slot[slot];
+  const size_t nslot = (size_t)nbins + 2;
+  HIPCHK_RC(ensure_scratch(c, sizeof(double) * (nbins + 1 + 2 * m) + sizeof(unsigned long long) * nslot));
+  double* dedges = (double*)c->scratch.get();
+  double* dring = dedges + nbins + 1;
+  unsigned long long* drow = (unsigned long long*)(dring + 2 * m);
+  HIPCHK(c, hipMemcpyAsync(dedges, edges, sizeof(double) * (nbins + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dring, ring_k, sizeof(double) * 2 * m, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(drow, 0, sizeof(unsigned long long) * nslot, c->stream));
+  const int64_t total = s.nx * s.nx * m;
+  const int nblk = (int)std::min<int64_t>(kOmegaBlocks, nblocks(total, kOmegaThreads));
+  hipLaunchKernelGGL(omega_ideal_kernel, dim3(nblk), dim3(kOmegaThreads), omega_lds_bytes((int)nbins), c->stream,
+                     s.nodes.get(), (int)s.nx, (int)s.npad, dring, m, omega0, dedges, (int)nbins, drow);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(counts_out, drow, sizeof(int64_t) * nslot, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN

@@ -318,6 +318,23 @@ struct RayDiagState {
   }
 };
 
+// the spectrum series (swrt_omega_series_*, swrt_diag.hpp).  Buffers of its
+// own, as RayDiagState's.  A frame is self-contained (its n is in its stats),
+// so swrt_packets_set with another N keeps the series.
+struct OmegaSeriesState {
+  bool open = false;        // swrt_omega_series_begin was called
+  int nb = 0;               // bins of the open series
+  double f2 = 0.0, Cg2 = 0.0;
+  DevBuf<double> edges;     // nb + 1
+  DevBuf<double> w;         // omega by original packet index
+  int64_t pcap = 0;         // packets w is sized for
+  DevBuf<double> partial;   // kOmegaHistoryChunk frames x kOmegaPartials x kOmegaBlocks
+  DevBuf<unsigned long long> counts;  // recorded rows, nb + 2 each
+  DevBuf<double> stats;     // recorded stats, kOmegaStats doubles each
+  int64_t frames = 0;
+  int64_t cap = 0;          // frames allocated
+};
+
 // debug knobs (swrt_debug_set): a spin kernel queued on every extra packet
 // stream before each of its part launches (adversarial overlap of consecutive
 // calls), and the pre-third-buffer ordering after a source-gather sort
@@ -395,6 +412,7 @@ struct swrt_ctx {
   QGState qg;
   Ode23State o23;
   RayDiagState rd;
+  OmegaSeriesState om;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an
   // event marker, ~7 us of idle on each stream).  Only consecutive split

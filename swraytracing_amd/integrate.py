@@ -37,6 +37,48 @@ def combine_frames(frames):
     return out
 
 
+def combine_spectra(parts):
+    """The spectrum series of an ensemble from its shards' series
+    (swrt_omega_series_*).  ``parts``: a sequence of (counts, stats) pairs, one
+    per shard, counts (T, nbins + 2) int64 [below, bins, above] and stats
+    (T, 4) [n, sum omega, min omega, max omega]: the counts, n and the sum add,
+    min and max are taken.  A shard without packets stands as zeros with
+    min = +inf and max = -inf, and changes nothing."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no series to combine")
+    counts = np.stack([np.asarray(c, dtype=np.int64) for c, _ in parts])
+    stats = np.stack([np.asarray(s, dtype=np.float64) for _, s in parts])
+    if counts.ndim != 3 or stats.shape != counts.shape[:2] + (4,):
+        raise ValueError("every shard must give counts (T, nbins + 2) and stats (T, 4) for the same T")
+    out = np.empty(stats.shape[1:])
+    out[:, 0:2] = stats[:, :, 0:2].sum(axis=0)
+    out[:, 2] = stats[:, :, 2].min(axis=0)
+    out[:, 3] = stats[:, :, 3].max(axis=0)
+    return counts.sum(axis=0), out
+
+
+def empty_spectrum(frames, nbins):
+    """The series of a shard without packets, as combine_spectra takes it."""
+    stats = np.zeros((frames, 4))
+    stats[:, 2], stats[:, 3] = np.inf, -np.inf
+    return np.zeros((frames, nbins + 2), dtype=np.int64), stats
+
+
+def energy_spectrum(counts, edges, lo=0, hi=None):
+    """(center, energy) of load_data.m:40,45-49 over the series frames
+    [lo, hi): center = (edges[1:] + edges[:-1])/2, energy = center times the
+    frames' summed counts (the nbins inner columns of ``counts``; below and
+    above are outside histcounts' edges)."""
+    counts = np.asarray(counts)
+    edges = np.asarray(edges, dtype=np.float64).ravel()
+    if counts.ndim != 2 or counts.shape[1] != edges.size + 1:
+        raise ValueError("counts must be (T, nbins + 2) for nbins + 1 edges")
+    center = (edges[1:] + edges[:-1]) / 2
+    distribution = counts[lo:hi, 1:-1].sum(axis=0)
+    return center, center * distribution
+
+
 def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False):
     """[x, k, t] = ode_symplectic(x0, k0, dt, T, f, gH, scheme).
 
@@ -435,13 +477,77 @@ class PacketEnsemble:
         if self.n > 0:
             self.ctx.raydiag_record(self.f, self.gH, nslots=2, alpha=alpha, bump=self.bump)
 
+    def begin_spectrum(self, edges):
+        """Open the energy-vs-omega series of this run over ``edges``
+        (load_data.m:39-40): swrt_omega_series_begin with the ensemble's f, Cg."""
+        self._spec_edges = np.array(edges, dtype=np.float64).ravel()
+        self._spec_frames = 0
+        if self.n > 0:
+            self.ctx.omega_series_begin(self.f, self.Cg, self._spec_edges)
+
+    def record_spectrum(self):
+        """Append this shard's frame at the current state to the device-side
+        series (queued, no host wait).  An empty shard records nothing."""
+        if getattr(self, "_spec_edges", None) is None:
+            raise SwrtError("record_spectrum: call begin_spectrum first")
+        self._spec_frames += 1
+        if self.n > 0:
+            self.ctx.omega_series_record()
+
+    def spectrum_series(self):
+        """(counts (T, nbins + 2) int64, stats (T, 4)) of the ensemble.
+        Sharded: a collective (every rank calls it); rank 0 gets
+        combine_spectra() of the shards' series, the others None."""
+        if getattr(self, "_spec_edges", None) is None:
+            raise SwrtError("spectrum_series: call begin_spectrum first")
+        T, nb = self._spec_frames, self._spec_edges.size - 1
+        counts, stats = self.ctx.omega_series(0, T) if self.n > 0 else empty_spectrum(T, nb)
+        if self.world == 1:
+            return counts, stats
+        import torch
+        import torch.distributed as dist
+
+        from .dist import _device_for
+        dev = _device_for(dist.get_backend())
+        parts = []
+        for a in (counts, stats):
+            buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            out = [torch.empty_like(buf) for _ in range(self.world)]
+            dist.all_gather(out, buf)
+            parts.append([o.cpu().numpy() for o in out])
+        if self.rank != 0:
+            return None
+        return combine_spectra(zip(parts[0], parts[1]))
+
     def state(self):
         return self.ctx.packets_get()
 
-    def write_frame(self, t, directory):
+    def write_spectrum(self, directory):
+        """The run's spectrum series as write_field files (read_field reads
+        them): omega_hist.bin, one frame of nbins + 2 counts [below, bins,
+        above] per recorded frame (fp64, exact: every count <= N < 2^53),
+        omega_stats.bin, 4 values per frame, and omega_edges.bin, one frame of
+        nbins + 1 values.  Sharded: a collective; rank 0 writes.  Returns the
+        frames recorded."""
+        series = self.spectrum_series()
+        if series is not None:
+            counts, stats = series
+            for row, st in zip(counts, stats):
+                write_field(row, os.path.join(directory, "omega_hist"))
+                write_field(st, os.path.join(directory, "omega_stats"))
+            write_field(self._spec_edges, os.path.join(directory, "omega_edges"))
+        return self._spec_frames
+
+    def write_frame(self, t, directory, packet_files=True):
         """qgsw_raytrace.m:159-162: wrapped x, k and t appended to
         packet_x.bin / packet_k.bin / packet_time.bin.  Sharded: a collective
-        (every rank calls it); rank 0 writes the whole ensemble."""
+        (every rank calls it); rank 0 writes the whole ensemble.  Without
+        ``packet_files`` only t is written (the time of a spectrum frame) and
+        nothing is downloaded."""
+        if not packet_files:
+            if self.rank == 0:
+                write_field(np.array([[t]]), os.path.join(directory, "packet_time"))
+            return
         if self.world > 1:
             from .dist import gather_packets
             full = gather_packets(self.ctx, self.n_total, self.world, self.rank, bounds=self.bounds)

@@ -230,10 +230,30 @@ def _fresh_outputs(out_dir, fresh):
     os.makedirs(out_dir, exist_ok=True)
     if not fresh:
         return
-    for name in ("packet_x", "packet_k", "packet_time", "pv", "pv_time"):
+    for name in ("packet_x", "packet_k", "packet_time", "pv", "pv_time", "omega_hist", "omega_stats", "omega_edges"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
+
+
+def _spectrum_args(spectrum_edges, packet_files):
+    """The drivers' ``spectrum_edges`` / ``packet_files`` checked before anything runs."""
+    if spectrum_edges is None:
+        if not packet_files:
+            raise ValueError("packet_files=False without spectrum_edges: the run would write no packet output")
+        return None
+    edges = np.array(spectrum_edges, dtype=np.float64).ravel()
+    if edges.size < 2 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
+        raise ValueError("spectrum_edges must be at least two finite increasing values")
+    return edges
+
+
+def _save_frame(ens, t, out_dir, spectrum, packet_files):
+    """One packet frame: its spectrum recorded on the device (queued, no host
+    wait) whether or not the frame itself is written."""
+    if spectrum:
+        ens.record_spectrum()
+    ens.write_frame(t, out_dir, packet_files)
 
 
 def _owner_setup(world, pde, owner_weight, nx, Npackets, link_buffers="auto"):
@@ -482,7 +502,7 @@ class ReceiverLoop:
 def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_days, U_g, f, Cg, *,
                   out_dir="data", nsub=4, max_steps=None, seed=146, verbose=False, r_drag=0.1,
                   packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
-                  pde="owner", owner_weight=None, link_buffers="auto"):
+                  pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None, packet_files=True):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -498,8 +518,17 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     "ode23" (the reference's own ode23 over each interval, qgsw_raytrace.m:149).
     ``fresh``: remove earlier output files first (default) or append to
     them as write_field.m:31 does.  ``pde``, ``owner_weight``: the sharded
-    forms, as in :func:`qg2layersw_raytrace`.  Returns a dict of run facts
-    (dt, Nsteps, steps run, frames written, final t)."""
+    forms, as in :func:`qg2layersw_raytrace`.  ``spectrum_edges`` (nbins + 1
+    increasing values): every packet frame's energy-vs-omega counts and
+    statistics are recorded on the device (analysis/load_data.m:33-52,63;
+    swrt_omega_series_*) and written at the end as omega_hist.bin (nbins + 2
+    values per frame: below, the bins, above), omega_stats.bin (n, sum omega,
+    min, max per frame) and omega_edges.bin.  ``packet_files=False`` skips the
+    packet_x.bin / packet_k.bin downloads and writes (packet_time.bin stays:
+    the spectrum frames' times); it needs ``spectrum_edges``.  Returns a dict
+    of run facts (dt, Nsteps, steps run, frames written, final t,
+    spectrum_frames)."""
+    spectrum_edges = _spectrum_args(spectrum_edges, packet_files)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
@@ -548,8 +577,11 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
             link.snapshot(ctx, slot, which, L, K_d2, 0.0, 1.0, 0)
     t = 0.0
     frames = 1
+    spectrum = ens is not None and spectrum_edges is not None
+    if spectrum:
+        ens.begin_spectrum(spectrum_edges)
     if ens is not None:
-        ens.write_frame(dt * (packet_step_start - 1), out_dir)
+        _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files)
     if rank == 0:
         write_field(model.q(), os.path.join(out_dir, "pv"))
         write_field(np.array([[t]]), os.path.join(out_dir, "pv_time"))
@@ -574,7 +606,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
             group.add(dt)
             if (step - packet_step_start + 1) % packet_steps_per_save == 0:
                 group.flush()
-                ens.write_frame(t, out_dir)
+                _save_frame(ens, t, out_dir, spectrum, packet_files)
                 frames += 1
         else:
             have_cur = False
@@ -586,23 +618,26 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
         group.flush()
     if link is not None:
         link.close()
+    spectrum_frames = ens.write_spectrum(out_dir) if spectrum else 0
     ctx.synchronize()
     ctx.set_timing(timing)
     log.finish()
     log.close()
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
-                packet_step_start=packet_step_start)
+                packet_step_start=packet_step_start, spectrum_frames=spectrum_frames)
 
 
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
                         out_dir="data", nsub=5, max_steps=None, seed=5, verbose=False,
                         packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
-                        pde="owner", owner_weight=None, link_buffers="auto"):
+                        pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None,
+                        packet_files=True):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
     pv.bin holds the initial nx x nx x 2 frame only, as in the reference.
-    ``packet_intervals``, ``integrator``, ``fresh``: as in :func:`qgsw_raytrace`.
+    ``packet_intervals``, ``integrator``, ``fresh``, ``spectrum_edges``,
+    ``packet_files``: as in :func:`qgsw_raytrace`.
 
     Sharded (torch.distributed, world > 1): ``pde="owner"`` (default) — rank 0
     steps the PDE and sends each step's top-layer qk and dt to the other
@@ -613,6 +648,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     Both write the single-process files byte for byte.  ``link_buffers``: the
     owner link's buffers ("auto": on the device with nccl, on the host with
     gloo; "device" / "host" to force one)."""
+    spectrum_edges = _spectrum_args(spectrum_edges, packet_files)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
@@ -652,8 +688,11 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                          bump=BUMP_QG, ctx=ctx, shard=(rank, world), bounds=bounds) if Npackets > 0 else None
     t = 0.0
     frames = 1
+    spectrum = ens is not None and spectrum_edges is not None
+    if spectrum:
+        ens.begin_spectrum(spectrum_edges)
     if ens is not None:
-        ens.write_frame(dt * (packet_step_start - 1), out_dir)
+        _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files)
     if rank == 0:
         write_field(model.q(), os.path.join(out_dir, "pv"))
         write_field(np.array([[t]]), os.path.join(out_dir, "pv_time"))
@@ -675,13 +714,14 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     while loop.t <= T and (max_steps is None or loop.steps < max_steps):
         if loop.step() and (loop.steps - packet_step_start + 1) % packet_steps_per_save == 0:
             loop.flush()
-            ens.write_frame(loop.t, out_dir)
+            _save_frame(ens, loop.t, out_dir, spectrum, packet_files)
             frames += 1
         log.progress(loop.steps, Nsteps)
     loop.flush()
     loop.settle()
     if link is not None:
         link.close()
+    spectrum_frames = ens.write_spectrum(out_dir) if spectrum else 0
     ctx.synchronize()
     ctx.set_timing(timing)
     log.finish()
@@ -689,4 +729,4 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     dt, dts, step, t = loop.dt, loop.dts, loop.steps, loop.t
     U0 = getattr(loop, "U0", U0)  # (a receiving rank never sees the owner's U0)
     return dict(dt=dt, dts=dts, Nsteps=Nsteps, steps=step, packet_frames=frames, t=t, U0=U0,
-                packet_step_start=packet_step_start)
+                packet_step_start=packet_step_start, spectrum_frames=spectrum_frames)

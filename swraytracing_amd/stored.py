@@ -46,7 +46,7 @@ def read_frame(pv_path, nx, frame, nlayers=1):
 
 def trace_stored(pv_path, nx, x, k, f, Cg, *, frames=None, times=None, nlayers=1, L=2 * math.pi, K_d2=None,
                  shear=0.0, k_scale=1.0, nsub=5, bump=BUMP_QG, out_dir=None, intervals_per_call=SLOT_INTERVALS,
-                 ctx: Context | None = None, shard=None):
+                 ctx: Context | None = None, shard=None, spectrum_edges=None, packet_files=True):
     """Advance packets (x, k: N x 2) through the stored frames of a PV series.
 
     ``frames``: 1-based frame numbers in time order (default: every frame in
@@ -57,7 +57,16 @@ def trace_stored(pv_path, nx, x, k, f, Cg, *, frames=None, times=None, nlayers=1
     driver's semantics, qg2layersw_raytrace.m:186-188); ``L``, ``K_d2``
     (default f/Cg), ``shear``, ``k_scale`` are grid_U's.  ``out_dir``: write
     packet_x/k/time.bin frames (write_field layout) at the first frame and
-    after every call.  Returns (x, k, t_end)."""
+    after every call.  ``spectrum_edges``, ``packet_files``: as in
+    :func:`swraytracing_amd.qg.qgsw_raytrace` — every frame's energy-vs-omega
+    counts recorded on the device and written to ``out_dir`` at the end as
+    omega_hist.bin / omega_stats.bin / omega_edges.bin (they need ``out_dir``).
+    Returns (x, k, t_end)."""
+    from .qg import _save_frame, _spectrum_args
+    spectrum_edges = _spectrum_args(spectrum_edges, packet_files)
+    spectrum = spectrum_edges is not None
+    if spectrum and out_dir is None:
+        raise ValueError("spectrum_edges needs out_dir")
     ctx = ctx if ctx is not None else Context(0)
     nx = int(nx)
     if frames is None:
@@ -84,7 +93,9 @@ def trace_stored(pv_path, nx, x, k, f, Cg, *, frames=None, times=None, nlayers=1
                          ctx=ctx, shard=shard)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
-        ens.write_frame(times[0], out_dir)
+        if spectrum:
+            ens.begin_spectrum(spectrum_edges)
+        _save_frame(ens, times[0], out_dir, spectrum, packet_files)
     load(0, frames[0])
     i = 1
     while i < len(frames):
@@ -95,6 +106,8 @@ def trace_stored(pv_path, nx, x, k, f, Cg, *, frames=None, times=None, nlayers=1
         ctx.swap_slots(0, g)  # the last frame starts the next call
         i += g
         if out_dir is not None:
-            ens.write_frame(times[i - 1], out_dir)
+            _save_frame(ens, times[i - 1], out_dir, spectrum, packet_files)
+    if spectrum:
+        ens.write_spectrum(out_dir)
     xs, ks = ens.state()
     return xs, ks, times[-1]
