@@ -368,6 +368,61 @@ int swrt_omega_series_reset(swrt_ctx* ctx);
 int swrt_omega_ideal(swrt_ctx* ctx, int slot, const double* ring_k, int64_t m, double omega0,
                      const double* edges, int64_t nbins, int64_t* counts_out);
 
+/* The packet density and wave-energy maps of a run, kept on the device: where
+ * the ensemble sits, which generate_image.m:9-34 and raytracing_figures.m:6-24
+ * draw packet by packet.  The map has m x m cells over the periodic square of
+ * side L.  The cell of a packet is interpolate.m:21-31's with dxm = L/m:
+ * i = floor(mod(x/dxm, m)), then i mod m (mod may round up to m), the same for
+ * y; cell (i, j) covers x in [i*dxm, (i+1)*dxm) and sits at plane[i + m*j]
+ * (first index x, column-major: with m = nx the layout of a pv.bin frame).
+ * Every packet has three moments, omega = sqrt(f^2 + Cg^2*(k*k + l*l)) in
+ * load_data.m:33's operation order, k and l, each quantised once per packet:
+ * q = rint(v * 2^frac_bits), round half even.  A packet is rejected — it adds
+ * to no cell — when x, y, k, l or omega is not finite or any
+ * |v * 2^frac_bits| >= 2^38.  A frame is
+ *   four m x m planes of int64 [count, sum q(omega), sum q(k), sum q(l)];
+ *   two int64 stats [n, rejected].
+ * With n <= 2^24 every sum stays below 2^62: integer addition is exact and
+ * order-free, so a frame is a function of the packet set alone (not of the
+ * storage order, the binning, the launch shape or a shard split), and the
+ * frame of a sharded ensemble is the element-wise sum of the shards' frames.
+ * Energy per cell at unit action per packet (load_data.m:49) is
+ * sum q(omega) * 2^-frac_bits; the mean wavevector sum q(k) / count *
+ * 2^-frac_bits. */
+
+/* Open a series: 1 <= m <= 4096, L > 0, 0 <= frac_bits <= 32, at most 2^24
+ * packets set (SWRT_ERR_ARG otherwise).  Empties the series. */
+int swrt_map_series_begin(swrt_ctx* ctx, double L, int64_t m, double f, double Cg, int frac_bits);
+
+/* Append the frame of the current packets: queued on the packet stream after
+ * whatever last wrote the packets (both packet streams, the ode23 attempts);
+ * the host does not wait.  Capacity: 64 MiB of frames (at least one, at most
+ * 4096), doubled when full; only a growing call may wait for the stream, and
+ * a failed allocation is an error return.  When the packets are binned for
+ * the LDS tile kernel, L is slot 0's and a map cell is c x c field cells with
+ * c dividing the tile side, one workgroup per tile accumulates in LDS; any
+ * other case adds per packet through global memory: the same integers.
+ * SWRT_ERR_STATE before swrt_map_series_begin, SWRT_ERR_ARG without packets
+ * or with more than 2^24. */
+int swrt_map_series_record(swrt_ctx* ctx);
+
+/* One frame per history frame in [first, first + count): the same bits as
+ * swrt_map_series_record on packets set to that frame.  A range out of
+ * bounds: SWRT_ERR_ARG. */
+int swrt_map_series_record_history(swrt_ctx* ctx, int64_t first, int64_t count);
+
+/* Frames recorded since begin or the last reset; m of the open series, 0 if none. */
+int64_t swrt_map_series_frames(const swrt_ctx* ctx);
+int64_t swrt_map_series_cells(const swrt_ctx* ctx);
+
+/* Frames [first, first + count): planes4_out count x 4 x m x m and stats2_out
+ * count x 2 (may be NULL), frame-major.  Waits for them. */
+int swrt_map_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* planes4_out,
+                        int64_t* stats2_out);
+
+/* Empty the series; L, m, f, Cg and frac_bits stay. */
+int swrt_map_series_reset(swrt_ctx* ctx);
+
 /* ---------------------------------------------------------------------------
  * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
  * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)
@@ -792,7 +847,12 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
  *   packets every n accepted steps (0: never inside a run); speed only, the
  *   same bits for every n.
  * SWRT_DEBUG_ODE23_DENSE_REBINS (get only): the re-binnings swrt_ode23_run_at
- *   made inside its runs. */
+ *   made inside its runs.
+ * SWRT_DEBUG_MAP_TILED_FRAMES (get only): map frames recorded by the tile
+ *   path (swrt_map_series_record), summed over the context's life.
+ * SWRT_DEBUG_MAP_STRAYS (get only): packets the tile path added through
+ *   global memory because they had drifted out of their tile's LDS window,
+ *   summed over those frames; reading it waits for the queued records. */
 #define SWRT_DEBUG_HAZARD_CHECK 1
 #define SWRT_DEBUG_SPIN_US 2
 #define SWRT_DEBUG_LEGACY_PARK 3
@@ -808,6 +868,8 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
 #define SWRT_DEBUG_ODE23_FIRST_CHAINED 14
 #define SWRT_DEBUG_ODE23_DENSE_REBIN 15
 #define SWRT_DEBUG_ODE23_DENSE_REBINS 16
+#define SWRT_DEBUG_MAP_TILED_FRAMES 17
+#define SWRT_DEBUG_MAP_STRAYS 18
 int swrt_debug_set(swrt_ctx* ctx, int key, int64_t value);
 int swrt_debug_get(swrt_ctx* ctx, int key, int64_t* value_out);
 

@@ -60,5 +60,33 @@ classdef SwrtContext < handle
         function counts = omega_ideal(obj, slot, ring, omega0, edges)
             counts = swrt_mex('omega_ideal', obj.id(), slot, ring, omega0, edges);
         end
+
+        % The packet density and wave-energy maps of the device-resident
+        % packets (what generate_image.m:9-34 scatters packet by packet):
+        % m x m cells over the periodic square of side L, integer sums of
+        % the moments quantised to 2^-frac_bits.
+        function map_series_begin(obj, L, m, f, Cg, frac_bits)
+            if nargin < 6, frac_bits = 20; end
+            swrt_mex('map_series_begin', obj.id(), L, m, f, Cg, frac_bits);
+        end
+
+        function map_series_record(obj)
+            swrt_mex('map_series_record', obj.id());
+        end
+
+        function map_series_record_history(obj, first, count)
+            % history frames first .. first+count-1, 0-based
+            swrt_mex('map_series_record_history', obj.id(), first, count);
+        end
+
+        function [planes, stats] = map_series_get(obj)
+            % planes: m x m x 4 x frames [count, sum q(omega), sum q(k), sum q(l)], first index x;
+            % stats: 2 x frames [n; rejected]
+            [planes, stats] = swrt_mex('map_series_get', obj.id());
+        end
+
+        function map_series_reset(obj)
+            swrt_mex('map_series_reset', obj.id());
+        end
     end
 end

@@ -46,6 +46,10 @@
 //   [counts, stats] = swrt_mex('omega_series_get', h)         % (nbins+2) x frames, 4 x frames
 //   swrt_mex('omega_series_reset', h)
 //   counts = swrt_mex('omega_ideal', h, slot, ring, omega0, edges)   % ideal_omega_distribution.m:3-11
+//   swrt_mex('map_series_begin', h, L, m, f, Cg[, frac_bits])  % packet density / wave-energy maps on the device
+//   swrt_mex('map_series_record', h);  swrt_mex('map_series_record_history', h, first, count)
+//   [planes, stats] = swrt_mex('map_series_get', h)           % m x m x 4 x frames, 2 x frames
+//   swrt_mex('map_series_reset', h)
 #include <cstring>
 #include <string>
 #include <vector>
@@ -462,6 +466,40 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
           "swrt_omega_ideal");
     plhs[0] = mxCreateDoubleMatrix((mwSize)counts.size(), 1, mxREAL);
     for (size_t i = 0; i < counts.size(); ++i) mxGetDoubles(plhs[0])[i] = (double)counts[i];
+    return;
+  }
+  if (!strcmp(cmd, "map_series_begin")) {  // (L, m, f, Cg[, frac_bits = 20])
+    need(na, 5, cmd);
+    check(c, swrt_map_series_begin(c, scalar(a[1]), (int64_t)scalar(a[2]), scalar(a[3]), scalar(a[4]),
+                                   na > 5 ? (int)scalar(a[5]) : 20),
+          "swrt_map_series_begin");
+    return;
+  }
+  if (!strcmp(cmd, "map_series_record")) {
+    check(c, swrt_map_series_record(c), "swrt_map_series_record");
+    return;
+  }
+  if (!strcmp(cmd, "map_series_record_history")) {  // (first, count): 0-based history frames
+    need(na, 3, cmd);
+    check(c, swrt_map_series_record_history(c, (int64_t)scalar(a[1]), (int64_t)scalar(a[2])),
+          "swrt_map_series_record_history");
+    return;
+  }
+  if (!strcmp(cmd, "map_series_get")) {  // -> planes m x m x 4 x frames (double, exact), stats 2 x frames
+    const int64_t nf = swrt_map_series_frames(c), m = swrt_map_series_cells(c);
+    std::vector<int64_t> planes((size_t)(nf * 4 * m * m)), st((size_t)(nf * 2));
+    const mwSize dims[4] = {(mwSize)m, (mwSize)m, 4, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(4, dims, mxDOUBLE_CLASS, mxREAL);
+    mxArray* stats = mxCreateDoubleMatrix(2, (mwSize)nf, mxREAL);
+    check(c, swrt_map_series_get(c, 0, nf, planes.data(), st.data()), "swrt_map_series_get");
+    double* d = mxGetDoubles(plhs[0]);
+    for (size_t i = 0; i < planes.size(); ++i) d[i] = (double)planes[i];
+    for (size_t i = 0; i < st.size(); ++i) mxGetDoubles(stats)[i] = (double)st[i];
+    if (nlhs > 1) plhs[1] = stats; else mxDestroyArray(stats);
+    return;
+  }
+  if (!strcmp(cmd, "map_series_reset")) {
+    check(c, swrt_map_series_reset(c), "swrt_map_series_reset");
     return;
   }
   mexErrMsgIdAndTxt("swrt:arg", "unknown command '%s'", cmd);

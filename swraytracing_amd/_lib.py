@@ -92,6 +92,13 @@ SIGNATURES = {
     "swrt_omega_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), _P]),
     "swrt_omega_series_reset": (_INT, [_VP]),
     "swrt_omega_ideal": (_INT, [_VP, _INT, _P, _I, _D, _P, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_map_series_begin": (_INT, [_VP, _D, _I, _D, _D, _INT]),
+    "swrt_map_series_record": (_INT, [_VP]),
+    "swrt_map_series_record_history": (_INT, [_VP, _I, _I]),
+    "swrt_map_series_frames": (_I, [_VP]),
+    "swrt_map_series_cells": (_I, [_VP]),
+    "swrt_map_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_map_series_reset": (_INT, [_VP]),
     "swrt_raydiag_mark": (_INT, [_VP, _D, _D, _INT, _D, _D]),
     "swrt_raydiag_sample": (_INT, [_VP, _D, _D, _INT, _D, _D, _P, _P]),
     "swrt_raydiag_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
@@ -162,6 +169,8 @@ DEBUG_ODE23_SPLIT_RUNS = 13
 DEBUG_ODE23_FIRST_CHAINED = 14
 DEBUG_ODE23_DENSE_REBIN = 15
 DEBUG_ODE23_DENSE_REBINS = 16
+DEBUG_MAP_TILED_FRAMES = 17
+DEBUG_MAP_STRAYS = 18
 
 _lib = None
 
@@ -562,6 +571,41 @@ class Context:
                                            edges.size - 1, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
                   "swrt_omega_ideal")
         return counts
+
+    # ---- the map series (swrt_map_series_*: packet density and wave energy) ----
+    def map_series_begin(self, L, m, f, Cg, frac_bits=20):
+        """Open a series of m x m maps over the periodic square of side ``L``;
+        moments quantised to 2^-frac_bits.  Empties the series."""
+        self._chk(self._L.swrt_map_series_begin(self._h, float(L), int(m), float(f), float(Cg), int(frac_bits)),
+                  "swrt_map_series_begin")
+
+    def map_series_record(self):
+        """Append the current packets' map frame to the device-side series (queued; no host wait)."""
+        self._chk(self._L.swrt_map_series_record(self._h), "swrt_map_series_record")
+
+    def map_series_record_history(self, first, count):
+        """One map frame per history frame [first, first + count) (queued; no host wait)."""
+        self._chk(self._L.swrt_map_series_record_history(self._h, int(first), int(count)),
+                  "swrt_map_series_record_history")
+
+    def map_series_frames(self):
+        return int(self._L.swrt_map_series_frames(self._h))
+
+    def map_series(self, first=0, count=None):
+        """Recorded frames [first, first + count) -> (planes (count, 4, m, m)
+        int64 [count, sum q(omega), sum q(k), sum q(l)], planes[t, p, i, j] the
+        cell with x index i and y index j; stats (count, 2) int64 [n, rejected])."""
+        count = self.map_series_frames() - first if count is None else count
+        m = int(self._L.swrt_map_series_cells(self._h))
+        planes = np.zeros((max(count, 0), 4, m, m), dtype=np.int64)
+        stats = np.zeros((max(count, 0), 2), dtype=np.int64)
+        i64 = ctypes.POINTER(ctypes.c_int64)
+        self._chk(self._L.swrt_map_series_get(self._h, int(first), int(count), planes.ctypes.data_as(i64),
+                                              stats.ctypes.data_as(i64)), "swrt_map_series_get")
+        return planes.transpose(0, 1, 3, 2), stats  # (the device's planes are column-major)
+
+    def map_series_reset(self):
+        self._chk(self._L.swrt_map_series_reset(self._h), "swrt_map_series_reset")
 
     # ---- the invariant and the flow along the rays (swrt_raydiag_*) ----------
     def raydiag_mark(self, f, gH, nslots=1, alpha=0.0, bump=1e-13):

@@ -28,6 +28,7 @@
 #include "swrt_hazard.hpp"
 #include "swrt_diag.hpp"
 #include "swrt_raydiag.hpp"
+#include "swrt_map.hpp"
 #include "swrt_res.hpp"
 
 using namespace swrt;
@@ -1465,6 +1466,206 @@ int swrt_omega_ideal(swrt_ctx* c, int slot, const double* ring_k, int64_t m, dou
   GUARD_END(c)
 }
 
+// ---- the map series (swrt_map.hpp) ----
+// Frames reserved by the first record: 64 MiB worth, at least one, at most 4096.
+inline int64_t map_series_min(size_t frame_bytes) {
+  return std::min<int64_t>(4096, std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / frame_bytes)));
+}
+
+// Room for `extra` more frames, as omega_reserve: growing keeps the recorded
+// frames and waits for the stream.  The frames are zeroed by the calls that
+// fill them.
+static int map_reserve(swrt_ctx* c, int64_t extra) {
+  MapSeriesState& ms = c->map;
+  if (ms.frames + extra <= ms.cap) return SWRT_OK;
+  const size_t fr = (size_t)kMapPlanes * ms.m * ms.m;
+  const int64_t ncap =
+      std::max<int64_t>({map_series_min(fr * sizeof(unsigned long long)), 2 * ms.cap, ms.frames + extra});
+  DevBuf<unsigned long long> np, ns;
+  HIPCHK(c, np.alloc(fr * ncap));
+  HIPCHK(c, ns.alloc((size_t)kMapStats * ncap));
+  if (ms.frames > 0) {
+    HIPCHK(c, hipMemcpyAsync(np.get(), ms.planes.get(), sizeof(unsigned long long) * fr * ms.frames,
+                             hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ns.get(), ms.stats.get(), sizeof(unsigned long long) * kMapStats * ms.frames,
+                             hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  hz_synced(c);
+  ms.planes = std::move(np);
+  ms.stats = std::move(ns);
+  ms.cap = ncap;
+  return SWRT_OK;
+}
+
+static MapGeom map_geom(const MapSeriesState& ms) {
+  MapGeom g;
+  g.dxm = ms.L / (double)ms.m;  // (as view_of's dx = L/nx)
+  g.inv_dxm = 1.0 / g.dxm;
+  g.pm = (double)ms.m;
+  g.inv_pm = 1.0 / g.pm;
+  g.m = ms.m;
+  g.f2 = ms.f2;
+  g.Cg2 = ms.Cg2;
+  g.scale = std::ldexp(1.0, ms.frac_bits);
+  return g;
+}
+
+// Zero `count` frames from the series' end on (planes and stats), on the stream.
+static int map_zero_frames(swrt_ctx* c, int64_t count) {
+  MapSeriesState& ms = c->map;
+  const size_t fr = (size_t)kMapPlanes * ms.m * ms.m;
+  HIPCHK(c, hipMemsetAsync(ms.planes.get() + fr * ms.frames, 0, sizeof(unsigned long long) * fr * count, c->stream));
+  HIPCHK(c, hipMemsetAsync(ms.stats.get() + (size_t)kMapStats * ms.frames, 0,
+                           sizeof(unsigned long long) * kMapStats * count, c->stream));
+  return SWRT_OK;
+}
+
+// `count` frames from the series' end on by the general kernel: frame i from
+// the packets at x + i*stride, k + i*stride (any order).
+static int map_general_launch(swrt_ctx* c, const double* x, const double* k, int64_t stride, int64_t count) {
+  MapSeriesState& ms = c->map;
+  const size_t fr = (size_t)kMapPlanes * ms.m * ms.m;
+  const int nblk = (int)std::min<int64_t>(kMapBlocks, nblocks(c->n, kMapThreads));
+  hipLaunchKernelGGL(map_general_kernel, dim3(nblk, (unsigned)count), dim3(kMapThreads), 0, c->stream, x, k, c->n,
+                     stride, map_geom(ms), ms.planes.get() + fr * ms.frames,
+                     ms.stats.get() + (size_t)kMapStats * ms.frames);
+  HIPCHK(c, hipGetLastError());
+  ms.frames += count;
+  return SWRT_OK;
+}
+
+// The tile path applies: the packets are in the order of the LDS tile kernel's
+// binning of slot 0's grid, the map covers that grid's square, and a map cell
+// is c x c field cells with c dividing the tile side.
+static bool map_tiled(const swrt_ctx* c) {
+  const MapSeriesState& ms = c->map;
+  const Slot& s = c->slot[0];
+  if (!s.set || !tile_binned(c) || c->bin.tile() != kTile) return false;
+  if (ms.L != s.L || s.nx % ms.m != 0) return false;
+  return kTile % (s.nx / ms.m) == 0;
+}
+
+int swrt_map_series_begin(swrt_ctx* c, double L, int64_t m, double f, double Cg, int frac_bits) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  if (m < 1 || m > kMapMaxCells) return fail(c, SWRT_ERR_ARG, "m must be 1..4096");
+  if (!(L > 0.0) || !std::isfinite(L)) return fail(c, SWRT_ERR_ARG, "L must be positive and finite");
+  if (frac_bits < 0 || frac_bits > kMapMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
+  if (c->n > kMapMaxPackets) return fail(c, SWRT_ERR_ARG, "a map frame takes at most 2^24 packets");
+  HIPCHK(c, hipSetDevice(c->device));
+  MapSeriesState& ms = c->map;
+  // (queued records may still write the old series: wait before releasing it)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  hz_synced(c);
+  ms.open = false;
+  ms.frames = 0;
+  ms.cap = 0;
+  ms.planes.reset();
+  ms.stats.reset();
+  if (!ms.strays) {
+    HIPCHK(c, ms.strays.alloc(1));
+    HIPCHK(c, hipMemsetAsync(ms.strays.get(), 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  ms.m = (int)m;
+  ms.frac_bits = frac_bits;
+  ms.L = L;
+  ms.f2 = f * f;
+  ms.Cg2 = Cg * Cg;
+  ms.open = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+static int map_series_check(swrt_ctx* c) {
+  if (!c->map.open) return fail(c, SWRT_ERR_STATE, "call swrt_map_series_begin first");
+  HIPCHK_RC(lost_check(c));
+  if (c->n == 0) return fail(c, SWRT_ERR_ARG, "no packets (swrt_packets_set first)");
+  if (c->n > kMapMaxPackets) return fail(c, SWRT_ERR_ARG, "a map frame takes at most 2^24 packets");
+  return SWRT_OK;
+}
+
+int swrt_map_series_record(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(map_series_check(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(map_reserve(c, 1));
+  HIPCHK_RC(map_zero_frames(c, 1));
+  MapSeriesState& ms = c->map;
+  if (!map_tiled(c)) return map_general_launch(c, c->pk.cur.x.get(), c->pk.cur.k.get(), 0, 1);
+  MapTileArgs a;
+  a.x = c->pk.cur.x.get();
+  a.k = c->pk.cur.k.get();
+  a.n = c->n;
+  a.starts = c->bins.starts();
+  a.order = c->bins.tile_order();
+  a.ntx = tiles_per_side(c->slot[0].nx);
+  a.c = (int)(c->slot[0].nx / ms.m);
+  a.g = map_geom(ms);
+  a.planes = ms.planes.get() + (size_t)kMapPlanes * ms.m * ms.m * ms.frames;
+  a.stats = ms.stats.get() + (size_t)kMapStats * ms.frames;
+  a.strays = ms.strays.get();
+  hipLaunchKernelGGL((map_tile_kernel<kTile, kMargin>), dim3((unsigned)(a.ntx * a.ntx)), dim3(kMapThreads), 0,
+                     c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  ++ms.frames;
+  ++ms.tiled_frames;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_map_series_record_history(swrt_ctx* c, int64_t first, int64_t count) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(map_series_check(c));
+  if (first < 0 || count < 0 || first + count > c->hframes)
+    return fail(c, SWRT_ERR_ARG, "history frame range out of bounds");
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(map_reserve(c, count));
+  HIPCHK_RC(map_zero_frames(c, count));
+  for (int64_t i = 0; i < count; i += kMapHistoryChunk) {
+    const int64_t nf = std::min<int64_t>(kMapHistoryChunk, count - i);
+    HIPCHK_RC(map_general_launch(c, c->hx.get() + (first + i) * 2 * c->n, c->hk.get() + (first + i) * 2 * c->n,
+                                 2 * c->n, nf));
+  }
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int64_t swrt_map_series_frames(const swrt_ctx* c) { return c ? c->map.frames : -1; }
+
+int64_t swrt_map_series_cells(const swrt_ctx* c) { return c ? (c->map.open ? c->map.m : 0) : -1; }
+
+int swrt_map_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* planes4_out, int64_t* stats2_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  const MapSeriesState& ms = c->map;
+  if (first < 0 || count < 0 || first + count > ms.frames) return fail(c, SWRT_ERR_ARG, "frame range out of bounds");
+  if (count == 0) return SWRT_OK;
+  if (!planes4_out) return fail(c, SWRT_ERR_ARG, "NULL buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t fr = (size_t)kMapPlanes * ms.m * ms.m;
+  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "a frame is copied out as it is");
+  HIPCHK(c, hipMemcpyAsync(planes4_out, ms.planes.get() + fr * first, sizeof(int64_t) * fr * count,
+                           hipMemcpyDeviceToHost, c->stream));
+  if (stats2_out)
+    HIPCHK(c, hipMemcpyAsync(stats2_out, ms.stats.get() + (size_t)kMapStats * first,
+                             sizeof(int64_t) * kMapStats * count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return dev_err_check(c);
+  GUARD_END(c)
+}
+
+int swrt_map_series_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (as swrt_omega_series_reset)
+  c->map.frames = 0;
+  return SWRT_OK;
+}
+
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
@@ -1568,6 +1769,17 @@ int swrt_debug_get(swrt_ctx* c, int key, int64_t* value_out) {
     case SWRT_DEBUG_ODE23_FIRST_CHAINED: *value_out = c->o23.chain.first_taken; return SWRT_OK;
     case SWRT_DEBUG_ODE23_DENSE_REBIN: *value_out = c->o23.dense_rebin; return SWRT_OK;
     case SWRT_DEBUG_ODE23_DENSE_REBINS: *value_out = c->o23.dense_rebins; return SWRT_OK;
+    case SWRT_DEBUG_MAP_TILED_FRAMES: *value_out = c->map.tiled_frames; return SWRT_OK;
+    case SWRT_DEBUG_MAP_STRAYS: {  // the device's counter: waits for the queued records
+      unsigned long long v = 0;
+      if (c->map.strays) {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipMemcpyAsync(&v, c->map.strays.get(), sizeof(v), hipMemcpyDeviceToHost, c->stream0.get()));
+        HIPCHK(c, hipStreamSynchronize(c->stream0.get()));
+      }
+      *value_out = (int64_t)v;
+      return SWRT_OK;
+    }
     default: return fail(c, SWRT_ERR_ARG, "unknown debug key");
   }
 }

@@ -335,6 +335,21 @@ struct OmegaSeriesState {
   int64_t cap = 0;          // frames allocated
 };
 
+// the map series (swrt_map_series_*, swrt_map.hpp).  Buffers of its own, as
+// OmegaSeriesState's; a frame is self-contained (its n is in its stats).
+struct MapSeriesState {
+  bool open = false;        // swrt_map_series_begin was called
+  int m = 0;                // cells per side of the open series
+  int frac_bits = 0;
+  double L = 0.0, f2 = 0.0, Cg2 = 0.0;
+  DevBuf<unsigned long long> planes;  // recorded frames, kMapPlanes x m x m each
+  DevBuf<unsigned long long> stats;   // recorded stats, kMapStats each
+  DevBuf<unsigned long long> strays;  // one counter: packets the tile path added through global memory
+  int64_t frames = 0;
+  int64_t cap = 0;          // frames allocated
+  int64_t tiled_frames = 0; // frames recorded by the tile path (SWRT_DEBUG_MAP_TILED_FRAMES)
+};
+
 // debug knobs (swrt_debug_set): a spin kernel queued on every extra packet
 // stream before each of its part launches (adversarial overlap of consecutive
 // calls), and the pre-third-buffer ordering after a source-gather sort
@@ -413,6 +428,7 @@ struct swrt_ctx {
   Ode23State o23;
   RayDiagState rd;
   OmegaSeriesState om;
+  MapSeriesState map;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an
   // event marker, ~7 us of idle on each stream).  Only consecutive split

@@ -79,6 +79,47 @@ def energy_spectrum(counts, edges, lo=0, hi=None):
     return center, center * distribution
 
 
+MAP_DRAIN_BYTES = 256 << 20  # record_map drains the device series into the files above this
+
+
+def combine_maps(parts):
+    """The map series of an ensemble from its shards' series
+    (swrt_map_series_*).  ``parts``: a sequence of (planes, stats) pairs, one
+    per shard, planes (T, 4, m, m) int64 and stats (T, 2) int64 [n, rejected]:
+    the element-wise sum (integer, exact and order-free).  A shard without
+    packets stands as zeros."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no series to combine")
+    planes = np.stack([np.asarray(p, dtype=np.int64) for p, _ in parts])
+    stats = np.stack([np.asarray(s, dtype=np.int64) for _, s in parts])
+    if planes.ndim != 5 or planes.shape[2] != 4 or stats.shape != planes.shape[:2] + (2,):
+        raise ValueError("every shard must give planes (T, 4, m, m) and stats (T, 2) for the same T and m")
+    return planes.sum(axis=0), stats.sum(axis=0)
+
+
+def map_fields(planes, frac_bits):
+    """Physical fields of map planes (..., 4, m, m) int64 as fp64: ``n`` the
+    packet count per cell, ``energy`` the wave energy per cell at unit action
+    per packet (load_data.m:49: sum omega), ``k_mean`` and ``l_mean`` the mean
+    wavevector; the last three NaN where the count is 0."""
+    planes = np.asarray(planes)
+    if planes.ndim < 3 or planes.shape[-3] != 4:
+        raise ValueError("planes must be (..., 4, m, m)")
+    if not 0 <= int(frac_bits) <= 32:
+        raise ValueError("frac_bits must be 0..32")
+    unit = 2.0 ** -int(frac_bits)
+    n = planes[..., 0, :, :].astype(np.float64)
+    empty = n == 0
+    count = np.where(empty, 1.0, n)
+    out = dict(n=n, energy=planes[..., 1, :, :].astype(np.float64) * unit,
+               k_mean=planes[..., 2, :, :].astype(np.float64) / count * unit,
+               l_mean=planes[..., 3, :, :].astype(np.float64) / count * unit)
+    for name in ("energy", "k_mean", "l_mean"):
+        out[name][empty] = np.nan
+    return out
+
+
 def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False):
     """[x, k, t] = ode_symplectic(x0, k0, dt, T, f, gH, scheme).
 
@@ -537,6 +578,97 @@ class PacketEnsemble:
                 write_field(st, os.path.join(directory, "omega_stats"))
             write_field(self._spec_edges, os.path.join(directory, "omega_edges"))
         return self._spec_frames
+
+    def begin_map(self, m, frac_bits=20, directory=None):
+        """Open the series of m x m packet density and wave-energy maps of
+        this run over the ensemble's periodic square (swrt_map_series_begin
+        with its L, f, Cg).  ``directory``: where record_map drains the device
+        series when it grows large (default: the drained frames wait in host
+        memory for write_maps)."""
+        m, frac_bits = int(m), int(frac_bits)
+        if not 1 <= m <= 4096:
+            raise ValueError("map cells must be 1..4096")
+        if not 0 <= frac_bits <= 32:
+            raise ValueError("map frac_bits must be 0..32")
+        self._map = dict(m=m, frac_bits=frac_bits, directory=directory, frames=0, pending=0, kept=[])
+        if self.n > 0:
+            self.ctx.map_series_begin(self.L, m, self.f, self.Cg, frac_bits)
+
+    def record_map(self):
+        """Append this shard's map frame at the current state to the
+        device-side series (queued, no host wait).  An empty shard records
+        nothing.  When the device series holds more than 256 MB it is drained
+        (get, combine, append, reset): a collective when sharded, at the same
+        frame on every rank."""
+        st = getattr(self, "_map", None)
+        if st is None:
+            raise SwrtError("record_map: call begin_map first")
+        st["frames"] += 1
+        st["pending"] += 1
+        if self.n > 0:
+            self.ctx.map_series_record()
+        if st["pending"] * 32 * st["m"] * st["m"] > MAP_DRAIN_BYTES:
+            self._drain_maps()
+
+    def _drain_maps(self):
+        """The frames on the device, combined over the shards, to the files or
+        the host list of rank 0; the device series emptied."""
+        st = self._map
+        T, m = st["pending"], st["m"]
+        if T == 0:
+            return
+        if self.n > 0:
+            planes, stats = self.ctx.map_series(0, T)
+            self.ctx.map_series_reset()
+        else:
+            planes, stats = np.zeros((T, 4, m, m), dtype=np.int64), np.zeros((T, 2), dtype=np.int64)
+        st["pending"] = 0
+        if self.world > 1:
+            import torch
+            import torch.distributed as dist
+
+            from .dist import _device_for
+            dev = _device_for(dist.get_backend())
+            summed = []
+            for a in (planes, stats):
+                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                dist.all_reduce(buf, op=dist.ReduceOp.SUM)  # (int64: exact, order-free)
+                summed.append(buf.cpu().numpy())
+            if self.rank != 0:
+                return
+            planes, stats = summed
+        if st["directory"] is None:
+            st["kept"].append((planes, stats))
+        else:
+            self._append_maps(st["directory"], planes, stats)
+
+    def _append_maps(self, directory, planes, stats):
+        st = self._map
+        for fr, s in zip(planes, stats):
+            for name, plane in zip(("map_n", "map_omega", "map_k", "map_l"), fr):
+                write_field(plane, os.path.join(directory, name))
+            write_field(np.array([s[0], s[1], st["m"], st["frac_bits"]], dtype=np.float64),
+                        os.path.join(directory, "map_stats"))
+
+    def write_maps(self, directory):
+        """The run's map series as write_field files (read_field(name, m, m, 1,
+        frames) reads them): map_n.bin, map_omega.bin, map_k.bin, map_l.bin —
+        the four planes [count, sum q(omega), sum q(k), sum q(l)] as exact
+        fp64 integers (every one below 2^53), one m x m frame each per record,
+        first index x — and map_stats.bin, [n, rejected, m, frac_bits] per
+        frame.  Sharded: a collective; rank 0 writes.  Returns the frames
+        recorded."""
+        st = getattr(self, "_map", None)
+        if st is None:
+            raise SwrtError("write_maps: call begin_map first")
+        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
+            raise ValueError("write_maps: begin_map drained into another directory")
+        self._drain_maps()
+        if st["directory"] is None:
+            for planes, stats in st["kept"]:
+                self._append_maps(directory, planes, stats)
+            st["kept"] = []
+        return st["frames"]
 
     def write_frame(self, t, directory, packet_files=True):
         """qgsw_raytrace.m:159-162: wrapped x, k and t appended to

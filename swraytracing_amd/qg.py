@@ -230,7 +230,8 @@ def _fresh_outputs(out_dir, fresh):
     os.makedirs(out_dir, exist_ok=True)
     if not fresh:
         return
-    for name in ("packet_x", "packet_k", "packet_time", "pv", "pv_time", "omega_hist", "omega_stats", "omega_edges"):
+    for name in ("packet_x", "packet_k", "packet_time", "pv", "pv_time", "omega_hist", "omega_stats", "omega_edges",
+                 "map_n", "map_omega", "map_k", "map_l", "map_stats"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
@@ -248,11 +249,24 @@ def _spectrum_args(spectrum_edges, packet_files):
     return edges
 
 
-def _save_frame(ens, t, out_dir, spectrum, packet_files):
-    """One packet frame: its spectrum recorded on the device (queued, no host
+def _map_args(map_cells, map_frac_bits):
+    """The drivers' ``map_cells`` / ``map_frac_bits`` checked before anything runs."""
+    if map_cells is None:
+        return None
+    if isinstance(map_cells, bool) or int(map_cells) != map_cells or not 1 <= int(map_cells) <= 4096:
+        raise ValueError("map_cells must be an integer 1..4096")
+    if isinstance(map_frac_bits, bool) or int(map_frac_bits) != map_frac_bits or not 0 <= int(map_frac_bits) <= 32:
+        raise ValueError("map_frac_bits must be an integer 0..32")
+    return int(map_cells), int(map_frac_bits)
+
+
+def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False):
+    """One packet frame: its spectrum and its map recorded on the device (queued, no host
     wait) whether or not the frame itself is written."""
     if spectrum:
         ens.record_spectrum()
+    if maps:
+        ens.record_map()
     ens.write_frame(t, out_dir, packet_files)
 
 
@@ -502,7 +516,8 @@ class ReceiverLoop:
 def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_days, U_g, f, Cg, *,
                   out_dir="data", nsub=4, max_steps=None, seed=146, verbose=False, r_drag=0.1,
                   packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
-                  pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None, packet_files=True):
+                  pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None, packet_files=True,
+                  map_cells=None, map_frac_bits=20):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -525,10 +540,16 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     values per frame: below, the bins, above), omega_stats.bin (n, sum omega,
     min, max per frame) and omega_edges.bin.  ``packet_files=False`` skips the
     packet_x.bin / packet_k.bin downloads and writes (packet_time.bin stays:
-    the spectrum frames' times); it needs ``spectrum_edges``.  Returns a dict
-    of run facts (dt, Nsteps, steps run, frames written, final t,
-    spectrum_frames)."""
+    the spectrum frames' times); it needs ``spectrum_edges``.  ``map_cells``
+    (m, 1..4096): every packet frame's m x m packet density and wave-energy
+    map over the domain is recorded on the device (swrt_map_series_*; moments
+    quantised to 2^-``map_frac_bits``) and written as map_n.bin, map_omega.bin,
+    map_k.bin, map_l.bin (one m x m frame each per packet frame, exact
+    integers) and map_stats.bin (n, rejected, m, frac_bits per frame).
+    Returns a dict of run facts (dt, Nsteps, steps run, frames written,
+    final t, spectrum_frames, map_frames)."""
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files)
+    map_args = _map_args(map_cells, map_frac_bits)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
@@ -580,8 +601,11 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     spectrum = ens is not None and spectrum_edges is not None
     if spectrum:
         ens.begin_spectrum(spectrum_edges)
+    maps = ens is not None and map_args is not None
+    if maps:
+        ens.begin_map(*map_args, directory=out_dir)
     if ens is not None:
-        _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files)
+        _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files, maps)
     if rank == 0:
         write_field(model.q(), os.path.join(out_dir, "pv"))
         write_field(np.array([[t]]), os.path.join(out_dir, "pv_time"))
@@ -606,7 +630,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
             group.add(dt)
             if (step - packet_step_start + 1) % packet_steps_per_save == 0:
                 group.flush()
-                _save_frame(ens, t, out_dir, spectrum, packet_files)
+                _save_frame(ens, t, out_dir, spectrum, packet_files, maps)
                 frames += 1
         else:
             have_cur = False
@@ -619,25 +643,27 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     if link is not None:
         link.close()
     spectrum_frames = ens.write_spectrum(out_dir) if spectrum else 0
+    map_frames = ens.write_maps(out_dir) if maps else 0
     ctx.synchronize()
     ctx.set_timing(timing)
     log.finish()
     log.close()
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
-                packet_step_start=packet_step_start, spectrum_frames=spectrum_frames)
+                packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames)
 
 
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
                         out_dir="data", nsub=5, max_steps=None, seed=5, verbose=False,
                         packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
                         pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None,
-                        packet_files=True):
+                        packet_files=True, map_cells=None, map_frac_bits=20):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
     pv.bin holds the initial nx x nx x 2 frame only, as in the reference.
     ``packet_intervals``, ``integrator``, ``fresh``, ``spectrum_edges``,
-    ``packet_files``: as in :func:`qgsw_raytrace`.
+    ``packet_files``, ``map_cells``, ``map_frac_bits``: as in
+    :func:`qgsw_raytrace`.
 
     Sharded (torch.distributed, world > 1): ``pde="owner"`` (default) — rank 0
     steps the PDE and sends each step's top-layer qk and dt to the other
@@ -649,6 +675,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     owner link's buffers ("auto": on the device with nccl, on the host with
     gloo; "device" / "host" to force one)."""
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files)
+    map_args = _map_args(map_cells, map_frac_bits)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
@@ -691,8 +718,11 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     spectrum = ens is not None and spectrum_edges is not None
     if spectrum:
         ens.begin_spectrum(spectrum_edges)
+    maps = ens is not None and map_args is not None
+    if maps:
+        ens.begin_map(*map_args, directory=out_dir)
     if ens is not None:
-        _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files)
+        _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files, maps)
     if rank == 0:
         write_field(model.q(), os.path.join(out_dir, "pv"))
         write_field(np.array([[t]]), os.path.join(out_dir, "pv_time"))
@@ -714,7 +744,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     while loop.t <= T and (max_steps is None or loop.steps < max_steps):
         if loop.step() and (loop.steps - packet_step_start + 1) % packet_steps_per_save == 0:
             loop.flush()
-            _save_frame(ens, loop.t, out_dir, spectrum, packet_files)
+            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps)
             frames += 1
         log.progress(loop.steps, Nsteps)
     loop.flush()
@@ -722,6 +752,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     if link is not None:
         link.close()
     spectrum_frames = ens.write_spectrum(out_dir) if spectrum else 0
+    map_frames = ens.write_maps(out_dir) if maps else 0
     ctx.synchronize()
     ctx.set_timing(timing)
     log.finish()
@@ -729,4 +760,4 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     dt, dts, step, t = loop.dt, loop.dts, loop.steps, loop.t
     U0 = getattr(loop, "U0", U0)  # (a receiving rank never sees the owner's U0)
     return dict(dt=dt, dts=dts, Nsteps=Nsteps, steps=step, packet_frames=frames, t=t, U0=U0,
-                packet_step_start=packet_step_start, spectrum_frames=spectrum_frames)
+                packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames)
