@@ -78,6 +78,7 @@ __global__ void clock_stamp_kernel(unsigned long long* out) {
 #include "swrt_host_packets.hpp"
 #include "swrt_host_qg.hpp"
 #include "swrt_host_ode23.hpp"
+#include "swrt_host_diag.hpp"
 
 extern "C" {
 
@@ -463,7 +464,7 @@ int swrt_packets_set(swrt_ctx* c, const double* x, const double* k, int64_t n) {
   // a new ensemble starts a new history and needs binning before the next step
   if (c->dev_err) c->dev_err[0] = 0;  // (an error raised over the old ensemble is superseded)
   c->packets_lost = false;
-  c->hframes = 0;
+  c->hist.ext.cleared();
   c->steps_done = 0;
   c->bin.invalidate();
   return SWRT_OK;
@@ -585,7 +586,7 @@ int swrt_advance(swrt_ctx* c, double dt, int64_t nsteps, double f, double gH, in
   if (rc) return rc;
   rc = run_advance(c, dt, nsteps, f, gH, nslots, alpha0, dalpha, bump, save_every);
   if (rc) return rc;
-  c->hframes += new_frames;
+  c->hist.ext.committed(new_frames);
   c->steps_done += nsteps;
   // a QG stream renames slots by their use events: mark them after the second stream's launches too
   if (slot_events(c)) HIPCHK_RC(join_b(c));
@@ -627,28 +628,21 @@ int swrt_advance_intervals(swrt_ctx* c, int nintervals, const double* dts, int64
   GUARD_END(c)
 }
 
-int64_t swrt_history_frames(const swrt_ctx* c) { return c ? c->hframes : -1; }
+int64_t swrt_history_frames(const swrt_ctx* c) { return c ? c->hist.ext.frames() : -1; }
 
 int swrt_history_get(swrt_ctx* c, int64_t first, int64_t count, double* hist_x, double* hist_k) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  if (first < 0 || count < 0 || first + count > c->hframes)
-    return fail(c, SWRT_ERR_ARG, "history frame range out of bounds");
-  if (count == 0) return SWRT_OK;
-  if (!hist_x || !hist_k) return fail(c, SWRT_ERR_ARG, "NULL buffer");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t fb = sizeof(double) * 2 * c->n;
-  HIPCHK(c, hipMemcpyAsync(hist_x, (char*)c->hx.get() + fb * first, fb * count, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(hist_k, (char*)c->hk.get() + fb * first, fb * count, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return dev_err_check(c);
+  // (both columns are wanted: without hist_k the first counts as missing too)
+  return series_get(c, c->hist, 2 * c->n, 2 * c->n, first, count, hist_k ? hist_x : nullptr, hist_k,
+                    "history frame range out of bounds");
   GUARD_END(c)
 }
 
 int swrt_history_reset(swrt_ctx* c) {
   if (!c) return SWRT_ERR_ARG;
   c->s0_dirty = true;  // (conservative: settings and syncs may precede packet-stream work)
-  c->hframes = 0;
+  c->hist.ext.cleared();
   c->steps_done = 0;
   return SWRT_OK;
 }
@@ -663,7 +657,7 @@ int swrt_leapfrog(swrt_ctx* c, double* x, double* k, int64_t n, double dt, int64
   if ((rc = swrt_advance(c, dt, nsteps, f, gH, nslots, alpha0, dalpha, bump, se))) return rc;
   if ((rc = swrt_packets_get(c, x, k))) return rc;
   if (se > 0) {
-    if ((rc = swrt_history_get(c, 0, c->hframes, hist_x, hist_k))) return rc;
+    if ((rc = swrt_history_get(c, 0, c->hist.ext.frames(), hist_x, hist_k))) return rc;
   }
   return SWRT_OK;
 }
@@ -1082,88 +1076,7 @@ int swrt_omega_histogram(swrt_ctx* c, double f, double Cg, const double* edges, 
   GUARD_END(c)
 }
 
-// ---- ray diagnostics (swrt_raydiag.hpp) ----
-// The three calls' common checks: SWRT_ERR_ARG with a message, as the header says.
-static int raydiag_check(swrt_ctx* c, int nslots) {
-  HIPCHK_RC(lost_check(c));
-  if (nslots != 1 && nslots != 2) return fail(c, SWRT_ERR_ARG, "nslots must be 1 or 2");
-  for (int s = 0; s < nslots; ++s)
-    if (!c->slot[s].set) return fail(c, SWRT_ERR_ARG, "field slot not set");
-  if (nslots == 2 && (c->slot[1].nx != c->slot[0].nx || c->slot[1].L != c->slot[0].L ||
-                      c->slot[1].ny_period != c->slot[0].ny_period))
-    return fail(c, SWRT_ERR_ARG, "slots 0 and 1 have different grids");
-  if (c->n == 0) return fail(c, SWRT_ERR_ARG, "no packets (swrt_packets_set first)");
-  return SWRT_OK;
-}
-
-constexpr int64_t kRayDiagSeriesMin = 4096;  // frames reserved by the mark or the first record (256 KiB)
-
-// The per-packet buffers for the current ensemble and room for `extra` more
-// frames.  Growing the series keeps the recorded frames and waits for the
-// stream (the old buffer may still be written by a queued record).
-static int raydiag_reserve(swrt_ctx* c, int64_t extra) {
-  RayDiagState& rd = c->rd;
-  if (!rd.partial) HIPCHK(c, rd.partial.alloc(kRayDiagStats * kRayDiagBlocks + kRayDiagFrame));
-  if (c->n > rd.pcap) {  // (a larger ensemble: swrt_packets_set dropped the mark; releasing waits for queued readers)
-    rd.pcap = 0;
-    rd.marked = false;
-    HIPCHK(c, rd.omega0.alloc(c->n));
-    HIPCHK(c, rd.rec.alloc(kRayDiagRec * c->n));
-    rd.pcap = c->n;
-  }
-  if (rd.frames + extra <= rd.cap) return SWRT_OK;
-  const int64_t ncap = std::max<int64_t>({kRayDiagSeriesMin, 2 * rd.cap, rd.frames + extra});
-  DevBuf<double> ns;
-  HIPCHK(c, ns.alloc(kRayDiagFrame * ncap));
-  if (rd.frames > 0)
-    HIPCHK(c, hipMemcpyAsync(ns.get(), rd.series.get(), sizeof(double) * kRayDiagFrame * rd.frames,
-                             hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  hz_synced(c);
-  rd.series = std::move(ns);
-  rd.cap = ncap;
-  return SWRT_OK;
-}
-
-// One pass over the packets on the context's stream: the mark, or a sample
-// (then the reduction over its records) whose frame goes to `frame` (device)
-// and whose N x 4 values go to `sample4` (device, may be NULL).
-static int raydiag_launch(swrt_ctx* c, bool mark, double f, double gH, int nslots, double alpha, double bump,
-                          double* sample4, double* frame, const double* hist_x = nullptr,
-                          const double* hist_k = nullptr) {
-  RayDiagState& rd = c->rd;
-  RayDiagArgs a;
-  a.f0 = view_of(c->slot[0]);
-  a.f1 = nslots == 2 ? view_of(c->slot[1]) : a.f0;
-  a.nslots = nslots;
-  a.alpha = alpha;
-  a.bump = bump;
-  a.x = c->pk.cur.x.get();
-  a.k = c->pk.cur.k.get();
-  a.perm = c->pk.cur.perm.get();
-  if (hist_x) {  // a history frame: the same layout in the original packet order
-    a.x = hist_x;
-    a.k = hist_k;
-    a.perm = nullptr;
-  }
-  a.n = c->n;
-  a.f2 = f * f;
-  a.gH = gH;
-  a.omega0 = (mark || rd.marked) ? rd.omega0.get() : nullptr;
-  a.sample4 = sample4;
-  a.rec = rd.rec.get();
-  const dim3 grid(nblocks(c->n, kRayDiagThreads)), block(kRayDiagThreads);
-  hipLaunchKernelGGL(mark ? ray_diag_kernel<true> : ray_diag_kernel<false>, grid, block, 0, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  if (mark) return SWRT_OK;
-  const int nblk = (int)std::min<int64_t>(kRayDiagBlocks, grid.x);
-  hipLaunchKernelGGL(ray_diag_reduce_kernel, dim3(nblk), block, 0, c->stream, rd.rec.get(), c->n, rd.partial.get());
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(ray_diag_frame_kernel, dim3(1), dim3(64), 0, c->stream, rd.partial.get(), nblk, c->n, frame);
-  HIPCHK(c, hipGetLastError());
-  return SWRT_OK;
-}
-
+// ---- ray diagnostics (swrt_raydiag.hpp, swrt_host_diag.hpp) ----
 int swrt_raydiag_mark(swrt_ctx* c, double f, double gH, int nslots, double alpha, double bump) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
@@ -1210,10 +1123,7 @@ int swrt_raydiag_record(swrt_ctx* c, double f, double gH, int nslots, double alp
   HIPCHK_RC(raydiag_check(c, nslots));
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK_RC(raydiag_reserve(c, 1));
-  HIPCHK_RC(raydiag_launch(c, false, f, gH, nslots, alpha, bump, nullptr,
-                           c->rd.series.get() + kRayDiagFrame * c->rd.frames));
-  ++c->rd.frames;
-  return SWRT_OK;
+  return raydiag_record_frame(c, f, gH, nslots, alpha, bump);
   GUARD_END(c)
 }
 
@@ -1223,135 +1133,45 @@ int swrt_raydiag_record_history(swrt_ctx* c, int64_t first, int64_t count, doubl
   GUARD_BEGIN
   SlotUse slot_use(c);
   HIPCHK_RC(raydiag_check(c, nslots));
-  if (first < 0 || count < 0 || first + count > c->hframes)
-    return fail(c, SWRT_ERR_ARG, "history frame range out of bounds");
+  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
   if (nslots == 2 && !alphas && count > 0) return fail(c, SWRT_ERR_ARG, "NULL buffer (alphas, two snapshots)");
   if (count == 0) return SWRT_OK;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK_RC(raydiag_reserve(c, count));
   for (int64_t i = 0; i < count; ++i) {
     const int64_t off = (first + i) * 2 * c->n;
-    HIPCHK_RC(raydiag_launch(c, false, f, gH, nslots, alphas ? alphas[i] : 0.0, bump, nullptr,
-                             c->rd.series.get() + kRayDiagFrame * c->rd.frames, c->hx.get() + off,
-                             c->hk.get() + off));
-    ++c->rd.frames;
+    HIPCHK_RC(raydiag_record_frame(c, f, gH, nslots, alphas ? alphas[i] : 0.0, bump, c->hist.a.get() + off,
+                                   c->hist.b.get() + off));
   }
   return SWRT_OK;
   GUARD_END(c)
 }
 
-int64_t swrt_raydiag_frames(const swrt_ctx* c) { return c ? c->rd.frames : -1; }
+int64_t swrt_raydiag_frames(const swrt_ctx* c) { return c ? c->rd.series.ext.frames() : -1; }
 
 int swrt_raydiag_series_get(swrt_ctx* c, int64_t first, int64_t count, double* frames8_out) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  if (first < 0 || count < 0 || first + count > c->rd.frames)
-    return fail(c, SWRT_ERR_ARG, "frame range out of bounds");
-  if (count == 0) return SWRT_OK;
-  if (!frames8_out) return fail(c, SWRT_ERR_ARG, "NULL buffer");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(frames8_out, c->rd.series.get() + kRayDiagFrame * first,
-                           sizeof(double) * kRayDiagFrame * count, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return dev_err_check(c);
+  return series_get(c, c->rd.series, kRayDiagFrame, 0, first, count, frames8_out, nullptr, "frame range out of bounds");
   GUARD_END(c)
 }
 
 int swrt_raydiag_series_reset(swrt_ctx* c) {
   if (!c) return SWRT_ERR_ARG;
   c->s0_dirty = true;  // (conservative: settings and syncs may precede packet-stream work)
-  c->rd.frames = 0;
+  c->rd.series.ext.cleared();
   return SWRT_OK;
 }
 
-// ---- the spectrum series (swrt_diag.hpp) ----
-// swrt_omega_histogram's checks on the edges, finite as well.
-static int omega_edges_check(swrt_ctx* c, const double* edges, int64_t nbins) {
-  if (nbins <= 0 || nbins > kMaxHistBins) return fail(c, SWRT_ERR_ARG, "nbins must be 1..4096");
-  if (!edges) return fail(c, SWRT_ERR_ARG, "NULL buffer");
-  for (int64_t i = 0; i <= nbins; ++i)
-    if (!std::isfinite(edges[i])) return fail(c, SWRT_ERR_ARG, "edges must be finite");
-  for (int64_t i = 0; i < nbins; ++i)
-    if (!(edges[i] < edges[i + 1])) return fail(c, SWRT_ERR_ARG, "edges must increase");
-  return SWRT_OK;
-}
-
-inline size_t omega_lds_bytes(int nb) { return sizeof(double) * (nb + 1) + sizeof(unsigned int) * (nb + 2); }
-
-constexpr int64_t kOmegaSeriesMin = 4096;  // frames reserved by the first record
-
-// omega's per-packet buffer for the current ensemble and room for `extra` more
-// frames, as raydiag_reserve: growing keeps the recorded frames and waits for
-// the stream.  The rows are zeroed by the launches that fill them.
-static int omega_reserve(swrt_ctx* c, int64_t extra, bool need_w) {
-  OmegaSeriesState& om = c->om;
-  if (!om.partial) HIPCHK(c, om.partial.alloc((size_t)kOmegaHistoryChunk * kOmegaPartials * kOmegaBlocks));
-  if (need_w && c->n > om.pcap) {  // (releasing the old buffer waits for queued readers)
-    om.pcap = 0;
-    HIPCHK(c, om.w.alloc(c->n));
-    om.pcap = c->n;
-  }
-  if (om.frames + extra <= om.cap) return SWRT_OK;
-  const int64_t ncap = std::max<int64_t>({kOmegaSeriesMin, 2 * om.cap, om.frames + extra});
-  const size_t nslot = (size_t)om.nb + 2;
-  DevBuf<unsigned long long> nc;
-  DevBuf<double> ns;
-  HIPCHK(c, nc.alloc(nslot * ncap));
-  HIPCHK(c, ns.alloc((size_t)kOmegaStats * ncap));
-  if (om.frames > 0) {
-    HIPCHK(c, hipMemcpyAsync(nc.get(), om.counts.get(), sizeof(unsigned long long) * nslot * om.frames,
-                             hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(ns.get(), om.stats.get(), sizeof(double) * kOmegaStats * om.frames,
-                             hipMemcpyDeviceToDevice, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  hz_synced(c);
-  om.counts = std::move(nc);
-  om.stats = std::move(ns);
-  om.cap = ncap;
-  return SWRT_OK;
-}
-
-// `count` frames from the series' end on: omega_frame_kernel over src (omega
-// by original index, or the k of consecutive history frames), then their stats.
-static int omega_frames_launch(swrt_ctx* c, bool from_k, const double* src, int64_t src_stride, int64_t count) {
-  OmegaSeriesState& om = c->om;
-  OmegaFrameArgs a;
-  a.src = src;
-  a.src_stride = src_stride;
-  a.n = c->n;
-  a.f2 = om.f2;
-  a.Cg2 = om.Cg2;
-  a.edges = om.edges.get();
-  a.nb = om.nb;
-  a.counts = om.counts.get() + (size_t)(om.nb + 2) * om.frames;
-  a.partial = om.partial.get();
-  const int nblk = (int)std::min<int64_t>(kOmegaBlocks, nblocks(c->n, kOmegaThreads));
-  const dim3 grid(nblk, (unsigned)count), block(kOmegaThreads);
-  hipLaunchKernelGGL(from_k ? omega_frame_kernel<true> : omega_frame_kernel<false>, grid, block,
-                     omega_lds_bytes(om.nb), c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(omega_stats_kernel, dim3((unsigned)count), dim3(kOmegaThreads), 0, c->stream, om.partial.get(), nblk, c->n,
-                     om.stats.get() + (size_t)kOmegaStats * om.frames);
-  HIPCHK(c, hipGetLastError());
-  om.frames += count;
-  return SWRT_OK;
-}
-
+// ---- the spectrum series (swrt_diag.hpp, swrt_host_diag.hpp) ----
 int swrt_omega_series_begin(swrt_ctx* c, double f, double Cg, const double* edges, int64_t nbins) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
   HIPCHK_RC(omega_edges_check(c, edges, nbins));
   HIPCHK(c, hipSetDevice(c->device));
   OmegaSeriesState& om = c->om;
-  // (queued records may still write the old series: wait before releasing it)
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  hz_synced(c);
+  HIPCHK_RC(series_release(c, om.series));
   om.open = false;
-  om.frames = 0;
-  om.cap = 0;
-  om.counts.reset();
-  om.stats.reset();
   HIPCHK(c, om.edges.alloc(nbins + 1));
   HIPCHK(c, hipMemcpyAsync(om.edges.get(), edges, sizeof(double) * (nbins + 1), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1363,13 +1183,6 @@ int swrt_omega_series_begin(swrt_ctx* c, double f, double Cg, const double* edge
   GUARD_END(c)
 }
 
-static int omega_series_check(swrt_ctx* c) {
-  if (!c->om.open) return fail(c, SWRT_ERR_STATE, "call swrt_omega_series_begin first");
-  HIPCHK_RC(lost_check(c));
-  if (c->n == 0) return fail(c, SWRT_ERR_ARG, "no packets (swrt_packets_set first)");
-  return SWRT_OK;
-}
-
 int swrt_omega_series_record(swrt_ctx* c) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
@@ -1379,7 +1192,7 @@ int swrt_omega_series_record(swrt_ctx* c) {
   OmegaSeriesState& om = c->om;
   hipLaunchKernelGGL(omega_scatter_kernel, dim3(nblocks(c->n, kOmegaThreads)), dim3(kOmegaThreads), 0, c->stream,
                      c->pk.cur.k.get(), c->pk.cur.perm.get(), c->n, om.f2, om.Cg2, om.w.get(),
-                     om.counts.get() + (size_t)(om.nb + 2) * om.frames, om.nb + 2);
+                     om.series.end_a(om.row()), om.nb + 2);
   HIPCHK(c, hipGetLastError());
   return omega_frames_launch(c, false, om.w.get(), 0, 1);
   GUARD_END(c)
@@ -1389,50 +1202,36 @@ int swrt_omega_series_record_history(swrt_ctx* c, int64_t first, int64_t count) 
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
   HIPCHK_RC(omega_series_check(c));
-  if (first < 0 || count < 0 || first + count > c->hframes)
-    return fail(c, SWRT_ERR_ARG, "history frame range out of bounds");
+  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
   if (count == 0) return SWRT_OK;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK_RC(omega_reserve(c, count, false));
   OmegaSeriesState& om = c->om;
-  HIPCHK(c, hipMemsetAsync(om.counts.get() + (size_t)(om.nb + 2) * om.frames, 0,
-                           sizeof(unsigned long long) * (om.nb + 2) * count, c->stream));
+  HIPCHK(c, hipMemsetAsync(om.series.end_a(om.row()), 0, sizeof(unsigned long long) * om.row() * count, c->stream));
   for (int64_t i = 0; i < count; i += kOmegaHistoryChunk) {
     const int64_t m = std::min<int64_t>(kOmegaHistoryChunk, count - i);
-    HIPCHK_RC(omega_frames_launch(c, true, c->hk.get() + (first + i) * 2 * c->n, 2 * c->n, m));
+    HIPCHK_RC(omega_frames_launch(c, true, c->hist.b.get() + (first + i) * 2 * c->n, 2 * c->n, m));
   }
   return SWRT_OK;
   GUARD_END(c)
 }
 
-int64_t swrt_omega_series_frames(const swrt_ctx* c) { return c ? c->om.frames : -1; }
+int64_t swrt_omega_series_frames(const swrt_ctx* c) { return c ? c->om.series.ext.frames() : -1; }
 
 int64_t swrt_omega_series_bins(const swrt_ctx* c) { return c ? (c->om.open ? c->om.nb : 0) : -1; }
 
 int swrt_omega_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, double* stats4_out) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  if (first < 0 || count < 0 || first + count > c->om.frames)
-    return fail(c, SWRT_ERR_ARG, "frame range out of bounds");
-  if (count == 0) return SWRT_OK;
-  if (!counts_out) return fail(c, SWRT_ERR_ARG, "NULL buffer");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t nslot = (size_t)c->om.nb + 2;
-  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "a count row is copied out as it is");
-  HIPCHK(c, hipMemcpyAsync(counts_out, c->om.counts.get() + nslot * first, sizeof(int64_t) * nslot * count,
-                           hipMemcpyDeviceToHost, c->stream));
-  if (stats4_out)
-    HIPCHK(c, hipMemcpyAsync(stats4_out, c->om.stats.get() + (size_t)kOmegaStats * first,
-                             sizeof(double) * kOmegaStats * count, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return dev_err_check(c);
+  return series_get(c, c->om.series, c->om.row(), kOmegaStats, first, count, counts_out, stats4_out,
+                    "frame range out of bounds");
   GUARD_END(c)
 }
 
 int swrt_omega_series_reset(swrt_ctx* c) {
   if (!c) return SWRT_ERR_ARG;
   c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
-  c->om.frames = 0;
+  c->om.series.ext.cleared();
   return SWRT_OK;
 }
 
@@ -1466,86 +1265,7 @@ int swrt_omega_ideal(swrt_ctx* c, int slot, const double* ring_k, int64_t m, dou
   GUARD_END(c)
 }
 
-// ---- the map series (swrt_map.hpp) ----
-// Frames reserved by the first record: 64 MiB worth, at least one, at most 4096.
-inline int64_t map_series_min(size_t frame_bytes) {
-  return std::min<int64_t>(4096, std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / frame_bytes)));
-}
-
-// Room for `extra` more frames, as omega_reserve: growing keeps the recorded
-// frames and waits for the stream.  The frames are zeroed by the calls that
-// fill them.
-static int map_reserve(swrt_ctx* c, int64_t extra) {
-  MapSeriesState& ms = c->map;
-  if (ms.frames + extra <= ms.cap) return SWRT_OK;
-  const size_t fr = (size_t)kMapPlanes * ms.m * ms.m;
-  const int64_t ncap =
-      std::max<int64_t>({map_series_min(fr * sizeof(unsigned long long)), 2 * ms.cap, ms.frames + extra});
-  DevBuf<unsigned long long> np, ns;
-  HIPCHK(c, np.alloc(fr * ncap));
-  HIPCHK(c, ns.alloc((size_t)kMapStats * ncap));
-  if (ms.frames > 0) {
-    HIPCHK(c, hipMemcpyAsync(np.get(), ms.planes.get(), sizeof(unsigned long long) * fr * ms.frames,
-                             hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(ns.get(), ms.stats.get(), sizeof(unsigned long long) * kMapStats * ms.frames,
-                             hipMemcpyDeviceToDevice, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  hz_synced(c);
-  ms.planes = std::move(np);
-  ms.stats = std::move(ns);
-  ms.cap = ncap;
-  return SWRT_OK;
-}
-
-static MapGeom map_geom(const MapSeriesState& ms) {
-  MapGeom g;
-  g.dxm = ms.L / (double)ms.m;  // (as view_of's dx = L/nx)
-  g.inv_dxm = 1.0 / g.dxm;
-  g.pm = (double)ms.m;
-  g.inv_pm = 1.0 / g.pm;
-  g.m = ms.m;
-  g.f2 = ms.f2;
-  g.Cg2 = ms.Cg2;
-  g.scale = std::ldexp(1.0, ms.frac_bits);
-  return g;
-}
-
-// Zero `count` frames from the series' end on (planes and stats), on the stream.
-static int map_zero_frames(swrt_ctx* c, int64_t count) {
-  MapSeriesState& ms = c->map;
-  const size_t fr = (size_t)kMapPlanes * ms.m * ms.m;
-  HIPCHK(c, hipMemsetAsync(ms.planes.get() + fr * ms.frames, 0, sizeof(unsigned long long) * fr * count, c->stream));
-  HIPCHK(c, hipMemsetAsync(ms.stats.get() + (size_t)kMapStats * ms.frames, 0,
-                           sizeof(unsigned long long) * kMapStats * count, c->stream));
-  return SWRT_OK;
-}
-
-// `count` frames from the series' end on by the general kernel: frame i from
-// the packets at x + i*stride, k + i*stride (any order).
-static int map_general_launch(swrt_ctx* c, const double* x, const double* k, int64_t stride, int64_t count) {
-  MapSeriesState& ms = c->map;
-  const size_t fr = (size_t)kMapPlanes * ms.m * ms.m;
-  const int nblk = (int)std::min<int64_t>(kMapBlocks, nblocks(c->n, kMapThreads));
-  hipLaunchKernelGGL(map_general_kernel, dim3(nblk, (unsigned)count), dim3(kMapThreads), 0, c->stream, x, k, c->n,
-                     stride, map_geom(ms), ms.planes.get() + fr * ms.frames,
-                     ms.stats.get() + (size_t)kMapStats * ms.frames);
-  HIPCHK(c, hipGetLastError());
-  ms.frames += count;
-  return SWRT_OK;
-}
-
-// The tile path applies: the packets are in the order of the LDS tile kernel's
-// binning of slot 0's grid, the map covers that grid's square, and a map cell
-// is c x c field cells with c dividing the tile side.
-static bool map_tiled(const swrt_ctx* c) {
-  const MapSeriesState& ms = c->map;
-  const Slot& s = c->slot[0];
-  if (!s.set || !tile_binned(c) || c->bin.tile() != kTile) return false;
-  if (ms.L != s.L || s.nx % ms.m != 0) return false;
-  return kTile % (s.nx / ms.m) == 0;
-}
-
+// ---- the map series (swrt_map.hpp, swrt_host_diag.hpp) ----
 int swrt_map_series_begin(swrt_ctx* c, double L, int64_t m, double f, double Cg, int frac_bits) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
@@ -1555,14 +1275,8 @@ int swrt_map_series_begin(swrt_ctx* c, double L, int64_t m, double f, double Cg,
   if (c->n > kMapMaxPackets) return fail(c, SWRT_ERR_ARG, "a map frame takes at most 2^24 packets");
   HIPCHK(c, hipSetDevice(c->device));
   MapSeriesState& ms = c->map;
-  // (queued records may still write the old series: wait before releasing it)
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  hz_synced(c);
+  HIPCHK_RC(series_release(c, ms.series));
   ms.open = false;
-  ms.frames = 0;
-  ms.cap = 0;
-  ms.planes.reset();
-  ms.stats.reset();
   if (!ms.strays) {
     HIPCHK(c, ms.strays.alloc(1));
     HIPCHK(c, hipMemsetAsync(ms.strays.get(), 0, sizeof(unsigned long long), c->stream));
@@ -1578,41 +1292,14 @@ int swrt_map_series_begin(swrt_ctx* c, double L, int64_t m, double f, double Cg,
   GUARD_END(c)
 }
 
-static int map_series_check(swrt_ctx* c) {
-  if (!c->map.open) return fail(c, SWRT_ERR_STATE, "call swrt_map_series_begin first");
-  HIPCHK_RC(lost_check(c));
-  if (c->n == 0) return fail(c, SWRT_ERR_ARG, "no packets (swrt_packets_set first)");
-  if (c->n > kMapMaxPackets) return fail(c, SWRT_ERR_ARG, "a map frame takes at most 2^24 packets");
-  return SWRT_OK;
-}
-
 int swrt_map_series_record(swrt_ctx* c) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
   HIPCHK_RC(map_series_check(c));
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK_RC(map_reserve(c, 1));
-  HIPCHK_RC(map_zero_frames(c, 1));
-  MapSeriesState& ms = c->map;
+  HIPCHK_RC(map_reserve_zeroed(c, 1));
   if (!map_tiled(c)) return map_general_launch(c, c->pk.cur.x.get(), c->pk.cur.k.get(), 0, 1);
-  MapTileArgs a;
-  a.x = c->pk.cur.x.get();
-  a.k = c->pk.cur.k.get();
-  a.n = c->n;
-  a.starts = c->bins.starts();
-  a.order = c->bins.tile_order();
-  a.ntx = tiles_per_side(c->slot[0].nx);
-  a.c = (int)(c->slot[0].nx / ms.m);
-  a.g = map_geom(ms);
-  a.planes = ms.planes.get() + (size_t)kMapPlanes * ms.m * ms.m * ms.frames;
-  a.stats = ms.stats.get() + (size_t)kMapStats * ms.frames;
-  a.strays = ms.strays.get();
-  hipLaunchKernelGGL((map_tile_kernel<kTile, kMargin>), dim3((unsigned)(a.ntx * a.ntx)), dim3(kMapThreads), 0,
-                     c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  ++ms.frames;
-  ++ms.tiled_frames;
-  return SWRT_OK;
+  return map_tile_launch(c);
   GUARD_END(c)
 }
 
@@ -1620,49 +1307,34 @@ int swrt_map_series_record_history(swrt_ctx* c, int64_t first, int64_t count) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
   HIPCHK_RC(map_series_check(c));
-  if (first < 0 || count < 0 || first + count > c->hframes)
-    return fail(c, SWRT_ERR_ARG, "history frame range out of bounds");
+  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
   if (count == 0) return SWRT_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK_RC(map_reserve(c, count));
-  HIPCHK_RC(map_zero_frames(c, count));
+  HIPCHK_RC(map_reserve_zeroed(c, count));
   for (int64_t i = 0; i < count; i += kMapHistoryChunk) {
-    const int64_t nf = std::min<int64_t>(kMapHistoryChunk, count - i);
-    HIPCHK_RC(map_general_launch(c, c->hx.get() + (first + i) * 2 * c->n, c->hk.get() + (first + i) * 2 * c->n,
-                                 2 * c->n, nf));
+    const int64_t nf = std::min<int64_t>(kMapHistoryChunk, count - i), off = (first + i) * 2 * c->n;
+    HIPCHK_RC(map_general_launch(c, c->hist.a.get() + off, c->hist.b.get() + off, 2 * c->n, nf));
   }
   return SWRT_OK;
   GUARD_END(c)
 }
 
-int64_t swrt_map_series_frames(const swrt_ctx* c) { return c ? c->map.frames : -1; }
+int64_t swrt_map_series_frames(const swrt_ctx* c) { return c ? c->map.series.ext.frames() : -1; }
 
 int64_t swrt_map_series_cells(const swrt_ctx* c) { return c ? (c->map.open ? c->map.m : 0) : -1; }
 
 int swrt_map_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* planes4_out, int64_t* stats2_out) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  const MapSeriesState& ms = c->map;
-  if (first < 0 || count < 0 || first + count > ms.frames) return fail(c, SWRT_ERR_ARG, "frame range out of bounds");
-  if (count == 0) return SWRT_OK;
-  if (!planes4_out) return fail(c, SWRT_ERR_ARG, "NULL buffer");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t fr = (size_t)kMapPlanes * ms.m * ms.m;
-  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "a frame is copied out as it is");
-  HIPCHK(c, hipMemcpyAsync(planes4_out, ms.planes.get() + fr * first, sizeof(int64_t) * fr * count,
-                           hipMemcpyDeviceToHost, c->stream));
-  if (stats2_out)
-    HIPCHK(c, hipMemcpyAsync(stats2_out, ms.stats.get() + (size_t)kMapStats * first,
-                             sizeof(int64_t) * kMapStats * count, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return dev_err_check(c);
+  return series_get(c, c->map.series, c->map.frame(), kMapStats, first, count, planes4_out, stats2_out,
+                    "frame range out of bounds");
   GUARD_END(c)
 }
 
 int swrt_map_series_reset(swrt_ctx* c) {
   if (!c) return SWRT_ERR_ARG;
-  c->s0_dirty = true;  // (as swrt_omega_series_reset)
-  c->map.frames = 0;
+  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
+  c->map.series.ext.cleared();
   return SWRT_OK;
 }
 

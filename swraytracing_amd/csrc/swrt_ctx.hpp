@@ -1,10 +1,12 @@
 // swrt_ctx.hpp — the context behind the C ABI (include/swrt.h): the tuning
 // constants, each subsystem's state (the handles of swrt_res.hpp own every GPU
-// resource), swrt_ctx, the entry points' error/guard macros and the
-// cross-stream ordering helpers.  Internal to swrt_api.hip, the library's one
+// resource), swrt_ctx, the entry points' error/guard macros, the
+// cross-stream ordering helpers and the one reserve / get / release of every
+// device-side frame series.  Internal to swrt_api.hip, the library's one
 // HIP translation unit, like the swrt_host_*.hpp headers that build on it.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
@@ -18,6 +20,7 @@
 #include "swrt_qg.hpp"
 #include "swrt_spectral.hpp"
 #include "swrt_hazard.hpp"
+#include "swrt_map.hpp"
 #include "swrt_ode23_ctl.hpp"
 #include "swrt_res.hpp"
 #include "swrt_packet_state.hpp"
@@ -309,14 +312,13 @@ struct RayDiagState {
   int64_t pcap = 0;        // packets omega0 and rec are sized for
   bool marked = false;
   DevBuf<double> partial;  // kRayDiagStats x kRayDiagBlocks workgroup partials, then one frame
-  DevBuf<double> series;   // recorded frames, kRayDiagFrame doubles each
-  int64_t frames = 0;
-  int64_t cap = 0;         // frames allocated
+  Series<double> series;   // recorded frames, kRayDiagFrame doubles each (one column)
   void drop() {            // the ensemble changed size: the mark and the series describe another one
     marked = false;
-    frames = 0;
+    series.ext.cleared();
   }
 };
+constexpr int64_t kRayDiagSeriesMin = 4096;  // frames reserved by the mark or the first record (256 KiB)
 
 // the spectrum series (swrt_omega_series_*, swrt_diag.hpp).  Buffers of its
 // own, as RayDiagState's.  A frame is self-contained (its n is in its stats),
@@ -329,11 +331,10 @@ struct OmegaSeriesState {
   DevBuf<double> w;         // omega by original packet index
   int64_t pcap = 0;         // packets w is sized for
   DevBuf<double> partial;   // kOmegaHistoryChunk frames x kOmegaPartials x kOmegaBlocks
-  DevBuf<unsigned long long> counts;  // recorded rows, nb + 2 each
-  DevBuf<double> stats;     // recorded stats, kOmegaStats doubles each
-  int64_t frames = 0;
-  int64_t cap = 0;          // frames allocated
+  Series<unsigned long long, double> series;  // recorded rows, nb + 2 counts each, and their kOmegaStats stats
+  size_t row() const { return (size_t)nb + 2; }
 };
+constexpr int64_t kOmegaSeriesMin = 4096;  // frames reserved by the first record
 
 // the map series (swrt_map_series_*, swrt_map.hpp).  Buffers of its own, as
 // OmegaSeriesState's; a frame is self-contained (its n is in its stats).
@@ -342,13 +343,15 @@ struct MapSeriesState {
   int m = 0;                // cells per side of the open series
   int frac_bits = 0;
   double L = 0.0, f2 = 0.0, Cg2 = 0.0;
-  DevBuf<unsigned long long> planes;  // recorded frames, kMapPlanes x m x m each
-  DevBuf<unsigned long long> stats;   // recorded stats, kMapStats each
+  Series<unsigned long long> series;  // recorded frames, kMapPlanes x m x m each, and their kMapStats stats
+  size_t frame() const { return (size_t)kMapPlanes * m * m; }
   DevBuf<unsigned long long> strays;  // one counter: packets the tile path added through global memory
-  int64_t frames = 0;
-  int64_t cap = 0;          // frames allocated
   int64_t tiled_frames = 0; // frames recorded by the tile path (SWRT_DEBUG_MAP_TILED_FRAMES)
 };
+// Frames reserved by the first record: 64 MiB worth, at least one, at most 4096.
+inline int64_t map_series_min(size_t frame_bytes) {
+  return std::min<int64_t>(4096, std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / frame_bytes)));
+}
 
 // debug knobs (swrt_debug_set): a spin kernel queued on every extra packet
 // stream before each of its part launches (adversarial overlap of consecutive
@@ -411,11 +414,7 @@ struct swrt_ctx {
   Event jx[kMaxPacketStreams - 1];  // the extra streams' join events
   Event fork_ev;
   int b_pending = 0;              // extra streams holding packet work not yet ordered before stream's
-  // history
-  DevBuf<double> hx;
-  DevBuf<double> hk;
-  int64_t hframes = 0;
-  int64_t hcap = 0;  // doubles allocated per history buffer (frames x 2 x n)
+  Series<double> hist;  // the history: x frames and k frames, 2 x n doubles each
   int64_t steps_done = 0;  // global step counter since history reset (for save cadence)
   // scratch
   DevBuf<char> scratch;
@@ -655,7 +654,7 @@ void hz_api(swrt_ctx* c) {
   for (const void* b : std::initializer_list<const void*>{
            p0.x.get(), p0.k.get(), p0.perm.get(), p1.x.get(), p1.k.get(), p1.perm.get(), p2.x.get(), p2.k.get(),
            p2.perm.get(), c->keys.get(), c->src_idx.get(), c->bins.counts(), c->bins.cursor(), c->bins.starts(),
-           c->bins.tile_order(), c->hx.get(), c->hk.get()})
+           c->bins.tile_order(), c->hist.a.get(), c->hist.b.get()})
     (void)c->hz.access(0, t, b, kHzWrite, HzRegion::all(), "an API call");  // (a null buffer is no access)
 }
 
@@ -685,6 +684,75 @@ int dev_err_check(swrt_ctx* c) {
 int lost_check(swrt_ctx* c) {
   if (c->packets_lost)
     return fail(c, SWRT_ERR_STATE, "the packet state was lost to a corrupted binning (swrt_packets_set again)");
+  return SWRT_OK;
+}
+
+// The recorders' common check: packets that are present and not lost.
+int packets_check(swrt_ctx* c) {
+  HIPCHK_RC(lost_check(c));
+  if (c->n == 0) return fail(c, SWRT_ERR_ARG, "no packets (swrt_packets_set first)");
+  return SWRT_OK;
+}
+
+// [first, first + count) must lie inside the frames `e` has recorded.
+int frame_range_check(swrt_ctx* c, const SeriesExtent& e, int64_t first, int64_t count, const char* msg) {
+  return e.holds(first, count) ? SWRT_OK : fail(c, SWRT_ERR_ARG, msg);
+}
+
+// Room for `extra` more frames of pa (and pb) elements in s, at least
+// `minimum` frames when it has to grow.  Growing keeps the recorded frames and
+// waits for the stream: the old columns may still be written by queued work,
+// so they are released only after the wait.  The new columns are locals until
+// then: a failed allocation leaves the series as it was (b_failed: the
+// history's message for its second column, SWRT_ERR_ALLOC).
+template <typename A, typename B>
+int series_reserve(swrt_ctx* c, Series<A, B>& s, size_t pa, size_t pb, int64_t extra, int64_t minimum,
+                   const char* b_failed = nullptr) {
+  if (s.ext.fits(extra, (int64_t)pa)) return SWRT_OK;
+  const int64_t ncap = s.ext.grown(extra, (int64_t)pa, minimum);
+  DevBuf<A> na;
+  DevBuf<B> nb;
+  HIPCHK(c, na.alloc(pa * ncap));
+  if (pb && b_failed) {
+    if (nb.alloc(pb * ncap) != hipSuccess) return fail(c, SWRT_ERR_ALLOC, b_failed);
+  } else if (pb) {
+    HIPCHK(c, nb.alloc(pb * ncap));
+  }
+  if (const size_t done = (size_t)s.ext.frames()) {
+    HIPCHK(c, hipMemcpyAsync(na.get(), s.a.get(), sizeof(A) * pa * done, hipMemcpyDeviceToDevice, c->stream));
+    if (pb) HIPCHK(c, hipMemcpyAsync(nb.get(), s.b.get(), sizeof(B) * pb * done, hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  hz_synced(c);
+  s.a = std::move(na);
+  s.b = std::move(nb);
+  s.ext.reserved(ncap, (int64_t)pa);
+  return SWRT_OK;
+}
+
+// Frames [first, first + count) of s to the host, synchronously; out_b may be NULL.
+template <typename A, typename B>
+int series_get(swrt_ctx* c, const Series<A, B>& s, size_t pa, size_t pb, int64_t first, int64_t count, void* out_a,
+               void* out_b, const char* range_msg) {
+  HIPCHK_RC(frame_range_check(c, s.ext, first, count, range_msg));
+  if (count == 0) return SWRT_OK;
+  if (!out_a) return fail(c, SWRT_ERR_ARG, "NULL buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(out_a, s.a.get() + pa * first, sizeof(A) * pa * count, hipMemcpyDeviceToHost, c->stream));
+  if (out_b)
+    HIPCHK(c, hipMemcpyAsync(out_b, s.b.get() + pb * first, sizeof(B) * pb * count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return dev_err_check(c);
+}
+
+// Drop s and its buffers (queued records may still write them: wait first).
+template <typename A, typename B>
+int series_release(swrt_ctx* c, Series<A, B>& s) {
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  hz_synced(c);
+  s.a.reset();
+  s.b.reset();
+  s.ext.released();
   return SWRT_OK;
 }
 

@@ -1,0 +1,229 @@
+// swrt_host_diag.hpp — host side of the three device-side recorders: the ray
+// diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp) and the
+// map series (swrt_map.hpp).  Each appends frames to a Series of its state
+// (swrt_ctx.hpp) without a host wait: a reserve, the launches that write at the
+// series' end, a commit.  The order below (ray, spectrum, map) is the order
+// their template kernels are first named in, hence emitted in.
+#pragma once
+#include <cmath>
+
+#include "swrt_ctx.hpp"
+#include "swrt_host_fields.hpp"
+#include "swrt_host_packets.hpp"
+#include "swrt_diag.hpp"
+#include "swrt_raydiag.hpp"
+#include "swrt_map.hpp"
+
+namespace {
+
+// ---- ray diagnostics ----
+// The three calls' common checks: SWRT_ERR_ARG with a message, as the header says.
+int raydiag_check(swrt_ctx* c, int nslots) {
+  HIPCHK_RC(lost_check(c));
+  if (nslots != 1 && nslots != 2) return fail(c, SWRT_ERR_ARG, "nslots must be 1 or 2");
+  for (int s = 0; s < nslots; ++s)
+    if (!c->slot[s].set) return fail(c, SWRT_ERR_ARG, "field slot not set");
+  if (nslots == 2 && (c->slot[1].nx != c->slot[0].nx || c->slot[1].L != c->slot[0].L ||
+                      c->slot[1].ny_period != c->slot[0].ny_period))
+    return fail(c, SWRT_ERR_ARG, "slots 0 and 1 have different grids");
+  return packets_check(c);
+}
+
+// The per-packet buffers for the current ensemble and room for `extra` more frames.
+int raydiag_reserve(swrt_ctx* c, int64_t extra) {
+  RayDiagState& rd = c->rd;
+  if (!rd.partial) HIPCHK(c, rd.partial.alloc(kRayDiagStats * kRayDiagBlocks + kRayDiagFrame));
+  if (c->n > rd.pcap) {  // (a larger ensemble: swrt_packets_set dropped the mark; releasing waits for queued readers)
+    rd.pcap = 0;
+    rd.marked = false;
+    HIPCHK(c, rd.omega0.alloc(c->n));
+    HIPCHK(c, rd.rec.alloc(kRayDiagRec * c->n));
+    rd.pcap = c->n;
+  }
+  return series_reserve(c, rd.series, kRayDiagFrame, 0, extra, kRayDiagSeriesMin);
+}
+
+// One pass over the packets on the context's stream: the mark, or a sample
+// (then the reduction over its records) whose frame goes to `frame` (device)
+// and whose N x 4 values go to `sample4` (device, may be NULL).
+int raydiag_launch(swrt_ctx* c, bool mark, double f, double gH, int nslots, double alpha, double bump, double* sample4,
+                   double* frame, const double* hist_x = nullptr, const double* hist_k = nullptr) {
+  RayDiagState& rd = c->rd;
+  RayDiagArgs a;
+  a.f0 = view_of(c->slot[0]);
+  a.f1 = nslots == 2 ? view_of(c->slot[1]) : a.f0;
+  a.nslots = nslots;
+  a.alpha = alpha;
+  a.bump = bump;
+  a.x = c->pk.cur.x.get();
+  a.k = c->pk.cur.k.get();
+  a.perm = c->pk.cur.perm.get();
+  if (hist_x) {  // a history frame: the same layout in the original packet order
+    a.x = hist_x;
+    a.k = hist_k;
+    a.perm = nullptr;
+  }
+  a.n = c->n;
+  a.f2 = f * f;
+  a.gH = gH;
+  a.omega0 = (mark || rd.marked) ? rd.omega0.get() : nullptr;
+  a.sample4 = sample4;
+  a.rec = rd.rec.get();
+  const dim3 grid(nblocks(c->n, kRayDiagThreads)), block(kRayDiagThreads);
+  hipLaunchKernelGGL(mark ? ray_diag_kernel<true> : ray_diag_kernel<false>, grid, block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  if (mark) return SWRT_OK;
+  const int nblk = (int)std::min<int64_t>(kRayDiagBlocks, grid.x);
+  hipLaunchKernelGGL(ray_diag_reduce_kernel, dim3(nblk), block, 0, c->stream, rd.rec.get(), c->n, rd.partial.get());
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(ray_diag_frame_kernel, dim3(1), dim3(64), 0, c->stream, rd.partial.get(), nblk, c->n, frame);
+  HIPCHK(c, hipGetLastError());
+  return SWRT_OK;
+}
+
+// One more frame of the series: from the packets, or from a history frame.
+int raydiag_record_frame(swrt_ctx* c, double f, double gH, int nslots, double alpha, double bump,
+                         const double* hist_x = nullptr, const double* hist_k = nullptr) {
+  HIPCHK_RC(raydiag_launch(c, false, f, gH, nslots, alpha, bump, nullptr, c->rd.series.end_a(kRayDiagFrame), hist_x,
+                           hist_k));
+  c->rd.series.ext.committed(1);
+  return SWRT_OK;
+}
+
+// ---- the spectrum series ----
+// swrt_omega_histogram's checks on the edges, finite as well.
+int omega_edges_check(swrt_ctx* c, const double* edges, int64_t nbins) {
+  if (nbins <= 0 || nbins > kMaxHistBins) return fail(c, SWRT_ERR_ARG, "nbins must be 1..4096");
+  if (!edges) return fail(c, SWRT_ERR_ARG, "NULL buffer");
+  for (int64_t i = 0; i <= nbins; ++i)
+    if (!std::isfinite(edges[i])) return fail(c, SWRT_ERR_ARG, "edges must be finite");
+  for (int64_t i = 0; i < nbins; ++i)
+    if (!(edges[i] < edges[i + 1])) return fail(c, SWRT_ERR_ARG, "edges must increase");
+  return SWRT_OK;
+}
+
+inline size_t omega_lds_bytes(int nb) { return sizeof(double) * (nb + 1) + sizeof(unsigned int) * (nb + 2); }
+
+int omega_series_check(swrt_ctx* c) {
+  if (!c->om.open) return fail(c, SWRT_ERR_STATE, "call swrt_omega_series_begin first");
+  return packets_check(c);
+}
+
+// omega's per-packet buffer for the current ensemble and room for `extra` more
+// frames.  The rows are zeroed by the launches that fill them.
+int omega_reserve(swrt_ctx* c, int64_t extra, bool need_w) {
+  OmegaSeriesState& om = c->om;
+  if (!om.partial) HIPCHK(c, om.partial.alloc((size_t)kOmegaHistoryChunk * kOmegaPartials * kOmegaBlocks));
+  if (need_w && c->n > om.pcap) {  // (releasing the old buffer waits for queued readers)
+    om.pcap = 0;
+    HIPCHK(c, om.w.alloc(c->n));
+    om.pcap = c->n;
+  }
+  return series_reserve(c, om.series, om.row(), kOmegaStats, extra, kOmegaSeriesMin);
+}
+
+// `count` frames from the series' end on: omega_frame_kernel over src (omega
+// by original index, or the k of consecutive history frames), then their stats.
+int omega_frames_launch(swrt_ctx* c, bool from_k, const double* src, int64_t src_stride, int64_t count) {
+  OmegaSeriesState& om = c->om;
+  OmegaFrameArgs a;
+  a.src = src;
+  a.src_stride = src_stride;
+  a.n = c->n;
+  a.f2 = om.f2;
+  a.Cg2 = om.Cg2;
+  a.edges = om.edges.get();
+  a.nb = om.nb;
+  a.counts = om.series.end_a(om.row());
+  a.partial = om.partial.get();
+  const int nblk = (int)std::min<int64_t>(kOmegaBlocks, nblocks(c->n, kOmegaThreads));
+  const dim3 grid(nblk, (unsigned)count), block(kOmegaThreads);
+  hipLaunchKernelGGL(from_k ? omega_frame_kernel<true> : omega_frame_kernel<false>, grid, block,
+                     omega_lds_bytes(om.nb), c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(omega_stats_kernel, dim3((unsigned)count), dim3(kOmegaThreads), 0, c->stream, om.partial.get(), nblk, c->n,
+                     om.series.end_b(kOmegaStats));
+  HIPCHK(c, hipGetLastError());
+  om.series.ext.committed(count);
+  return SWRT_OK;
+}
+
+// ---- the map series ----
+int map_series_check(swrt_ctx* c) {
+  if (!c->map.open) return fail(c, SWRT_ERR_STATE, "call swrt_map_series_begin first");
+  HIPCHK_RC(packets_check(c));
+  if (c->n > kMapMaxPackets) return fail(c, SWRT_ERR_ARG, "a map frame takes at most 2^24 packets");
+  return SWRT_OK;
+}
+
+// Room for `count` more frames, zeroed on the stream (planes and stats): the
+// launches that fill them only add.
+int map_reserve_zeroed(swrt_ctx* c, int64_t count) {
+  MapSeriesState& ms = c->map;
+  const size_t fr = ms.frame();
+  HIPCHK_RC(series_reserve(c, ms.series, fr, kMapStats, count, map_series_min(fr * sizeof(unsigned long long))));
+  HIPCHK(c, hipMemsetAsync(ms.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
+  HIPCHK(c, hipMemsetAsync(ms.series.end_b(kMapStats), 0, sizeof(unsigned long long) * kMapStats * count, c->stream));
+  return SWRT_OK;
+}
+
+MapGeom map_geom(const MapSeriesState& ms) {
+  MapGeom g;
+  g.dxm = ms.L / (double)ms.m;  // (as view_of's dx = L/nx)
+  g.inv_dxm = 1.0 / g.dxm;
+  g.pm = (double)ms.m;
+  g.inv_pm = 1.0 / g.pm;
+  g.m = ms.m;
+  g.f2 = ms.f2;
+  g.Cg2 = ms.Cg2;
+  g.scale = std::ldexp(1.0, ms.frac_bits);
+  return g;
+}
+
+// `count` frames from the series' end on by the general kernel: frame i from
+// the packets at x + i*stride, k + i*stride (any order).
+int map_general_launch(swrt_ctx* c, const double* x, const double* k, int64_t stride, int64_t count) {
+  MapSeriesState& ms = c->map;
+  const int nblk = (int)std::min<int64_t>(kMapBlocks, nblocks(c->n, kMapThreads));
+  hipLaunchKernelGGL(map_general_kernel, dim3(nblk, (unsigned)count), dim3(kMapThreads), 0, c->stream, x, k, c->n,
+                     stride, map_geom(ms), ms.series.end_a(ms.frame()), ms.series.end_b(kMapStats));
+  HIPCHK(c, hipGetLastError());
+  ms.series.ext.committed(count);
+  return SWRT_OK;
+}
+
+// The tile path applies: the packets are in the order of the LDS tile kernel's
+// binning of slot 0's grid, the map covers that grid's square, and a map cell
+// is c x c field cells with c dividing the tile side.
+bool map_tiled(const swrt_ctx* c) {
+  const MapSeriesState& ms = c->map;
+  const Slot& s = c->slot[0];
+  if (!s.set || !tile_binned(c) || c->bin.tile() != kTile) return false;
+  if (ms.L != s.L || s.nx % ms.m != 0) return false;
+  return kTile % (s.nx / ms.m) == 0;
+}
+
+// One frame at the series' end from the binned packets, a workgroup per tile.
+int map_tile_launch(swrt_ctx* c) {
+  MapSeriesState& ms = c->map;
+  MapTileArgs a;
+  a.x = c->pk.cur.x.get();
+  a.k = c->pk.cur.k.get();
+  a.n = c->n;
+  a.starts = c->bins.starts();
+  a.order = c->bins.tile_order();
+  a.ntx = tiles_per_side(c->slot[0].nx);
+  a.c = (int)(c->slot[0].nx / ms.m);
+  a.g = map_geom(ms);
+  a.planes = ms.series.end_a(ms.frame());
+  a.stats = ms.series.end_b(kMapStats);
+  a.strays = ms.strays.get();
+  hipLaunchKernelGGL((map_tile_kernel<kTile, kMargin>), dim3((unsigned)(a.ntx * a.ntx)), dim3(kMapThreads), 0,
+                     c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  ms.series.ext.committed(1);
+  ++ms.tiled_frames;
+  return SWRT_OK;
+}
+
+}  // namespace

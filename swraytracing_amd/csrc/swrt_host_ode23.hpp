@@ -694,7 +694,7 @@ int ode23_attempt(swrt_ctx* c, double t, double h, double tnew, double tmax, dou
 int ode23_ntrp_queue(swrt_ctx* c, double t, double tnew, const double* tout, int64_t nout) {
   if (nout <= 0) return SWRT_OK;
   const int64_t n = c->n;
-  if ((c->hframes + nout) * 2 * n > c->hcap) return fail(c, SWRT_ERR_STATE, "ode23 ntrp: history capacity not reserved");
+  if (!c->hist.ext.fits(nout, 2 * n)) return fail(c, SWRT_ERR_STATE, "ode23 ntrp: history capacity not reserved");
   const double h = tnew - t;
   NtrpArgs a;
   a.yx = c->pk.cur.x.get();
@@ -720,11 +720,11 @@ int ode23_ntrp_queue(swrt_ctx* c, double t, double tnew, const double* tout, int
       a.s2[j] = s2;
       a.s3[j] = s2 * s;
     }
-    a.hx = c->hx.get() + c->hframes * 2 * n;
-    a.hk = c->hk.get() + c->hframes * 2 * n;
+    a.hx = c->hist.end_a(2 * n);
+    a.hk = c->hist.end_b(2 * n);
     hipLaunchKernelGGL(ode23_ntrp_kernel, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
-    c->hframes += a.nf;
+    c->hist.ext.committed(a.nf);
   }
   return SWRT_OK;
 }

@@ -408,9 +408,9 @@ StepArgs step_args(swrt_ctx* c, const FieldView& f0, const FieldView& f1, int ns
   a.dalpha = dalpha;
   a.bump = bump;
   a.save_every = save_every > 0 ? save_every : 1;
-  a.hist_x = save_every > 0 ? c->hx.get() : nullptr;
-  a.hist_k = save_every > 0 ? c->hk.get() : nullptr;
-  a.frame0 = c->hframes;
+  a.hist_x = save_every > 0 ? c->hist.a.get() : nullptr;
+  a.hist_k = save_every > 0 ? c->hist.b.get() : nullptr;
+  a.frame0 = c->hist.ext.frames();
   return a;
 }
 
@@ -463,7 +463,7 @@ int run_advance_intervals(swrt_ctx* c, int nint, const double* hs, int64_t nsub,
     }
     if (k < 1) {  // one interval on its own (it may straddle a re-binning)
       HIPCHK_RC(run_advance(c, hs[i0], nsub, f, gH, 2, alpha0, dalpha, bump, save_every, i0));
-      c->hframes += fpi;
+      c->hist.ext.committed(fpi);
       i0 += 1;
       continue;
     }
@@ -477,44 +477,27 @@ int run_advance_intervals(swrt_ctx* c, int nint, const double* hs, int64_t nsub,
     for (int i = 0; i < k; ++i) iv.dts[i] = hs[i0 + i];
     StepArgs a = step_args(c, iv.views[0], iv.views[1], 2, hs[i0], f, gH, alpha0, dalpha, bump, save_every);
     HIPCHK_RC(advance_launch(c, a, 0, nsub, k * nsub, &iv));
-    c->hframes += k * fpi;
+    c->hist.ext.committed(k * fpi);
     i0 += k;
   }
   return SWRT_OK;
 }
 
-// grow the history frames (keeps the existing ones).  The capacity is kept in
-// doubles, not frames: a frame is 2 x n doubles and n changes with every
-// swrt_packets_set, so a frame count sized for a smaller ensemble must not
-// pass the check.
+// Room for new_frames more history frames of the current ensemble (2 x n
+// doubles in each column; SeriesExtent keeps the capacity right when n changes).
 int ensure_history(swrt_ctx* c, int64_t new_frames) {
   const int64_t per = 2 * c->n;
-  const int64_t need = (c->hframes + new_frames) * per;
-  if (new_frames <= 0 || need <= c->hcap) return SWRT_OK;
+  if (c->hist.ext.fits(new_frames, per)) return SWRT_OK;
   if (int rc = join_b(c)) return rc;  // the second stream may still write frames into the old buffers
   c->s0_dirty = true;
-  const int64_t ncap = std::max<int64_t>(need, 2 * c->hcap);
-  DevBuf<double> nx_, nk_;
-  HIPCHK(c, nx_.alloc(ncap));
-  if (nk_.alloc(ncap) != hipSuccess) return fail(c, SWRT_ERR_ALLOC, "history allocation failed");
-  if (c->hframes > 0) {
-    HIPCHK(c, hipMemcpyAsync(nx_.get(), c->hx.get(), sizeof(double) * per * c->hframes, hipMemcpyDeviceToDevice,
-                             c->stream));
-    HIPCHK(c, hipMemcpyAsync(nk_.get(), c->hk.get(), sizeof(double) * per * c->hframes, hipMemcpyDeviceToDevice,
-                             c->stream));
-  }
-  // the old buffers may still be read or written by queued work
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  hz_synced(c);
+  const double *old_x = c->hist.a.get(), *old_k = c->hist.b.get();
+  HIPCHK_RC(series_reserve(c, c->hist, per, per, new_frames, 0, "history allocation failed"));
   if (c->hz.on) {
-    c->hz.bufs.erase(c->hx.get());
-    c->hz.bufs.erase(c->hk.get());
-    c->hz.name(nx_.get(), "history x frames");
-    c->hz.name(nk_.get(), "history k frames");
+    c->hz.bufs.erase(old_x);
+    c->hz.bufs.erase(old_k);
+    c->hz.name(c->hist.a.get(), "history x frames");
+    c->hz.name(c->hist.b.get(), "history k frames");
   }
-  c->hx = std::move(nx_);  // (the old buffers are released here)
-  c->hk = std::move(nk_);
-  c->hcap = ncap;
   return SWRT_OK;
 }
 

@@ -3,6 +3,7 @@
 // device's binning (Binning).  Plain host code, no HIP type: the library uses
 // it in swrt_ctx, the CPU model tests/hazard_model.cpp on its own.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <utility>
 
@@ -84,6 +85,33 @@ class Binning {
   int nbins_ = 0, tile_ = 0, lanes_ = 0, o23_since_ = 0;
   int64_t steps_ = 0, key_nx_ = 0;
   double key_dx_ = 0.0;
+};
+
+// How far a series of fixed-size frames in a growable buffer has got: the
+// frames recorded and the capacity allocated.  The capacity is kept in words,
+// not frames, and asked for in frames of the caller's current size `per`: the
+// history's frame is 2 x n words and n changes with every swrt_packets_set, so
+// a frame count reserved for a smaller frame must not pass the check.
+class SeriesExtent {
+ public:
+  int64_t frames() const { return frames_; }
+  int64_t capacity(int64_t per) const { return per > 0 ? words_ / per : 0; }  // in frames of `per` words
+  // `extra` more frames of `per` words fit (nothing more always does)
+  bool fits(int64_t extra, int64_t per) const { return extra <= 0 || frames_ + extra <= capacity(per); }
+  // the capacity, in frames, to grow to when they do not: at least `minimum`
+  int64_t grown(int64_t extra, int64_t per, int64_t minimum) const {
+    return std::max<int64_t>({minimum, 2 * capacity(per), frames_ + extra});
+  }
+  // [first, first + count) lies inside the recorded frames
+  bool holds(int64_t first, int64_t count) const { return !(first < 0 || count < 0 || first + count > frames_); }
+
+  void reserved(int64_t cap, int64_t per) { words_ = cap * per; }  // buffers for `cap` frames of `per` words are in place
+  void committed(int64_t count) { frames_ += count; }              // `count` more frames were queued
+  void cleared() { frames_ = 0; }                                  // the series starts again in the same buffers
+  void released() { frames_ = words_ = 0; }                        // the buffers are gone
+
+ private:
+  int64_t frames_ = 0, words_ = 0;
 };
 
 }  // namespace swrt

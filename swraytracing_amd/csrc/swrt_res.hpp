@@ -5,11 +5,14 @@
 // hipEventDestroy and hipStreamDestroy calls.  alloc() / create() release the
 // old resource first and return the HIP status; get() is the raw handle for
 // kernel arguments and HIP calls.  std::swap and moves transfer ownership.
+// Series groups one or two DevBufs of recorded frames with their counting.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <utility>
+
+#include "swrt_packet_state.hpp"
 
 namespace swrt {
 
@@ -91,6 +94,21 @@ struct Stream : Owned<hipStream_t, hipStreamDestroy> {
     reset();
     return held(hipStreamCreateWithPriority(&h_, flags, priority));
   }
+};
+
+// A series of frames recorded on the device: one or two columns, a frame being
+// `per` elements of an 8-byte type in each, and how far it has got.  The
+// context's series_reserve / series_get / series_release (swrt_ctx.hpp) grow,
+// read and drop it; the recorders write at end_a / end_b and commit to ext.
+template <typename A, typename B = A>
+struct Series {
+  static_assert(sizeof(A) == 8 && sizeof(B) == 8, "frames are counted in 8-byte words and copied out as they are");
+  DevBuf<A> a;
+  DevBuf<B> b;  // (null in a series of one column)
+  SeriesExtent ext;
+  // the first unrecorded frame of a column whose frames are `per` elements
+  A* end_a(size_t per) const { return a.get() + per * ext.frames(); }
+  B* end_b(size_t per) const { return b.get() + per * ext.frames(); }
 };
 
 }  // namespace swrt

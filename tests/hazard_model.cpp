@@ -6,8 +6,9 @@
 // each part (swrt_share.hpp share_slot, the same function the kernels run)
 // — and prints one line per scenario: "<name> ok" when the checker's verdict
 // is the expected one.  The rotation of the three packet sets is the library's
-// own (swrt_packet_state.hpp SetRing), and a last block drives its Binning
-// through the transitions the library makes.  Built (hipcc, host code only) and run by
+// own (swrt_packet_state.hpp SetRing), and the last blocks drive its Binning
+// and its SeriesExtent (the frame series' counting) through the transitions
+// the library makes.  Built (hipcc, host code only) and run by
 // tests/test_hazard_model.py; no GPU.
 #include <cstdio>
 #include <string>
@@ -222,6 +223,35 @@ int main() {
     r.park_cur();
     ok = ok && r.cur == 0 && r.out == 2 && r.park == 1;
     expect("set_ring_rotations", ok, true);
+  }
+  {  // SeriesExtent: frames of 8 words, a minimum of 4096 frames
+    const int64_t per = 8, minimum = 4096;
+    SeriesExtent e;
+    expect("series_empty_does_not_fit", e.fits(1, per), false);
+    expect("series_growth_from_empty_takes_minimum", e.grown(1, per, minimum) == minimum, true);
+    e.reserved(minimum, per);
+    expect("series_fits_up_to_capacity", e.fits(minimum, per) && !e.fits(minimum + 1, per), true);
+    e.committed(minimum);
+    expect("series_growth_doubles", !e.fits(1, per) && e.grown(1, per, minimum) == 2 * minimum, true);
+    expect("series_growth_takes_needed", e.grown(3 * minimum, per, minimum) == 4 * minimum, true);
+    SeriesExtent none;  // (no capacity at all, nor a minimum: the history)
+    expect("series_extra_zero_never_grows", e.fits(0, per) && none.fits(0, per) && none.fits(0, 0), true);
+    expect("series_no_minimum_takes_needed", none.grown(3, per, 0) == 3, true);
+    expect("series_range_inside", e.holds(0, minimum) && e.holds(minimum, 0) && e.holds(minimum - 1, 1), true);
+    expect("series_range_past_end", e.holds(0, minimum + 1) || e.holds(minimum, 1) || e.holds(minimum + 1, 0), false);
+    expect("series_range_negative", e.holds(-1, 1) || e.holds(0, -1) || e.holds(-1, 0), false);
+    e.cleared();
+    expect("series_cleared_keeps_capacity", e.frames() == 0 && e.capacity(per) == minimum && e.fits(minimum, per), true);
+    expect("series_cleared_holds_nothing", e.holds(0, 0) && !e.holds(0, 1), true);
+    e.released();
+    expect("series_released_drops_capacity", e.frames() == 0 && e.capacity(per) == 0 && !e.fits(1, per), true);
+    // the history rule: 10 frames reserved for 512 packets (2 x 512 words a
+    // frame) do not admit 10 frames of 4096 packets, only the one that fits
+    SeriesExtent h;
+    h.reserved(10, 2 * 512);
+    expect("series_history_smaller_frame_does_not_pass",
+           h.fits(10, 2 * 512) && !h.fits(10, 2 * 4096) && h.fits(1, 2 * 4096) && !h.fits(2, 2 * 4096), true);
+    expect("series_history_growth_for_larger_frame", h.grown(10, 2 * 4096, 0) == 10, true);
   }
   std::printf("%s\n", fails ? "FAILED" : "ALL OK");
   return fails ? 1 : 0;

@@ -199,6 +199,48 @@ def test_series_matches_synchronous_samples(fresh_ctx):
         b.close()
 
 
+def test_series_grows_and_resets(fresh_ctx):
+    """4,100 frames: past the 4,096 the first record reserves, so the series
+    grows once with frames recorded.  Frames 0..4090 are of the packets 10 steps
+    after the mark, the rest of the packets at the mark again (the same N keeps
+    the mark and the series): each equals raydiag_sample's frame of that state."""
+    c = fresh_ctx
+    _set_fields(c, 2)
+    phys = dict(nslots=2, alpha=0.3, bump=BUMP)
+    xa, ka = _packets(37, seed=23)
+    c.packets_set(xa, ka)
+    c.raydiag_mark(F, GH, **phys)
+    c.advance(DT, 10, F, GH, nslots=2, alpha0=0.3, dalpha=0.0, bump=BUMP)
+    moved = c.raydiag_sample(F, GH, values=False, **phys)[1]
+    for i in range(4100):
+        if i == 4091:
+            c.packets_set(xa, ka)
+            at_mark = c.raydiag_sample(F, GH, values=False, **phys)[1]
+        c.raydiag_record(F, GH, **phys)
+    assert c.raydiag_frames() == 4100
+    assert moved[0] == 37 and moved[1] > 0 and at_mark[0] == 37 and at_mark[1] == 0.0  # the two states differ
+    ser = c.raydiag_series()
+    assert ser.shape == (4100, 8)
+    for i, want in ((0, moved), (4090, moved), (4091, at_mark), (4095, at_mark), (4096, at_mark), (4099, at_mark)):
+        assert ser[i].tobytes() == want.tobytes(), f"frame {i}"
+    assert (ser[:4091] == ser[0]).all() and (ser[4091:] == ser[4099]).all()
+    np.testing.assert_array_equal(c.raydiag_series(4095, 3), ser[4095:4098])
+    # a reset keeps the mark (and the buffers): one record, one frame, r measured against the old mark
+    c.raydiag_series_reset()
+    assert c.raydiag_frames() == 0 and c.raydiag_series().shape == (0, 8)
+    c.advance(DT, 10, F, GH, nslots=2, alpha0=0.3, dalpha=0.0, bump=BUMP)
+    c.raydiag_record(F, GH, **phys)
+    one = c.raydiag_series()
+    assert one.shape == (1, 8) and one[0, 1] > 0
+    assert one[0].tobytes() == c.raydiag_sample(F, GH, values=False, **phys)[1].tobytes()
+    # another N empties the series and drops the mark
+    xb, kb = _packets(41, seed=24)
+    c.packets_set(xb, kb)
+    assert c.raydiag_frames() == 0 and c.raydiag_series().shape == (0, 8)
+    fr = c.raydiag_sample(F, GH, values=False, **phys)[1]
+    assert fr[0] == 41 and fr[1] == 0.0 and fr[2] == 0.0 and fr[3] == 0.0
+
+
 def test_advance_unaffected_and_ordered_after_split_launches(fresh_ctx, flows):
     """70,001 packets: above the size from which a tile launch runs as two part
     launches on two streams.  Marks and records between the advance calls leave

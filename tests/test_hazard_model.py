@@ -33,3 +33,11 @@ def test_hazard_checker_model(tmp_path):
                  "binning_memset_skip_survives_invalidate", "binning_invalidate_as_constructed",
                  "binning_cadence", "binning_due_after_cycle"):
         assert name + " ok" in r.stdout, r.stdout
+    # the frame series' counting (SeriesExtent): growth, the range query, clear / release, the history rule
+    for name in ("series_empty_does_not_fit", "series_growth_from_empty_takes_minimum", "series_fits_up_to_capacity",
+                 "series_growth_doubles", "series_growth_takes_needed", "series_extra_zero_never_grows",
+                 "series_no_minimum_takes_needed", "series_range_inside", "series_range_past_end",
+                 "series_range_negative", "series_cleared_keeps_capacity", "series_cleared_holds_nothing",
+                 "series_released_drops_capacity", "series_history_smaller_frame_does_not_pass",
+                 "series_history_growth_for_larger_frame"):
+        assert name + " ok" in r.stdout, r.stdout
