@@ -423,6 +423,59 @@ int swrt_map_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* pl
 /* Empty the series; L, m, f, Cg and frac_bits stay. */
 int swrt_map_series_reset(swrt_ctx* ctx);
 
+/* The trajectories of a chosen few packets, kept on the device: what
+ * images/QG_spread*.png, the (k, l) paths of raytracing_figures.m:76-83 and
+ * the Omega time series draw per packet, and analysis/load_data.m:29-33 reads
+ * as packet_x.bin / packet_k.bin, for m packets out of an ensemble too large
+ * to download every frame.  A frame is m x 8 doubles, column-major: row j is
+ * packet ids[j], in the order the ids were given, the columns
+ *   [x, y, k, l, Omega, zeta, sigma, D].
+ * x, y, k, l are the bits swrt_packets_get returns for that packet (positions
+ * unwrapped).  Omega, zeta, sigma and D are the bits swrt_raydiag_sample's
+ * sample4_out holds for it with the same (f, gH, nslots, alpha, bump): the
+ * formulas and operation order of the ray-diagnostics section below, through
+ * the same device code.  With nslots == 0 no flow is read and columns 4..7
+ * hold the quiet NaN 0x7ff8000000000000. */
+
+/* Name the packets to track by their original index: 1 <= m <= N, m <= 2^20,
+ * 0 <= ids[j] < N, all distinct, ids not NULL, packets set (SWRT_ERR_ARG with
+ * a message otherwise).  Empties the series and writes the N-entry device
+ * table the records look the ids up in; waits for the stream.
+ * swrt_packets_set with a different N closes the series (the ids name packets
+ * of the old ensemble); the same N keeps it. */
+int swrt_track_begin(swrt_ctx* ctx, const int64_t* ids, int64_t m);
+
+/* Append the frame of the current state: queued on the packet stream after
+ * whatever last wrote the packets (both packet streams, the ode23 attempts, a
+ * re-binning's parked set) and after the snapshot writes of the slots it
+ * reads; the host does not wait.  nslots is 0, 1 or 2; with 1 or 2 the checks
+ * of swrt_raydiag_record apply.  One lane per stored packet finds the tracked
+ * ones through the table: 8 bytes read per packet, then m gathers.  Capacity:
+ * 64 MiB of frames (at least one, at most 4096), doubled when full; only a
+ * growing call may wait for the stream, and a failed allocation is an error
+ * return.  SWRT_ERR_STATE before swrt_track_begin. */
+int swrt_track_record(swrt_ctx* ctx, double f, double gH, int nslots, double alpha, double bump);
+
+/* One frame per history frame in [first, first + count), frame i with the
+ * snapshot blend alphas[i] (alphas may be NULL when nslots < 2): the same
+ * bits as swrt_track_record on packets set to that frame.  A range out of
+ * bounds: SWRT_ERR_ARG. */
+int swrt_track_record_history(swrt_ctx* ctx, int64_t first, int64_t count, double f, double gH, int nslots,
+                              const double* alphas, double bump);
+
+/* Frames recorded since begin or the last reset; m of the open series, 0 if
+ * none; its ids into ids_out (m values; SWRT_ERR_STATE if none is open). */
+int64_t swrt_track_frames(const swrt_ctx* ctx);
+int64_t swrt_track_count(const swrt_ctx* ctx);
+int swrt_track_ids(const swrt_ctx* ctx, int64_t* ids_out);
+
+/* Frames [first, first + count) into frames_out: count x 8 x m, frame-major
+ * (each frame m x 8 column-major).  Waits for them. */
+int swrt_track_get(swrt_ctx* ctx, int64_t first, int64_t count, double* frames_out);
+
+/* Empty the series; the ids stay. */
+int swrt_track_reset(swrt_ctx* ctx);
+
 /* ---------------------------------------------------------------------------
  * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
  * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)

@@ -88,5 +88,38 @@ classdef SwrtContext < handle
         function map_series_reset(obj)
             swrt_mex('map_series_reset', obj.id());
         end
+
+        % The trajectories of chosen packets on the device (what
+        % raytracing_figures.m:76-83 and load_data.m:29-33 take per packet,
+        % for m of an ensemble too large to download): a frame is m x 8,
+        % row j packet ids(j), columns [x y k l Omega zeta sigma D].
+        function track_begin(obj, ids)
+            % ids: original packet indices, 0-based as in the C ABI, distinct
+            swrt_mex('track_begin', obj.id(), double(ids));
+        end
+
+        function track_record(obj, f, gH, nslots, alpha, bump)
+            % nslots 0: no flow is read, columns 5..8 are NaN
+            if nargin < 4, nslots = 1; end
+            if nargin < 5, alpha = 0; end
+            if nargin < 6, bump = 1e-13; end
+            swrt_mex('track_record', obj.id(), f, gH, nslots, alpha, bump);
+        end
+
+        function track_record_history(obj, first, count, f, gH, nslots, alphas, bump)
+            % history frames first .. first+count-1, 0-based; alphas: one per frame, [] when nslots < 2
+            if nargin < 7, alphas = []; end
+            if nargin < 8, bump = 1e-13; end
+            swrt_mex('track_record_history', obj.id(), first, count, f, gH, nslots, alphas, bump);
+        end
+
+        function frames = track_get(obj)
+            % frames: m x 8 x frames
+            frames = swrt_mex('track_get', obj.id());
+        end
+
+        function track_reset(obj)
+            swrt_mex('track_reset', obj.id());
+        end
     end
 end

@@ -50,6 +50,11 @@
 //   swrt_mex('map_series_record', h);  swrt_mex('map_series_record_history', h, first, count)
 //   [planes, stats] = swrt_mex('map_series_get', h)           % m x m x 4 x frames, 2 x frames
 //   swrt_mex('map_series_reset', h)
+//   swrt_mex('track_begin', h, ids)                           % trajectories of chosen packets; ids 0-based doubles
+//   swrt_mex('track_record', h, f, gH, nslots, alpha, bump)   % nslots 0: no flow, Omega..D are NaN
+//   swrt_mex('track_record_history', h, first, count, f, gH, nslots, alphas, bump)   % alphas [] when nslots < 2
+//   frames = swrt_mex('track_get', h)                         % m x 8 x frames [x y k l Omega zeta sigma D]
+//   swrt_mex('track_reset', h)
 #include <cstring>
 #include <string>
 #include <vector>
@@ -500,6 +505,45 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   if (!strcmp(cmd, "map_series_reset")) {
     check(c, swrt_map_series_reset(c), "swrt_map_series_reset");
+    return;
+  }
+  if (!strcmp(cmd, "track_begin")) {  // (ids): 0-based original packet indices, as doubles
+    need(na, 2, cmd);
+    const double* v = reals(a[1], "ids");
+    std::vector<int64_t> ids(mxGetNumberOfElements(a[1]));
+    for (size_t i = 0; i < ids.size(); ++i) {
+      if (!(v[i] >= -9.0e15 && v[i] <= 9.0e15) || (double)(int64_t)v[i] != v[i])
+        mexErrMsgIdAndTxt("swrt:arg", "ids must be whole numbers");
+      ids[i] = (int64_t)v[i];
+    }
+    check(c, swrt_track_begin(c, ids.data(), (int64_t)ids.size()), "swrt_track_begin");
+    return;
+  }
+  if (!strcmp(cmd, "track_record")) {  // (f, gH, nslots, alpha, bump)
+    need(na, 6, cmd);
+    check(c, swrt_track_record(c, scalar(a[1]), scalar(a[2]), (int)scalar(a[3]), scalar(a[4]), scalar(a[5])),
+          "swrt_track_record");
+    return;
+  }
+  if (!strcmp(cmd, "track_record_history")) {  // (first, count, f, gH, nslots, alphas, bump): [] alphas = none
+    need(na, 8, cmd);
+    const int64_t count = (int64_t)scalar(a[2]);
+    const size_t nal = mxGetNumberOfElements(a[6]);
+    if (nal != 0 && (int64_t)nal != count) mexErrMsgIdAndTxt("swrt:arg", "alphas must hold one value per frame");
+    check(c, swrt_track_record_history(c, (int64_t)scalar(a[1]), count, scalar(a[3]), scalar(a[4]), (int)scalar(a[5]),
+                                       nal ? reals(a[6], "alphas") : nullptr, scalar(a[7])),
+          "swrt_track_record_history");
+    return;
+  }
+  if (!strcmp(cmd, "track_get")) {  // -> m x 8 x frames [x y k l Omega zeta sigma D]
+    const int64_t nf = swrt_track_frames(c), m = swrt_track_count(c);
+    const mwSize dims[3] = {(mwSize)m, 8, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    check(c, swrt_track_get(c, 0, nf, mxGetDoubles(plhs[0])), "swrt_track_get");
+    return;
+  }
+  if (!strcmp(cmd, "track_reset")) {
+    check(c, swrt_track_reset(c), "swrt_track_reset");
     return;
   }
   mexErrMsgIdAndTxt("swrt:arg", "unknown command '%s'", cmd);

@@ -99,6 +99,14 @@ SIGNATURES = {
     "swrt_map_series_cells": (_I, [_VP]),
     "swrt_map_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "swrt_map_series_reset": (_INT, [_VP]),
+    "swrt_track_begin": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64), _I]),
+    "swrt_track_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
+    "swrt_track_record_history": (_INT, [_VP, _I, _I, _D, _D, _INT, _P, _D]),
+    "swrt_track_frames": (_I, [_VP]),
+    "swrt_track_count": (_I, [_VP]),
+    "swrt_track_ids": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_track_get": (_INT, [_VP, _I, _I, _P]),
+    "swrt_track_reset": (_INT, [_VP]),
     "swrt_raydiag_mark": (_INT, [_VP, _D, _D, _INT, _D, _D]),
     "swrt_raydiag_sample": (_INT, [_VP, _D, _D, _INT, _D, _D, _P, _P]),
     "swrt_raydiag_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
@@ -606,6 +614,58 @@ class Context:
 
     def map_series_reset(self):
         self._chk(self._L.swrt_map_series_reset(self._h), "swrt_map_series_reset")
+
+    # ---- the track series (swrt_track_*: trajectories of chosen packets) ------
+    def track_begin(self, ids):
+        """Track the packets with the original indices ``ids`` (distinct, in
+        0..N-1); a frame's rows follow their order.  Empties the series."""
+        ids = np.asarray(ids)
+        if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+            raise ValueError("ids must be a one-dimensional sequence of integers")
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        ptr = ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if ids.size else None
+        self._chk(self._L.swrt_track_begin(self._h, ptr, ids.size), "swrt_track_begin")
+
+    def track_record(self, f, gH, nslots=1, alpha=0.0, bump=1e-13):
+        """Append the tracked packets' frame [x, y, k, l, Omega, zeta, sigma, D]
+        to the device-side series (queued; no host wait).  ``nslots=0``: no
+        flow, the last four columns are NaN."""
+        self._chk(self._L.swrt_track_record(self._h, float(f), float(gH), int(nslots), float(alpha), float(bump)),
+                  "swrt_track_record")
+
+    def track_record_history(self, first, count, f, gH, nslots=1, alphas=None, bump=1e-13):
+        """One track frame per history frame [first, first + count) (queued; no
+        host wait), frame i with the snapshot blend ``alphas[i]`` (None: 0)."""
+        if alphas is not None:
+            alphas = np.ascontiguousarray(alphas, dtype=np.float64)
+            if alphas.shape != (int(count),):
+                raise ValueError("alphas must hold one value per frame")
+        self._chk(self._L.swrt_track_record_history(self._h, int(first), int(count), float(f), float(gH),
+                                                    int(nslots), _p(alphas), float(bump)),
+                  "swrt_track_record_history")
+
+    def track_frames(self):
+        return int(self._L.swrt_track_frames(self._h))
+
+    def track_ids(self):
+        """The ids of the open series, in the order given (empty if none)."""
+        ids = np.zeros(max(int(self._L.swrt_track_count(self._h)), 0), dtype=np.int64)
+        if ids.size:
+            self._chk(self._L.swrt_track_ids(self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+                      "swrt_track_ids")
+        return ids
+
+    def track_series(self, first=0, count=None):
+        """Recorded frames [first, first + count) as (count, 8, m) float64:
+        [t, c, j] is column c of packet ids[j] at frame t."""
+        count = self.track_frames() - first if count is None else count
+        m = max(int(self._L.swrt_track_count(self._h)), 0)
+        out = np.empty((max(count, 0), 8, m))
+        self._chk(self._L.swrt_track_get(self._h, int(first), int(count), _p(out)), "swrt_track_get")
+        return out
+
+    def track_reset(self):
+        self._chk(self._L.swrt_track_reset(self._h), "swrt_track_reset")
 
     # ---- the invariant and the flow along the rays (swrt_raydiag_*) ----------
     def raydiag_mark(self, f, gH, nslots=1, alpha=0.0, bump=1e-13):

@@ -436,6 +436,7 @@ int swrt_packets_set(swrt_ctx* c, const double* x, const double* k, int64_t n) {
   }
   if (!c->bins.buf) HIPCHK(c, c->bins.alloc());
   if (n != c->n) c->rd.drop();  // Omega_0 and the frame series belong to an ensemble of the old size
+  if (n != c->n) c->trk.drop();  // (the tracked ids too)
   c->n = n;
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(c->pk.cur.x.get(), x, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
@@ -1335,6 +1336,95 @@ int swrt_map_series_reset(swrt_ctx* c) {
   if (!c) return SWRT_ERR_ARG;
   c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
   c->map.series.ext.cleared();
+  return SWRT_OK;
+}
+
+// ---- the track series (swrt_track.hpp, swrt_host_diag.hpp) ----
+int swrt_track_begin(swrt_ctx* c, const int64_t* ids, int64_t m) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(packets_check(c));
+  if (m < 1 || m > c->n || m > kTrackMax) return fail(c, SWRT_ERR_ARG, "m must be 1..min(N, 2^20)");
+  if (!ids) return fail(c, SWRT_ERR_ARG, "NULL buffer (ids)");
+  std::vector<int> table((size_t)c->n, -1), dense((size_t)m);
+  for (int64_t j = 0; j < m; ++j) {
+    if (ids[j] < 0 || ids[j] >= c->n)
+      return fail(c, SWRT_ERR_ARG, "track id " + std::to_string(ids[j]) + " out of range (0..N-1)");
+    if (table[ids[j]] >= 0) return fail(c, SWRT_ERR_ARG, "track id " + std::to_string(ids[j]) + " given twice");
+    table[ids[j]] = (int)j;
+    dense[j] = (int)ids[j];
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  TrackState& tr = c->trk;
+  HIPCHK_RC(series_release(c, tr.series));  // (waits: queued records read the old tables too)
+  tr.drop();
+  HIPCHK(c, tr.slot_of.alloc(c->n));
+  HIPCHK(c, tr.dids.alloc(m));
+  HIPCHK(c, hipMemcpyAsync(tr.slot_of.get(), table.data(), sizeof(int) * c->n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tr.dids.get(), dense.data(), sizeof(int) * m, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  tr.ids.assign(ids, ids + m);
+  tr.m = m;
+  tr.open = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_track_record(swrt_ctx* c, double f, double gH, int nslots, double alpha, double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c, false, track_slot_mask(nslots));
+  HIPCHK_RC(track_check(c, nslots));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(track_reserve(c, 1));
+  return track_record_frame(c, f, gH, nslots, alpha, bump);
+  GUARD_END(c)
+}
+
+int swrt_track_record_history(swrt_ctx* c, int64_t first, int64_t count, double f, double gH, int nslots,
+                              const double* alphas, double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c, false, track_slot_mask(nslots));
+  HIPCHK_RC(track_check(c, nslots));
+  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
+  if (nslots == 2 && !alphas && count > 0) return fail(c, SWRT_ERR_ARG, "NULL buffer (alphas, two snapshots)");
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(track_reserve(c, count));
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t off = (first + i) * 2 * c->n;
+    HIPCHK_RC(track_record_frame(c, f, gH, nslots, alphas ? alphas[i] : 0.0, bump, c->hist.a.get() + off,
+                                 c->hist.b.get() + off));
+  }
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int64_t swrt_track_frames(const swrt_ctx* c) { return c ? c->trk.series.ext.frames() : -1; }
+
+int64_t swrt_track_count(const swrt_ctx* c) { return c ? (c->trk.open ? c->trk.m : 0) : -1; }
+
+int swrt_track_ids(const swrt_ctx* c, int64_t* ids_out) {
+  if (!c) return SWRT_ERR_ARG;
+  if (!c->trk.open) return SWRT_ERR_STATE;
+  if (!ids_out) return SWRT_ERR_ARG;
+  std::copy(c->trk.ids.begin(), c->trk.ids.end(), ids_out);
+  return SWRT_OK;
+}
+
+int swrt_track_get(swrt_ctx* c, int64_t first, int64_t count, double* frames_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  return series_get(c, c->trk.series, c->trk.frame(), 0, first, count, frames_out, nullptr,
+                    "frame range out of bounds");
+  GUARD_END(c)
+}
+
+int swrt_track_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
+  c->trk.series.ext.cleared();
   return SWRT_OK;
 }
 

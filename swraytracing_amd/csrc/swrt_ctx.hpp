@@ -353,6 +353,25 @@ inline int64_t map_series_min(size_t frame_bytes) {
   return std::min<int64_t>(4096, std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / frame_bytes)));
 }
 
+// the track series (swrt_track_*, swrt_track.hpp): the trajectories of m chosen
+// packets.  Buffers of its own, as the other recorders'.  A frame's rows are
+// packets of one ensemble, so swrt_packets_set with another N closes it.
+struct TrackState {
+  bool open = false;           // swrt_track_begin was called
+  int64_t m = 0;               // tracked packets
+  std::vector<int64_t> ids;    // their original indices, in the caller's order
+  DevBuf<int> slot_of;         // n entries: the frame row of an original index, or -1
+  DevBuf<int> dids;            // m entries: ids on the device (history frames)
+  Series<double> series;       // recorded frames, m x 8 doubles each (one column)
+  size_t frame() const { return (size_t)8 * m; }
+  void drop() {                // the ensemble changed size: the ids name another one's packets
+    open = false;
+    m = 0;
+    ids.clear();
+    series.ext.cleared();
+  }
+};
+
 // debug knobs (swrt_debug_set): a spin kernel queued on every extra packet
 // stream before each of its part launches (adversarial overlap of consecutive
 // calls), and the pre-third-buffer ordering after a source-gather sort
@@ -428,6 +447,7 @@ struct swrt_ctx {
   RayDiagState rd;
   OmegaSeriesState om;
   MapSeriesState map;
+  TrackState trk;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an
   // event marker, ~7 us of idle on each stream).  Only consecutive split

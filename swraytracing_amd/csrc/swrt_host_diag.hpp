@@ -1,9 +1,10 @@
-// swrt_host_diag.hpp — host side of the three device-side recorders: the ray
-// diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp) and the
-// map series (swrt_map.hpp).  Each appends frames to a Series of its state
-// (swrt_ctx.hpp) without a host wait: a reserve, the launches that write at the
-// series' end, a commit.  The order below (ray, spectrum, map) is the order
-// their template kernels are first named in, hence emitted in.
+// swrt_host_diag.hpp — host side of the four device-side recorders: the ray
+// diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp), the
+// map series (swrt_map.hpp) and the track series (swrt_track.hpp).  Each
+// appends frames to a Series of its state (swrt_ctx.hpp) without a host wait:
+// a reserve, the launches that write at the series' end, a commit.  The order
+// below (ray, spectrum, map, track) is the order their template kernels are
+// first named in, hence emitted in.
 #pragma once
 #include <cmath>
 
@@ -13,6 +14,7 @@
 #include "swrt_diag.hpp"
 #include "swrt_raydiag.hpp"
 #include "swrt_map.hpp"
+#include "swrt_track.hpp"
 
 namespace {
 
@@ -223,6 +225,49 @@ int map_tile_launch(swrt_ctx* c) {
   HIPCHK(c, hipGetLastError());
   ms.series.ext.committed(1);
   ++ms.tiled_frames;
+  return SWRT_OK;
+}
+
+// ---- the track series ----
+// The two records' common checks; nslots == 0 (no flow) needs no slot.
+int track_check(swrt_ctx* c, int nslots) {
+  if (!c->trk.open) return fail(c, SWRT_ERR_STATE, "call swrt_track_begin first");
+  if (nslots == 0) return packets_check(c);
+  if (nslots != 1 && nslots != 2) return fail(c, SWRT_ERR_ARG, "nslots must be 0, 1 or 2");
+  return raydiag_check(c, nslots);
+}
+
+// The field slots a record with `nslots` snapshots reads (SlotUse's wait mask).
+inline unsigned track_slot_mask(int nslots) { return nslots <= 0 ? 0u : nslots == 1 ? 1u : kSlots01; }
+
+int track_reserve(swrt_ctx* c, int64_t extra) {
+  TrackState& tr = c->trk;
+  return series_reserve(c, tr.series, tr.frame(), 0, extra, map_series_min(tr.frame() * sizeof(double)));
+}
+
+// One frame at the series' end: from the packets, or from a history frame.
+int track_record_frame(swrt_ctx* c, double f, double gH, int nslots, double alpha, double bump,
+                       const double* hist_x = nullptr, const double* hist_k = nullptr) {
+  TrackState& tr = c->trk;
+  TrackArgs a;
+  a.f0 = nslots ? view_of(c->slot[0]) : FieldView{};
+  a.f1 = nslots == 2 ? view_of(c->slot[1]) : a.f0;
+  a.nslots = nslots;
+  a.alpha = alpha;
+  a.bump = bump;
+  a.x = hist_x ? hist_x : c->pk.cur.x.get();
+  a.k = hist_x ? hist_k : c->pk.cur.k.get();
+  a.perm = c->pk.cur.perm.get();
+  a.lookup = hist_x ? tr.dids.get() : tr.slot_of.get();
+  a.n = c->n;
+  a.m = tr.m;
+  a.f2 = f * f;
+  a.gH = gH;
+  a.frame = tr.series.end_a(tr.frame());
+  const dim3 grid(nblocks(hist_x ? tr.m : c->n, kTrackThreads)), block(kTrackThreads);
+  hipLaunchKernelGGL(hist_x ? track_kernel<true> : track_kernel<false>, grid, block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  tr.series.ext.committed(1);
   return SWRT_OK;
 }
 

@@ -55,6 +55,32 @@ struct RayDiagArgs {
   double* rec;       // N records of kRayDiagRec doubles by original index (not MARK)
 };
 
+// What one packet at (x, y, k, l) leaves: omega(k), Omega and the flow's three
+// scalars, in the operation order of the header comment.  ray_diag_kernel's
+// record and the track series' frame (swrt_track.hpp) are both this function,
+// hence the same bits.
+struct RayPoint {
+  double w, Om, zeta, sigma, D;
+};
+
+__device__ __forceinline__ void ray_point_omega(const double I[kRec], double k1, double k2, double f2, double gH,
+                                                RayPoint& r) {
+  const double w = sqrt(f2 + gH * (k1 * k1 + k2 * k2));
+  const double Om = w + (I[0] * k1 + I[1] * k2);
+  r.w = w;
+  r.Om = Om;
+}
+
+__device__ __forceinline__ void ray_point_flow(const double I[kRec], RayPoint& r) {
+  const double zeta = I[4] - I[3];               // RaytracingScheme.m:20
+  const double s1 = I[2] - I[5], s2 = I[4] + I[3];
+  const double sigma = sqrt(s1 * s1 + s2 * s2);  // RaytracingScheme.m:25
+  const double D = I[5] * I[5] + I[4] * I[3];    // RaytracingScheme.m:30
+  r.zeta = zeta;
+  r.sigma = sigma;
+  r.D = D;
+}
+
 // MARK: Omega_0 of every packet (symplectic_full_fourier.m:41) and nothing else.
 // nslots is a run-time branch as in eval_kernel: with the two-snapshot gather
 // alone in straight-line code the compiler issues every tap's loads at once,
@@ -66,16 +92,15 @@ __global__ void __launch_bounds__(kRayDiagThreads) ray_diag_kernel(RayDiagArgs a
   const double k1 = a.k[p], k2 = a.k[a.n + p];
   double I[kRec];  // u, v, u_x, u_y, v_x, v_y
   eval_flow(a.f0, a.f1, a.nslots, a.alpha, a.x[p], a.x[a.n + p], a.bump, I);
-  const double w = sqrt(a.f2 + a.gH * (k1 * k1 + k2 * k2));
-  const double Om = w + (I[0] * k1 + I[1] * k2);
+  RayPoint pt;
+  ray_point_omega(I, k1, k2, a.f2, a.gH, pt);
+  const double w = pt.w, Om = pt.Om;
   const int64_t o = a.perm ? a.perm[p] : p;
   if constexpr (MARK) {
     a.omega0[o] = Om;
   } else {
-    const double zeta = I[4] - I[3];               // RaytracingScheme.m:20
-    const double s1 = I[2] - I[5], s2 = I[4] + I[3];
-    const double sigma = sqrt(s1 * s1 + s2 * s2);  // RaytracingScheme.m:25
-    const double D = I[5] * I[5] + I[4] * I[3];    // RaytracingScheme.m:30
+    ray_point_flow(I, pt);
+    const double zeta = pt.zeta, sigma = pt.sigma, D = pt.D;
     double r = 0.0;
     if (a.omega0 != nullptr) {
       const double Om0 = a.omega0[o];

@@ -120,6 +120,56 @@ def map_fields(planes, frac_bits):
     return out
 
 
+def track_ids_array(ids, n_total):
+    """``ids`` as a checked int64 array: a one-dimensional, non-empty sequence
+    of distinct integers in 0..n_total-1 (ValueError otherwise)."""
+    a = np.asarray(ids)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError("track ids must be a non-empty one-dimensional sequence")
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.floating) or not np.all(a == np.floor(a)):
+            raise ValueError("track ids must be integers")
+    a = a.astype(np.int64)
+    if a.min() < 0 or a.max() >= int(n_total):
+        raise ValueError(f"track ids must lie in 0..{int(n_total) - 1}")
+    if np.unique(a).size != a.size:
+        raise ValueError("track ids must be distinct")
+    return a
+
+
+def shard_track_rows(ids, lo, hi):
+    """The rows of a track frame (positions in ``ids``) whose packets lie in
+    the shard [lo, hi), in the order they appear in ``ids``."""
+    ids = np.asarray(ids, dtype=np.int64)
+    return np.nonzero((ids >= lo) & (ids < hi))[0]
+
+
+def combine_tracks(parts, ids, bounds):
+    """The track series of an ensemble from its shards' series
+    (swrt_track_*).  ``ids``: the m global packet ids in the caller's order;
+    ``bounds``: every shard's [lo, hi); ``parts``: one (T, 8, m_r) series per
+    shard, its rows the ids inside the shard's bounds in the order they have
+    in ``ids`` (a shard that owns none gives (T, 8, 0), or None).  Returns
+    (T, 8, m): every row back at its place in ``ids``, bit for bit."""
+    ids = np.asarray(ids, dtype=np.int64)
+    parts, bounds = list(parts), list(bounds)
+    if len(parts) != len(bounds) or not parts:
+        raise ValueError("one series per shard")
+    rows = [shard_track_rows(ids, lo, hi) for lo, hi in bounds]
+    if sum(r.size for r in rows) != ids.size:
+        raise ValueError("the shards' bounds must cover every id once")
+    T = max((np.asarray(p).shape[0] for p, r in zip(parts, rows) if r.size), default=0)
+    out = np.empty((T, 8, ids.size))
+    for p, r in zip(parts, rows):
+        if r.size == 0:
+            continue
+        p = np.asarray(p, dtype=np.float64)
+        if p.shape != (T, 8, r.size):
+            raise ValueError("every shard must give (T, 8, m_r) for the same T and its own ids")
+        out.view(np.uint64)[:, :, r] = p.view(np.uint64)  # (the bits, NaN payloads included)
+    return out
+
+
 def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False):
     """[x, k, t] = ode_symplectic(x0, k0, dt, T, f, gH, scheme).
 
@@ -668,6 +718,110 @@ class PacketEnsemble:
             for planes, stats in st["kept"]:
                 self._append_maps(directory, planes, stats)
             st["kept"] = []
+        return st["frames"]
+
+    def begin_tracks(self, ids, directory=None):
+        """Track the packets with the **global** ids ``ids`` (distinct, in
+        0..N-1 of the whole ensemble; a frame's rows follow their order):
+        swrt_track_begin on this shard with the ids inside its bounds, as
+        local indices.  A shard that owns none records nothing.
+        ``directory``: where record_tracks drains the device series when it
+        grows large (default: the drained frames wait in host memory for
+        write_tracks)."""
+        ids = track_ids_array(ids, self.n_total)
+        lo, hi = self.bounds[self.rank] if self.bounds is not None else (0, self.n_total)
+        rows = shard_track_rows(ids, lo, hi)
+        self._trk = dict(ids=ids, rows=rows, directory=directory, frames=0, pending=0, kept=[], times=[],
+                         ids_written=False)
+        if rows.size > 0:
+            self.ctx.track_begin(ids[rows] - lo)
+
+    def record_tracks(self, t, nslots, alpha=0.0):
+        """Append this shard's track frame at the current state, time ``t``,
+        to the device-side series (queued, no host wait); the flow from slot 0
+        (``nslots=1``), the blend of slots 0 and 1 at ``alpha`` (2), or none
+        (0: Omega, zeta, sigma, D are NaN).  When the ensemble's device series
+        pass 256 MB they are drained: a collective when sharded, at the same
+        frame on every rank."""
+        st = getattr(self, "_trk", None)
+        if st is None:
+            raise SwrtError("record_tracks: call begin_tracks first")
+        st["frames"] += 1
+        st["pending"] += 1
+        st["times"].append(float(t))
+        if st["rows"].size > 0:
+            self.ctx.track_record(self.f, self.gH, nslots=nslots, alpha=alpha, bump=self.bump)
+        if st["pending"] * 64 * st["ids"].size > MAP_DRAIN_BYTES:
+            self._drain_tracks()
+
+    def _drain_tracks(self):
+        """The frames on the device, every shard's rows back in the caller's
+        id order, to the files or the host list of rank 0; the device series
+        emptied."""
+        st = self._trk
+        T, m = st["pending"], st["ids"].size
+        if T == 0:
+            return
+        if st["rows"].size > 0:
+            part = self.ctx.track_series(0, T)
+            self.ctx.track_reset()
+        else:
+            part = np.zeros((T, 8, 0))
+        times, st["times"] = st["times"], []
+        st["pending"] = 0
+        if self.world > 1:
+            import torch
+            import torch.distributed as dist
+
+            from .dist import _device_for
+            dev = _device_for(dist.get_backend())
+            padded = np.zeros((T, 8, m), dtype=np.int64)  # (as integers: the transport keeps every bit)
+            padded[:, :, :part.shape[2]] = part.view(np.int64)
+            buf = torch.from_numpy(padded).to(dev)
+            out = [torch.empty_like(buf) for _ in range(self.world)]
+            dist.all_gather(out, buf)
+            if self.rank != 0:
+                return
+            counts = [shard_track_rows(st["ids"], lo, hi).size for lo, hi in self.bounds]
+            parts = [o.cpu().numpy()[:, :, :c].view(np.float64) for o, c in zip(out, counts)]
+            series = combine_tracks(parts, st["ids"], self.bounds)
+        else:
+            series = part
+        if st["directory"] is None:
+            st["kept"].append((series, times))
+        else:
+            self._append_tracks(st["directory"], series, times)
+
+    def _append_tracks(self, directory, series, times):
+        L = self.L
+        for fr, t in zip(series, times):
+            write_field(np.mod(fr[0:2].T + L / 2, L) - L / 2, os.path.join(directory, "track_x"))
+            write_field(fr[2:4].T, os.path.join(directory, "track_k"))
+            write_field(fr[4:8].T, os.path.join(directory, "track_diag"))
+            write_field(np.array([[t]]), os.path.join(directory, "track_time"))
+
+    def write_tracks(self, directory):
+        """The run's track series as write_field files: track_x.bin (m x 2 per
+        frame, x wrapped to [-L/2, L/2) as write_frame wraps packet_x.bin),
+        track_k.bin (m x 2), track_diag.bin (m x 4: Omega, zeta, sigma, D),
+        track_time.bin (one value per frame) and track_ids.bin (one frame of m
+        values, the global ids in row order) — read_field("track_x", m, 2, 1,
+        frames) and load_data.m with Npackets = m read them.  Sharded: a
+        collective; rank 0 writes.  Returns the frames recorded."""
+        st = getattr(self, "_trk", None)
+        if st is None:
+            raise SwrtError("write_tracks: call begin_tracks first")
+        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
+            raise ValueError("write_tracks: begin_tracks drained into another directory")
+        self._drain_tracks()
+        if self.rank == 0:
+            if st["directory"] is None:
+                for series, times in st["kept"]:
+                    self._append_tracks(directory, series, times)
+                st["kept"] = []
+            if not st["ids_written"]:
+                write_field(st["ids"].astype(np.float64), os.path.join(directory, "track_ids"))
+                st["ids_written"] = True
         return st["frames"]
 
     def write_frame(self, t, directory, packet_files=True):

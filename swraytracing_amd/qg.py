@@ -21,7 +21,7 @@ import os
 import numpy as np
 
 from ._lib import Context, QGParams
-from .integrate import PacketEnsemble
+from .integrate import PacketEnsemble, track_ids_array
 from .io import write_field
 from .runlog import RunLog, parameter_block
 from .scheme import BUMP_QG
@@ -231,7 +231,8 @@ def _fresh_outputs(out_dir, fresh):
     if not fresh:
         return
     for name in ("packet_x", "packet_k", "packet_time", "pv", "pv_time", "omega_hist", "omega_stats", "omega_edges",
-                 "map_n", "map_omega", "map_k", "map_l", "map_stats"):
+                 "map_n", "map_omega", "map_k", "map_l", "map_stats", "track_x", "track_k", "track_diag", "track_time",
+                 "track_ids"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
@@ -258,6 +259,34 @@ def _map_args(map_cells, map_frac_bits):
     if isinstance(map_frac_bits, bool) or int(map_frac_bits) != map_frac_bits or not 0 <= int(map_frac_bits) <= 32:
         raise ValueError("map_frac_bits must be an integer 0..32")
     return int(map_cells), int(map_frac_bits)
+
+
+def _track_args(track_ids, track_every, Npackets, default_every):
+    """The drivers' ``track_ids`` / ``track_every`` checked before anything
+    runs: (ids as int64 in the caller's order, PDE steps per track frame), or
+    None without ``track_ids``.  An integer K stands for K ids spread evenly,
+    arange(K) * (Npackets // K)."""
+    if track_every is None:
+        track_every = default_every
+    elif isinstance(track_every, (bool, np.bool_)) or not np.isscalar(track_every) or not np.isreal(track_every) \
+            or int(track_every) != track_every or int(track_every) < 1:
+        raise ValueError("track_every must be an integer >= 1 (PDE steps per track frame)")
+    if track_ids is None:
+        return None
+    if isinstance(track_ids, (bool, np.bool_)):
+        raise ValueError("track_ids must be a sequence of packet ids or an integer count")
+    if np.isscalar(track_ids):
+        if not np.isreal(track_ids) or int(track_ids) != track_ids:
+            raise ValueError("track_ids: the count K must be an integer")
+        K = int(track_ids)
+        if not 1 <= K <= int(Npackets):
+            raise ValueError(f"track_ids: the count K must be 1..Npackets ({int(Npackets)})")
+        ids = np.arange(K, dtype=np.int64) * (int(Npackets) // K)
+    else:
+        ids = track_ids_array(track_ids, Npackets)
+    if ids.size > 1 << 20:
+        raise ValueError("track_ids: at most 2^20 packets can be tracked")
+    return ids, int(track_every)
 
 
 def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False):
@@ -517,7 +546,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                   out_dir="data", nsub=4, max_steps=None, seed=146, verbose=False, r_drag=0.1,
                   packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
                   pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None, packet_files=True,
-                  map_cells=None, map_frac_bits=20):
+                  map_cells=None, map_frac_bits=20, track_ids=None, track_every=None):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -546,10 +575,20 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     quantised to 2^-``map_frac_bits``) and written as map_n.bin, map_omega.bin,
     map_k.bin, map_l.bin (one m x m frame each per packet frame, exact
     integers) and map_stats.bin (n, rejected, m, frac_bits per frame).
+    ``track_ids`` (a sequence of distinct packet ids, or an integer K for
+    arange(K) * (Npackets // K)): the trajectories of those packets are
+    recorded on the device (swrt_track_*) every ``track_every`` PDE steps
+    (default: the packet frames' cadence, 5) and written at the end as
+    track_x.bin, track_k.bin (m x 2 per frame, the layout of packet_x.bin /
+    packet_k.bin: load_data.m reads them with Npackets = m), track_diag.bin
+    (m x 4: Omega, zeta, sigma, D of swrt_raydiag_sample at the packets' time;
+    NaN in the first frame, written before any snapshot exists),
+    track_time.bin and track_ids.bin; no other output changes.
     Returns a dict of run facts (dt, Nsteps, steps run, frames written,
-    final t, spectrum_frames, map_frames)."""
+    final t, spectrum_frames, map_frames, track_frames)."""
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files)
     map_args = _map_args(map_cells, map_frac_bits)
+    track_args = _track_args(track_ids, track_every, Npackets, 5)  # (5: packet_steps_per_save below)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
@@ -604,6 +643,10 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     maps = ens is not None and map_args is not None
     if maps:
         ens.begin_map(*map_args, directory=out_dir)
+    tracks = ens is not None and track_args is not None
+    if tracks:
+        ens.begin_tracks(track_args[0], directory=out_dir)
+        ens.record_tracks(dt * (packet_step_start - 1), 0)  # (no snapshot yet: the flow columns are NaN)
     if ens is not None:
         _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files, maps)
     if rank == 0:
@@ -628,6 +671,9 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                 snapshot(group.next_slot(), 0)  # grid_U(qk)
             have_cur = True
             group.add(dt)
+            if tracks and (step - packet_step_start + 1) % track_args[1] == 0:
+                group.flush()  # (slot 0 now holds the snapshot at the packets' time)
+                ens.record_tracks(t, 1)
             if (step - packet_step_start + 1) % packet_steps_per_save == 0:
                 group.flush()
                 _save_frame(ens, t, out_dir, spectrum, packet_files, maps)
@@ -644,25 +690,28 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
         link.close()
     spectrum_frames = ens.write_spectrum(out_dir) if spectrum else 0
     map_frames = ens.write_maps(out_dir) if maps else 0
+    track_frames = ens.write_tracks(out_dir) if tracks else 0
     ctx.synchronize()
     ctx.set_timing(timing)
     log.finish()
     log.close()
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
-                packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames)
+                packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
+                track_frames=track_frames)
 
 
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
                         out_dir="data", nsub=5, max_steps=None, seed=5, verbose=False,
                         packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
                         pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None,
-                        packet_files=True, map_cells=None, map_frac_bits=20):
+                        packet_files=True, map_cells=None, map_frac_bits=20, track_ids=None, track_every=None):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
     pv.bin holds the initial nx x nx x 2 frame only, as in the reference.
     ``packet_intervals``, ``integrator``, ``fresh``, ``spectrum_edges``,
-    ``packet_files``, ``map_cells``, ``map_frac_bits``: as in
+    ``packet_files``, ``map_cells``, ``map_frac_bits``, ``track_ids``,
+    ``track_every`` (default: this driver's packet cadence, 25): as in
     :func:`qgsw_raytrace`.
 
     Sharded (torch.distributed, world > 1): ``pde="owner"`` (default) — rank 0
@@ -676,6 +725,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     gloo; "device" / "host" to force one)."""
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files)
     map_args = _map_args(map_cells, map_frac_bits)
+    track_args = _track_args(track_ids, track_every, Npackets, 25)  # (25: packet_steps_per_save below)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
@@ -721,6 +771,10 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     maps = ens is not None and map_args is not None
     if maps:
         ens.begin_map(*map_args, directory=out_dir)
+    tracks = ens is not None and track_args is not None
+    if tracks:
+        ens.begin_tracks(track_args[0], directory=out_dir)
+        ens.record_tracks(dt * (packet_step_start - 1), 0)  # (no snapshot yet: the flow columns are NaN)
     if ens is not None:
         _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files, maps)
     if rank == 0:
@@ -742,7 +796,11 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     # pv.bin writes are commented out, qg2layersw_raytrace.m:211-239)
     log.start()
     while loop.t <= T and (max_steps is None or loop.steps < max_steps):
-        if loop.step() and (loop.steps - packet_step_start + 1) % packet_steps_per_save == 0:
+        active = loop.step()
+        if active and tracks and (loop.steps - packet_step_start + 1) % track_args[1] == 0:
+            loop.flush()  # (slot 0 now holds the snapshot at the packets' time)
+            ens.record_tracks(loop.t, 1)
+        if active and (loop.steps - packet_step_start + 1) % packet_steps_per_save == 0:
             loop.flush()
             _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps)
             frames += 1
@@ -753,6 +811,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
         link.close()
     spectrum_frames = ens.write_spectrum(out_dir) if spectrum else 0
     map_frames = ens.write_maps(out_dir) if maps else 0
+    track_frames = ens.write_tracks(out_dir) if tracks else 0
     ctx.synchronize()
     ctx.set_timing(timing)
     log.finish()
@@ -760,4 +819,5 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     dt, dts, step, t = loop.dt, loop.dts, loop.steps, loop.t
     U0 = getattr(loop, "U0", U0)  # (a receiving rank never sees the owner's U0)
     return dict(dt=dt, dts=dts, Nsteps=Nsteps, steps=step, packet_frames=frames, t=t, U0=U0,
-                packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames)
+                packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
+                track_frames=track_frames)

@@ -46,7 +46,8 @@ def read_frame(pv_path, nx, frame, nlayers=1):
 
 def trace_stored(pv_path, nx, x, k, f, Cg, *, frames=None, times=None, nlayers=1, L=2 * math.pi, K_d2=None,
                  shear=0.0, k_scale=1.0, nsub=5, bump=BUMP_QG, out_dir=None, intervals_per_call=SLOT_INTERVALS,
-                 ctx: Context | None = None, shard=None, spectrum_edges=None, packet_files=True):
+                 ctx: Context | None = None, shard=None, spectrum_edges=None, packet_files=True, track_ids=None,
+                 track_every=None):
     """Advance packets (x, k: N x 2) through the stored frames of a PV series.
 
     ``frames``: 1-based frame numbers in time order (default: every frame in
@@ -61,12 +62,22 @@ def trace_stored(pv_path, nx, x, k, f, Cg, *, frames=None, times=None, nlayers=1
     :func:`swraytracing_amd.qg.qgsw_raytrace` — every frame's energy-vs-omega
     counts recorded on the device and written to ``out_dir`` at the end as
     omega_hist.bin / omega_stats.bin / omega_edges.bin (they need ``out_dir``).
+    ``track_ids``, ``track_every``: as in qgsw_raytrace, a PDE step being one
+    stored interval here — the tracked packets' frames at the first stored
+    frame and after every ``track_every`` intervals (default: where the packet
+    frames are written, after every call) go to ``out_dir`` as track_x.bin,
+    track_k.bin, track_diag.bin, track_time.bin and track_ids.bin (earlier
+    track files there are removed first).  The calls are cut at the track
+    frames; the packets and every other file keep their bits.
     Returns (x, k, t_end)."""
-    from .qg import _save_frame, _spectrum_args
+    from .qg import _save_frame, _spectrum_args, _track_args
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files)
     spectrum = spectrum_edges is not None
     if spectrum and out_dir is None:
         raise ValueError("spectrum_edges needs out_dir")
+    track_args = _track_args(track_ids, track_every, np.asarray(x).shape[0], 0)
+    if track_args is not None and out_dir is None:
+        raise ValueError("track_ids needs out_dir")
     ctx = ctx if ctx is not None else Context(0)
     nx = int(nx)
     if frames is None:
@@ -95,19 +106,35 @@ def trace_stored(pv_path, nx, x, k, f, Cg, *, frames=None, times=None, nlayers=1
         os.makedirs(out_dir, exist_ok=True)
         if spectrum:
             ens.begin_spectrum(spectrum_edges)
+        if track_args is not None:
+            for name in ("track_x", "track_k", "track_diag", "track_time", "track_ids"):
+                if os.path.exists(os.path.join(out_dir, name + ".bin")):
+                    os.remove(os.path.join(out_dir, name + ".bin"))
+            ens.begin_tracks(track_args[0], directory=out_dir)
+            ens.record_tracks(times[0], 0)  # (no snapshot loaded yet: the flow columns are NaN)
         _save_frame(ens, times[0], out_dir, spectrum, packet_files)
+    every = track_args[1] if track_args is not None else 0  # (0: at the packet frames)
     load(0, frames[0])
     i = 1
+    save_at = min(1 + intervals_per_call, len(frames))  # the i at which the next packet frame is written
     while i < len(frames):
-        g = min(intervals_per_call, len(frames) - i)
+        g = save_at - i
+        if every:
+            g = min(g, every - (i - 1) % every)  # a call ends at every track frame
         for j in range(g):
             load(1 + j, frames[i + j])
         ens.advance_intervals([times[i + j] - times[i + j - 1] for j in range(g)], nsub)
         ctx.swap_slots(0, g)  # the last frame starts the next call
         i += g
-        if out_dir is not None:
-            _save_frame(ens, times[i - 1], out_dir, spectrum, packet_files)
+        if track_args is not None and ((i - 1) % every == 0 if every else i == save_at):
+            ens.record_tracks(times[i - 1], 1)  # (slot 0 holds the stored frame at the packets' time)
+        if i == save_at:
+            save_at = min(i + intervals_per_call, len(frames))
+            if out_dir is not None:
+                _save_frame(ens, times[i - 1], out_dir, spectrum, packet_files)
     if spectrum:
         ens.write_spectrum(out_dir)
+    if track_args is not None:
+        ens.write_tracks(out_dir)
     xs, ks = ens.state()
     return xs, ks, times[-1]
