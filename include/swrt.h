@@ -423,6 +423,68 @@ int swrt_map_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* pl
 /* Empty the series; L, m, f, Cg and frac_bits stay. */
 int swrt_map_series_reset(swrt_ctx* ctx);
 
+/* The wave-vector plane of a run, kept on the device: the density of the
+ * ensemble over (k, l) and the moments of the wavevector, which
+ * raytracing_figures.m:19-26,76-83, SW_zero_background_raytracing.m:103-104
+ * and qgflow_animation.m:59-63 draw packet by packet.  The plane has m x m
+ * cells over [-K, K) in both components; the host computes s = m / (2.0*K)
+ * once, in double.  A record reads only the packets' k and l: no positions and
+ * no field slot.  Every packet has five values in this operation order, k, l,
+ * k*k, l*l, k*l (each product one double multiplication), each quantised once
+ * per packet: q = rint(v * 2^frac_bits), round half even.  A packet is
+ * rejected when k or l is not finite or any |v * 2^frac_bits| >= 2^38; it then
+ * adds to nothing but `rejected`.  A packet is inside iff -K <= k < K and
+ * -K <= l < K, tested on k and l themselves; its index is
+ * i = min((int)floor((k + K) * s), m - 1) (one add, then one multiply, never
+ * contracted; the product can round up to exactly m for the last double below
+ * K), j the same for l, and cell (i, j) sits at plane[i + m*j] (first index
+ * k).  A packet that is not rejected but not inside counts as `outside` and
+ * still adds to the moments.  A frame is
+ *   one m x m plane of int64 counts;
+ *   eight int64 stats [n, rejected, outside, sum q(k), sum q(l), sum q(k*k),
+ *   sum q(l*l), sum q(k*l)].
+ * With n <= 2^24 every sum stays below 2^62: integer addition is exact and
+ * order-free, so a frame is a function of the packet set alone (not of the
+ * storage order, the binning, the launch shape or a shard split), and the
+ * frame of a sharded ensemble is the element-wise sum of the shards' frames.
+ * Negative sums wrap in two's complement and are read back as int64.  With
+ * n_used = n - rejected the mean wavevector is sum q(k) / n_used *
+ * 2^-frac_bits, and the covariance follows from the second moments. */
+
+/* Open a series: K > 0 finite, 1 <= m <= 4096, 0 <= frac_bits <= 32, at most
+ * 2^24 packets set (SWRT_ERR_ARG with a message otherwise).  Empties the
+ * series. */
+int swrt_kmap_series_begin(swrt_ctx* ctx, double K, int64_t m, int frac_bits);
+
+/* Append the frame of the current packets: queued on the packet stream after
+ * whatever last wrote the packets (both packet streams, the ode23 attempts, a
+ * re-binning's parked set); the host does not wait.  Capacity: 64 MiB of
+ * frames (at least one, at most 4096), doubled when full; only a growing call
+ * may wait for the stream, and a failed allocation is an error return.  Up to
+ * m = 128 every workgroup counts into a private plane in LDS and adds its
+ * non-zero cells to the frame; beyond, every packet adds through global
+ * memory: the same integers.  SWRT_ERR_STATE before swrt_kmap_series_begin,
+ * SWRT_ERR_ARG without packets or with more than 2^24. */
+int swrt_kmap_series_record(swrt_ctx* ctx);
+
+/* One frame per history frame in [first, first + count): the same bits as
+ * swrt_kmap_series_record on packets set to that frame.  A range out of
+ * bounds: SWRT_ERR_ARG. */
+int swrt_kmap_series_record_history(swrt_ctx* ctx, int64_t first, int64_t count);
+
+/* Frames recorded since begin or the last reset; m of the open series, 0 if none. */
+int64_t swrt_kmap_series_frames(const swrt_ctx* ctx);
+int64_t swrt_kmap_series_cells(const swrt_ctx* ctx);
+
+/* Frames [first, first + count): plane_out count x m x m and stats8_out
+ * count x 8, frame-major.  Either may be NULL, not both (SWRT_ERR_ARG).
+ * Waits for the frames. */
+int swrt_kmap_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* plane_out,
+                         int64_t* stats8_out);
+
+/* Empty the series; K, m and frac_bits stay. */
+int swrt_kmap_series_reset(swrt_ctx* ctx);
+
 /* The trajectories of a chosen few packets, kept on the device: what
  * images/QG_spread*.png, the (k, l) paths of raytracing_figures.m:76-83 and
  * the Omega time series draw per packet, and analysis/load_data.m:29-33 reads
@@ -905,7 +967,12 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
  *   path (swrt_map_series_record), summed over the context's life.
  * SWRT_DEBUG_MAP_STRAYS (get only): packets the tile path added through
  *   global memory because they had drifted out of their tile's LDS window,
- *   summed over those frames; reading it waits for the queued records. */
+ *   summed over those frames; reading it waits for the queued records.
+ * SWRT_DEBUG_KMAP_GLOBAL 0..3 (default 0): the kernel of the k-plane series'
+ *   records.  0: by m (the LDS kernel up to m = 128, the global one beyond);
+ *   1: the global kernel for every m, as it ships; 2 / 3: the global kernel
+ *   with / without its wave-level merge (tools/kmap_series_rate.py).  Every
+ *   value gives the same integers. */
 #define SWRT_DEBUG_HAZARD_CHECK 1
 #define SWRT_DEBUG_SPIN_US 2
 #define SWRT_DEBUG_LEGACY_PARK 3
@@ -923,6 +990,7 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
 #define SWRT_DEBUG_ODE23_DENSE_REBINS 16
 #define SWRT_DEBUG_MAP_TILED_FRAMES 17
 #define SWRT_DEBUG_MAP_STRAYS 18
+#define SWRT_DEBUG_KMAP_GLOBAL 19
 int swrt_debug_set(swrt_ctx* ctx, int key, int64_t value);
 int swrt_debug_get(swrt_ctx* ctx, int key, int64_t* value_out);
 

@@ -89,6 +89,38 @@ classdef SwrtContext < handle
             swrt_mex('map_series_reset', obj.id());
         end
 
+        % The wave-vector plane on the device (what raytracing_figures.m:19-26,
+        % 76-83 scatter packet by packet): per frame an m x m int64 count
+        % plane over [-K, K) x [-K, K), first index k, and eight int64 stats
+        % [n; rejected; outside; sum q(k); sum q(l); sum q(k*k); sum q(l*l);
+        % sum q(k*l)], q = round(v * 2^frac_bits).
+        function kmap_series_begin(obj, K, m, frac_bits)
+            if nargin < 4, frac_bits = 16; end
+            swrt_mex('kmap_series_begin', obj.id(), K, m, frac_bits);
+        end
+
+        function kmap_series_record(obj)
+            swrt_mex('kmap_series_record', obj.id());
+        end
+
+        function kmap_series_record_history(obj, first, count)
+            % history frames first .. first+count-1, 0-based
+            swrt_mex('kmap_series_record_history', obj.id(), first, count);
+        end
+
+        function n = kmap_series_frames(obj)
+            n = swrt_mex('kmap_series_frames', obj.id());
+        end
+
+        function [planes, stats] = kmap_series_get(obj)
+            % planes: int64 m x m x frames; stats: int64 8 x frames
+            [planes, stats] = swrt_mex('kmap_series_get', obj.id());
+        end
+
+        function kmap_series_reset(obj)
+            swrt_mex('kmap_series_reset', obj.id());
+        end
+
         % The trajectories of chosen packets on the device (what
         % raytracing_figures.m:76-83 and load_data.m:29-33 take per packet,
         % for m of an ensemble too large to download): a frame is m x 8,

@@ -50,6 +50,11 @@
 //   swrt_mex('map_series_record', h);  swrt_mex('map_series_record_history', h, first, count)
 //   [planes, stats] = swrt_mex('map_series_get', h)           % m x m x 4 x frames, 2 x frames
 //   swrt_mex('map_series_reset', h)
+//   swrt_mex('kmap_series_begin', h, K, m[, frac_bits])       % (k, l)-plane counts and wavevector moments on the device
+//   swrt_mex('kmap_series_record', h);  swrt_mex('kmap_series_record_history', h, first, count)
+//   n = swrt_mex('kmap_series_frames', h)
+//   [planes, stats] = swrt_mex('kmap_series_get', h)          % int64 m x m x frames, int64 8 x frames
+//   swrt_mex('kmap_series_reset', h)
 //   swrt_mex('track_begin', h, ids)                           % trajectories of chosen packets; ids 0-based doubles
 //   swrt_mex('track_record', h, f, gH, nslots, alpha, bump)   % nslots 0: no flow, Omega..D are NaN
 //   swrt_mex('track_record_history', h, first, count, f, gH, nslots, alphas, bump)   % alphas [] when nslots < 2
@@ -60,6 +65,11 @@
 #include <vector>
 
 #include "mex.h"
+#if defined(__has_include)
+#if __has_include("mex_int64.h")
+#include "mex_int64.h"  // a test build against tests/mex_shim: its mex.h declares no int64 arrays
+#endif
+#endif
 #include "swrt.h"
 
 static std::vector<swrt_ctx*> g_ctx;  // handle h = index + 1; closed handles hold nullptr
@@ -505,6 +515,41 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   if (!strcmp(cmd, "map_series_reset")) {
     check(c, swrt_map_series_reset(c), "swrt_map_series_reset");
+    return;
+  }
+  if (!strcmp(cmd, "kmap_series_begin")) {  // (K, m[, frac_bits = 16])
+    need(na, 3, cmd);
+    check(c, swrt_kmap_series_begin(c, scalar(a[1]), (int64_t)scalar(a[2]), na > 3 ? (int)scalar(a[3]) : 16),
+          "swrt_kmap_series_begin");
+    return;
+  }
+  if (!strcmp(cmd, "kmap_series_record")) {
+    check(c, swrt_kmap_series_record(c), "swrt_kmap_series_record");
+    return;
+  }
+  if (!strcmp(cmd, "kmap_series_record_history")) {  // (first, count): 0-based history frames
+    need(na, 3, cmd);
+    check(c, swrt_kmap_series_record_history(c, (int64_t)scalar(a[1]), (int64_t)scalar(a[2])),
+          "swrt_kmap_series_record_history");
+    return;
+  }
+  if (!strcmp(cmd, "kmap_series_frames")) {
+    plhs[0] = mxCreateDoubleScalar((double)swrt_kmap_series_frames(c));
+    return;
+  }
+  if (!strcmp(cmd, "kmap_series_get")) {  // -> planes m x m x frames (int64), stats 8 x frames (int64)
+    const int64_t nf = swrt_kmap_series_frames(c), m = swrt_kmap_series_cells(c);
+    const mwSize dims[3] = {(mwSize)m, (mwSize)m, (mwSize)nf}, sdims[2] = {8, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(3, dims, mxINT64_CLASS, mxREAL);
+    mxArray* stats = mxCreateNumericArray(2, sdims, mxINT64_CLASS, mxREAL);
+    if (nf > 0)
+      check(c, swrt_kmap_series_get(c, 0, nf, (int64_t*)mxGetInt64s(plhs[0]), (int64_t*)mxGetInt64s(stats)),
+            "swrt_kmap_series_get");
+    if (nlhs > 1) plhs[1] = stats; else mxDestroyArray(stats);
+    return;
+  }
+  if (!strcmp(cmd, "kmap_series_reset")) {
+    check(c, swrt_kmap_series_reset(c), "swrt_kmap_series_reset");
     return;
   }
   if (!strcmp(cmd, "track_begin")) {  // (ids): 0-based original packet indices, as doubles

@@ -99,6 +99,13 @@ SIGNATURES = {
     "swrt_map_series_cells": (_I, [_VP]),
     "swrt_map_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "swrt_map_series_reset": (_INT, [_VP]),
+    "swrt_kmap_series_begin": (_INT, [_VP, _D, _I, _INT]),
+    "swrt_kmap_series_record": (_INT, [_VP]),
+    "swrt_kmap_series_record_history": (_INT, [_VP, _I, _I]),
+    "swrt_kmap_series_frames": (_I, [_VP]),
+    "swrt_kmap_series_cells": (_I, [_VP]),
+    "swrt_kmap_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_kmap_series_reset": (_INT, [_VP]),
     "swrt_track_begin": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64), _I]),
     "swrt_track_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
     "swrt_track_record_history": (_INT, [_VP, _I, _I, _D, _D, _INT, _P, _D]),
@@ -179,6 +186,7 @@ DEBUG_ODE23_DENSE_REBIN = 15
 DEBUG_ODE23_DENSE_REBINS = 16
 DEBUG_MAP_TILED_FRAMES = 17
 DEBUG_MAP_STRAYS = 18
+DEBUG_KMAP_GLOBAL = 19
 
 _lib = None
 
@@ -614,6 +622,45 @@ class Context:
 
     def map_series_reset(self):
         self._chk(self._L.swrt_map_series_reset(self._h), "swrt_map_series_reset")
+
+    # ---- the wave-vector plane series (swrt_kmap_series_*: density over (k, l), moments) ----
+    def kmap_series_begin(self, K, m, frac_bits=16):
+        """Open a series of m x m count planes over [-K, K) x [-K, K) of the
+        (k, l) plane; moments quantised to 2^-frac_bits.  Empties the series."""
+        self._chk(self._L.swrt_kmap_series_begin(self._h, float(K), int(m), int(frac_bits)),
+                  "swrt_kmap_series_begin")
+
+    def kmap_series_record(self):
+        """Append the current packets' k-plane frame to the device-side series (queued; no host wait)."""
+        self._chk(self._L.swrt_kmap_series_record(self._h), "swrt_kmap_series_record")
+
+    def kmap_series_record_history(self, first, count):
+        """One k-plane frame per history frame [first, first + count) (queued; no host wait)."""
+        self._chk(self._L.swrt_kmap_series_record_history(self._h, int(first), int(count)),
+                  "swrt_kmap_series_record_history")
+
+    def kmap_series_frames(self):
+        return int(self._L.swrt_kmap_series_frames(self._h))
+
+    def kmap_series_cells(self):
+        return int(self._L.swrt_kmap_series_cells(self._h))
+
+    def kmap_series_get(self, first=0, count=None):
+        """Recorded frames [first, first + count) -> (planes (count, m, m)
+        int64, planes[t, i, j] the cell with k index i and l index j; stats
+        (count, 8) int64 [n, rejected, outside, sum q(k), sum q(l), sum q(k*k),
+        sum q(l*l), sum q(k*l)])."""
+        count = self.kmap_series_frames() - first if count is None else count
+        m = self.kmap_series_cells()
+        planes = np.zeros((max(count, 0), m, m), dtype=np.int64)
+        stats = np.zeros((max(count, 0), 8), dtype=np.int64)
+        i64 = ctypes.POINTER(ctypes.c_int64)
+        self._chk(self._L.swrt_kmap_series_get(self._h, int(first), int(count), planes.ctypes.data_as(i64),
+                                               stats.ctypes.data_as(i64)), "swrt_kmap_series_get")
+        return planes.transpose(0, 2, 1), stats  # (the device's planes are column-major)
+
+    def kmap_series_reset(self):
+        self._chk(self._L.swrt_kmap_series_reset(self._h), "swrt_kmap_series_reset")
 
     # ---- the track series (swrt_track_*: trajectories of chosen packets) ------
     def track_begin(self, ids):

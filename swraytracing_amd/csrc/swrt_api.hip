@@ -29,6 +29,7 @@
 #include "swrt_diag.hpp"
 #include "swrt_raydiag.hpp"
 #include "swrt_map.hpp"
+#include "swrt_kmap.hpp"
 #include "swrt_res.hpp"
 
 using namespace swrt;
@@ -1339,6 +1340,70 @@ int swrt_map_series_reset(swrt_ctx* c) {
   return SWRT_OK;
 }
 
+// ---- the wave-vector plane series (swrt_kmap.hpp, swrt_host_diag.hpp) ----
+int swrt_kmap_series_begin(swrt_ctx* c, double K, int64_t m, int frac_bits) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  if (!(K > 0.0) || !std::isfinite(K)) return fail(c, SWRT_ERR_ARG, "K must be positive and finite");
+  if (m < 1 || m > kKmapMaxCells) return fail(c, SWRT_ERR_ARG, "m must be 1..4096");
+  if (frac_bits < 0 || frac_bits > kKmapMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
+  if (c->n > kKmapMaxPackets) return fail(c, SWRT_ERR_ARG, "a k-plane frame takes at most 2^24 packets");
+  HIPCHK(c, hipSetDevice(c->device));
+  KmapSeriesState& ks = c->kmap;
+  HIPCHK_RC(series_release(c, ks.series));
+  ks.m = (int)m;
+  ks.frac_bits = frac_bits;
+  ks.K = K;
+  ks.s = (double)m / (2.0 * K);
+  ks.open = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_kmap_series_record(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(kmap_series_check(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(kmap_reserve_zeroed(c, 1));
+  return kmap_launch(c, c->pk.cur.k.get(), 0, 1);
+  GUARD_END(c)
+}
+
+int swrt_kmap_series_record_history(swrt_ctx* c, int64_t first, int64_t count) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(kmap_series_check(c));
+  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(kmap_reserve_zeroed(c, count));
+  for (int64_t i = 0; i < count; i += kKmapHistoryChunk) {
+    const int64_t nf = std::min<int64_t>(kKmapHistoryChunk, count - i);
+    HIPCHK_RC(kmap_launch(c, c->hist.b.get() + (first + i) * 2 * c->n, 2 * c->n, nf));
+  }
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int64_t swrt_kmap_series_frames(const swrt_ctx* c) { return c ? c->kmap.series.ext.frames() : -1; }
+
+int64_t swrt_kmap_series_cells(const swrt_ctx* c) { return c ? (c->kmap.open ? c->kmap.m : 0) : -1; }
+
+int swrt_kmap_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* plane_out, int64_t* stats8_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  return kmap_series_get(c, first, count, plane_out, stats8_out);
+  GUARD_END(c)
+}
+
+int swrt_kmap_series_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
+  c->kmap.series.ext.cleared();
+  return SWRT_OK;
+}
+
 // ---- the track series (swrt_track.hpp, swrt_host_diag.hpp) ----
 int swrt_track_begin(swrt_ctx* c, const int64_t* ids, int64_t m) {
   if (!c) return SWRT_ERR_ARG;
@@ -1495,6 +1560,10 @@ int swrt_debug_set(swrt_ctx* c, int key, int64_t value) {
       if (value < 0 || value > 1000000) return fail(c, SWRT_ERR_ARG, "ode23 run_at re-binning cadence out of range");
       c->o23.dense_rebin = value;
       return SWRT_OK;
+    case SWRT_DEBUG_KMAP_GLOBAL:
+      if (value < 0 || value > 3) return fail(c, SWRT_ERR_ARG, "k-plane path must be 0..3");
+      c->dbg.kmap_path = (int)value;
+      return SWRT_OK;
     case SWRT_DEBUG_QG_UPDATE_COLS:
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "QG update/column-pass fusion must be 0 or 1");
       if (c->qg.spec) return fail(c, SWRT_ERR_STATE, "a speculative QG step is pending (swrt_qg_resolve first)");
@@ -1532,6 +1601,7 @@ int swrt_debug_get(swrt_ctx* c, int key, int64_t* value_out) {
     case SWRT_DEBUG_ODE23_DENSE_REBIN: *value_out = c->o23.dense_rebin; return SWRT_OK;
     case SWRT_DEBUG_ODE23_DENSE_REBINS: *value_out = c->o23.dense_rebins; return SWRT_OK;
     case SWRT_DEBUG_MAP_TILED_FRAMES: *value_out = c->map.tiled_frames; return SWRT_OK;
+    case SWRT_DEBUG_KMAP_GLOBAL: *value_out = c->dbg.kmap_path; return SWRT_OK;
     case SWRT_DEBUG_MAP_STRAYS: {  // the device's counter: waits for the queued records
       unsigned long long v = 0;
       if (c->map.strays) {

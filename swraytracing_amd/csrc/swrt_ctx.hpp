@@ -21,6 +21,7 @@
 #include "swrt_spectral.hpp"
 #include "swrt_hazard.hpp"
 #include "swrt_map.hpp"
+#include "swrt_kmap.hpp"
 #include "swrt_ode23_ctl.hpp"
 #include "swrt_res.hpp"
 #include "swrt_packet_state.hpp"
@@ -353,6 +354,19 @@ inline int64_t map_series_min(size_t frame_bytes) {
   return std::min<int64_t>(4096, std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / frame_bytes)));
 }
 
+// the wave-vector plane series (swrt_kmap_series_*, swrt_kmap.hpp).  Buffers
+// of its own, as MapSeriesState's; a frame is self-contained (its n is in its
+// stats), so swrt_packets_set with another N keeps the series.
+struct KmapSeriesState {
+  bool open = false;        // swrt_kmap_series_begin was called
+  int m = 0;                // cells per side of the open series
+  int frac_bits = 0;
+  double K = 0.0;           // half-width of the plane
+  double s = 0.0;           // m / (2K)
+  Series<unsigned long long> series;  // recorded frames, m x m counts each, and their kKmapStats stats
+  size_t frame() const { return (size_t)m * m; }
+};
+
 // the track series (swrt_track_*, swrt_track.hpp): the trajectories of m chosen
 // packets.  Buffers of its own, as the other recorders'.  A frame's rows are
 // packets of one ensemble, so swrt_packets_set with another N closes it.
@@ -381,6 +395,7 @@ struct DebugKnobs {
   bool legacy_park = false;
   bool share_skew = false;  // test-only: the cycle-ending launch takes an uneven share (checker on only)
   int corrupt_count = 0;    // test-only: added to one tile count before the next scan (once)
+  int kmap_path = 0;        // SWRT_DEBUG_KMAP_GLOBAL: 0 by m; 1 global; 2 / 3 global with / without the wave merge
 };
 }  // namespace
 
@@ -447,6 +462,7 @@ struct swrt_ctx {
   RayDiagState rd;
   OmegaSeriesState om;
   MapSeriesState map;
+  KmapSeriesState kmap;
   TrackState trk;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an

@@ -1,10 +1,11 @@
-// swrt_host_diag.hpp — host side of the four device-side recorders: the ray
+// swrt_host_diag.hpp — host side of the five device-side recorders: the ray
 // diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp), the
-// map series (swrt_map.hpp) and the track series (swrt_track.hpp).  Each
-// appends frames to a Series of its state (swrt_ctx.hpp) without a host wait:
-// a reserve, the launches that write at the series' end, a commit.  The order
-// below (ray, spectrum, map, track) is the order their template kernels are
-// first named in, hence emitted in.
+// map series (swrt_map.hpp), the wave-vector plane series (swrt_kmap.hpp) and
+// the track series (swrt_track.hpp).  Each appends frames to a Series of its
+// state (swrt_ctx.hpp) without a host wait: a reserve, the launches that write
+// at the series' end, a commit.  The order below (ray, spectrum, map, k-plane,
+// track) is the order their template kernels are first named in, hence
+// emitted in.
 #pragma once
 #include <cmath>
 
@@ -14,6 +15,7 @@
 #include "swrt_diag.hpp"
 #include "swrt_raydiag.hpp"
 #include "swrt_map.hpp"
+#include "swrt_kmap.hpp"
 #include "swrt_track.hpp"
 
 namespace {
@@ -226,6 +228,73 @@ int map_tile_launch(swrt_ctx* c) {
   ms.series.ext.committed(1);
   ++ms.tiled_frames;
   return SWRT_OK;
+}
+
+// ---- the wave-vector plane series ----
+int kmap_series_check(swrt_ctx* c) {
+  if (!c->kmap.open) return fail(c, SWRT_ERR_STATE, "call swrt_kmap_series_begin first");
+  HIPCHK_RC(packets_check(c));
+  if (c->n > kKmapMaxPackets) return fail(c, SWRT_ERR_ARG, "a k-plane frame takes at most 2^24 packets");
+  return SWRT_OK;
+}
+
+// Room for `count` more frames, zeroed on the stream (planes and stats): the
+// launches that fill them only add.
+int kmap_reserve_zeroed(swrt_ctx* c, int64_t count) {
+  KmapSeriesState& ks = c->kmap;
+  const size_t fr = ks.frame();
+  HIPCHK_RC(series_reserve(c, ks.series, fr, kKmapStats, count, map_series_min(fr * sizeof(unsigned long long))));
+  HIPCHK(c, hipMemsetAsync(ks.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
+  HIPCHK(c, hipMemsetAsync(ks.series.end_b(kKmapStats), 0, sizeof(unsigned long long) * kKmapStats * count, c->stream));
+  return SWRT_OK;
+}
+
+// `count` frames from the series' end on: frame i from the packets' k at
+// k + i*stride (any order).  The LDS kernel while the plane fits a workgroup's
+// LDS, the global one beyond (or when SWRT_DEBUG_KMAP_GLOBAL says so).
+int kmap_launch(swrt_ctx* c, const double* k, int64_t stride, int64_t count) {
+  KmapSeriesState& ks = c->kmap;
+  KmapGeom g;
+  g.K = ks.K;
+  g.s = ks.s;
+  g.m = ks.m;
+  g.scale = std::ldexp(1.0, ks.frac_bits);
+  unsigned long long* planes = ks.series.end_a(ks.frame());
+  unsigned long long* stats = ks.series.end_b(kKmapStats);
+  const int path = c->dbg.kmap_path;
+  const dim3 block(kKmapThreads);
+  if (path == 0 && ks.m <= kKmapLdsCells) {
+    const int nblk = (int)std::min<int64_t>(kKmapLdsBlocks, nblocks(c->n, kKmapThreads));
+    hipLaunchKernelGGL(kmap_lds_kernel, dim3(nblk, (unsigned)count), block, 0, c->stream, k, c->n, stride, g, planes,
+                       stats);
+  } else {
+    const int nblk = (int)std::min<int64_t>(kKmapBlocks, nblocks(c->n, kKmapThreads));
+    const bool merge = path == 2 || (path != 3 && kKmapGlobalMerge);
+    hipLaunchKernelGGL(merge ? kmap_global_kernel<true> : kmap_global_kernel<false>, dim3(nblk, (unsigned)count), block,
+                       0, c->stream, k, c->n, stride, g, planes, stats);
+  }
+  HIPCHK(c, hipGetLastError());
+  ks.series.ext.committed(count);
+  return SWRT_OK;
+}
+
+// Frames [first, first + count) to the host, synchronously; either output may
+// be NULL, not both.
+int kmap_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* plane_out, int64_t* stats_out) {
+  const KmapSeriesState& ks = c->kmap;
+  HIPCHK_RC(frame_range_check(c, ks.series.ext, first, count, "frame range out of bounds"));
+  if (!plane_out && !stats_out) return fail(c, SWRT_ERR_ARG, "NULL buffer (plane_out and stats8_out)");
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t fr = ks.frame();
+  if (plane_out)
+    HIPCHK(c, hipMemcpyAsync(plane_out, ks.series.a.get() + fr * first, sizeof(int64_t) * fr * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  if (stats_out)
+    HIPCHK(c, hipMemcpyAsync(stats_out, ks.series.b.get() + (size_t)kKmapStats * first,
+                             sizeof(int64_t) * kKmapStats * count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return dev_err_check(c);
 }
 
 // ---- the track series ----

@@ -120,6 +120,48 @@ def map_fields(planes, frac_bits):
     return out
 
 
+def combine_kmaps(parts):
+    """The wave-vector plane series of an ensemble from its shards' series
+    (swrt_kmap_series_*).  ``parts``: a sequence of (planes, stats) pairs, one
+    per shard, planes (T, m, m) int64 and stats (T, 8) int64 [n, rejected,
+    outside, sum q(k), sum q(l), sum q(k*k), sum q(l*l), sum q(k*l)]: the
+    element-wise sum (integer, exact and order-free).  A shard without packets
+    stands as zeros."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no series to combine")
+    planes = np.stack([np.asarray(p, dtype=np.int64) for p, _ in parts])
+    stats = np.stack([np.asarray(s, dtype=np.int64) for _, s in parts])
+    if planes.ndim != 4 or planes.shape[2] != planes.shape[3] or stats.shape != planes.shape[:2] + (8,):
+        raise ValueError("every shard must give planes (T, m, m) and stats (T, 8) for the same T and m")
+    return planes.sum(axis=0), stats.sum(axis=0)
+
+
+def kmap_moments(stats, frac_bits):
+    """Moments of the wavevector from k-plane stats (..., 8) int64 as fp64:
+    ``n_used`` = n - rejected, ``mean`` (..., 2) the mean (k, l), ``cov``
+    (..., 2, 2) the covariance <(k - <k>)(k - <k>)^T> over the n_used packets;
+    mean and cov NaN where n_used is 0."""
+    stats = np.asarray(stats)
+    if stats.ndim < 1 or stats.shape[-1] != 8:
+        raise ValueError("stats must be (..., 8)")
+    if not 0 <= int(frac_bits) <= 32:
+        raise ValueError("frac_bits must be 0..32")
+    unit = 2.0 ** -int(frac_bits)
+    n_used = (stats[..., 0] - stats[..., 1]).astype(np.float64)
+    empty = n_used == 0
+    count = np.where(empty, 1.0, n_used)
+    m1 = stats[..., 3:5].astype(np.float64) * unit / count[..., None]
+    kk, ll, kl = (stats[..., 5 + q].astype(np.float64) * unit / count for q in range(3))
+    cov = np.empty(stats.shape[:-1] + (2, 2))
+    cov[..., 0, 0] = kk - m1[..., 0] * m1[..., 0]
+    cov[..., 1, 1] = ll - m1[..., 1] * m1[..., 1]
+    cov[..., 0, 1] = cov[..., 1, 0] = kl - m1[..., 0] * m1[..., 1]
+    m1[empty] = np.nan
+    cov[empty] = np.nan
+    return dict(n_used=n_used, mean=m1, cov=cov)
+
+
 def track_ids_array(ids, n_total):
     """``ids`` as a checked int64 array: a one-dimensional, non-empty sequence
     of distinct integers in 0..n_total-1 (ValueError otherwise)."""
@@ -718,6 +760,118 @@ class PacketEnsemble:
             for planes, stats in st["kept"]:
                 self._append_maps(directory, planes, stats)
             st["kept"] = []
+        return st["frames"]
+
+    def begin_kmap(self, K, m, frac_bits=16, directory=None):
+        """Open the series of m x m count planes over [-K, K) x [-K, K) of the
+        (k, l) plane and the wavevector moments of this run
+        (swrt_kmap_series_begin).  ``directory``: where record_kmap drains the
+        device series when it grows large (default: the drained frames wait in
+        host memory for write_kmaps)."""
+        K, m, frac_bits = float(K), int(m), int(frac_bits)
+        if not (K > 0 and math.isfinite(K)):
+            raise ValueError("k-plane half-width must be positive and finite")
+        if not 1 <= m <= 4096:
+            raise ValueError("k-plane cells must be 1..4096")
+        if not 0 <= frac_bits <= 32:
+            raise ValueError("k-plane frac_bits must be 0..32")
+        self._kmap = dict(K=K, m=m, frac_bits=frac_bits, directory=directory, frames=0, pending=0, kept=[])
+        if self.n > 0:
+            self.ctx.kmap_series_begin(K, m, frac_bits)
+
+    def record_kmap(self):
+        """Append this shard's k-plane frame at the current state to the
+        device-side series (queued, no host wait).  An empty shard records
+        nothing.  When the device series holds more than 256 MB it is drained
+        (get, combine, append, reset): a collective when sharded, at the same
+        frame on every rank."""
+        st = getattr(self, "_kmap", None)
+        if st is None:
+            raise SwrtError("record_kmap: call begin_kmap first")
+        st["frames"] += 1
+        st["pending"] += 1
+        if self.n > 0:
+            self.ctx.kmap_series_record()
+        if st["pending"] * 8 * (st["m"] * st["m"] + 8) > MAP_DRAIN_BYTES:
+            self._drain_kmaps()
+
+    def _drain_kmaps(self):
+        """The frames on the device, summed over the shards, to the files or
+        the host list of rank 0; the device series emptied."""
+        st = self._kmap
+        T, m = st["pending"], st["m"]
+        if T == 0:
+            return
+        if self.n > 0:
+            planes, stats = self.ctx.kmap_series_get(0, T)
+            self.ctx.kmap_series_reset()
+        else:
+            planes, stats = np.zeros((T, m, m), dtype=np.int64), np.zeros((T, 8), dtype=np.int64)
+        st["pending"] = 0
+        if self.world > 1:
+            import torch
+            import torch.distributed as dist
+
+            from .dist import _device_for
+            dev = _device_for(dist.get_backend())
+            summed = []
+            for a in (planes, stats):
+                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                dist.all_reduce(buf, op=dist.ReduceOp.SUM)  # (int64: exact, order-free)
+                summed.append(buf.cpu().numpy())
+            if self.rank != 0:
+                return
+            planes, stats = summed
+        if st["directory"] is None:
+            st["kept"].append((planes, stats))
+        else:
+            self._append_kmaps(st["directory"], planes, stats)
+
+    @staticmethod
+    def _append_kmaps(directory, planes, stats):
+        with open(os.path.join(directory, "kmap_n.bin"), "ab") as fn, \
+                open(os.path.join(directory, "kmap_stats.bin"), "ab") as fs:
+            for fr, s in zip(planes, stats):
+                fn.write(np.asarray(fr, dtype=np.int64).tobytes(order="F"))  # (cell (i, j) at i + m*j)
+                fs.write(np.asarray(s, dtype=np.int64).tobytes())
+
+    def kmap_series(self):
+        """(planes (T, m, m) int64, stats (T, 8) int64) of the ensemble's
+        frames still held (not yet drained into files): planes[t, i, j] the
+        cell with k index i and l index j.  Sharded: a collective; rank 0 gets
+        the sum of the shards' frames, the others None."""
+        st = getattr(self, "_kmap", None)
+        if st is None:
+            raise SwrtError("kmap_series: call begin_kmap first")
+        if st["directory"] is not None:
+            raise ValueError("kmap_series: begin_kmap drains into a directory (read its files)")
+        self._drain_kmaps()
+        if self.rank != 0:
+            return None
+        m = st["m"]
+        if not st["kept"]:
+            return np.zeros((0, m, m), dtype=np.int64), np.zeros((0, 8), dtype=np.int64)
+        return (np.concatenate([p for p, _ in st["kept"]]), np.concatenate([s for _, s in st["kept"]]))
+
+    def write_kmaps(self, directory):
+        """The run's k-plane series as raw native-endian files: kmap_n.bin
+        (int64, one m x m plane per frame, cell (i, j) at i + m*j, first index
+        k), kmap_stats.bin (8 int64 per frame: n, rejected, outside and the
+        five moment sums) and kmap_geom.bin (three doubles [K, m, frac_bits]).
+        Sharded: a collective; rank 0 writes.  Returns the frames recorded."""
+        st = getattr(self, "_kmap", None)
+        if st is None:
+            raise SwrtError("write_kmaps: call begin_kmap first")
+        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
+            raise ValueError("write_kmaps: begin_kmap drained into another directory")
+        self._drain_kmaps()
+        if self.rank == 0:
+            if st["directory"] is None:
+                for planes, stats in st["kept"]:
+                    self._append_kmaps(directory, planes, stats)
+                st["kept"] = []
+            with open(os.path.join(directory, "kmap_geom.bin"), "wb") as fh:
+                fh.write(np.array([st["K"], st["m"], st["frac_bits"]], dtype=np.float64).tobytes())
         return st["frames"]
 
     def begin_tracks(self, ids, directory=None):

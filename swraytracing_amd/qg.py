@@ -16,6 +16,7 @@ drivers built on them.
 from __future__ import annotations
 
 import math
+import numbers
 import os
 
 import numpy as np
@@ -232,16 +233,16 @@ def _fresh_outputs(out_dir, fresh):
         return
     for name in ("packet_x", "packet_k", "packet_time", "pv", "pv_time", "omega_hist", "omega_stats", "omega_edges",
                  "map_n", "map_omega", "map_k", "map_l", "map_stats", "track_x", "track_k", "track_diag", "track_time",
-                 "track_ids"):
+                 "track_ids", "kmap_n", "kmap_stats", "kmap_geom"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
 
 
-def _spectrum_args(spectrum_edges, packet_files):
+def _spectrum_args(spectrum_edges, packet_files, kmap_cells=None):
     """The drivers' ``spectrum_edges`` / ``packet_files`` checked before anything runs."""
     if spectrum_edges is None:
-        if not packet_files:
+        if not packet_files and kmap_cells is None:
             raise ValueError("packet_files=False without spectrum_edges: the run would write no packet output")
         return None
     edges = np.array(spectrum_edges, dtype=np.float64).ravel()
@@ -259,6 +260,38 @@ def _map_args(map_cells, map_frac_bits):
     if isinstance(map_frac_bits, bool) or int(map_frac_bits) != map_frac_bits or not 0 <= int(map_frac_bits) <= 32:
         raise ValueError("map_frac_bits must be an integer 0..32")
     return int(map_cells), int(map_frac_bits)
+
+
+def _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits, ring_radius=None):
+    """The drivers' ``kmap_cells`` / ``kmap_kmax`` / ``kmap_frac_bits`` checked
+    before anything runs: (K, m, frac_bits), or None without ``kmap_cells``.
+    ``kmap_kmax=None`` stands for four times ``ring_radius``, the radius of
+    the initial ring the driver computes."""
+    if kmap_cells is None:
+        return None
+
+    def real(v):
+        return isinstance(v, numbers.Real) and not isinstance(v, (bool, np.bool_))
+
+    def integer(v):
+        return real(v) and math.isfinite(v) and int(v) == v
+
+    if not integer(kmap_cells) or not 1 <= int(kmap_cells) <= 4096:
+        raise ValueError("kmap_cells must be an integer 1..4096")
+    if not integer(kmap_frac_bits) or not 0 <= int(kmap_frac_bits) <= 32:
+        raise ValueError("kmap_frac_bits must be an integer 0..32")
+    if kmap_kmax is None:
+        if ring_radius is None:
+            raise ValueError("kmap_kmax=None needs the initial ring radius")
+        kmap_kmax = 4.0 * float(ring_radius)
+    if not real(kmap_kmax) or not math.isfinite(kmap_kmax) or not kmap_kmax > 0:
+        raise ValueError("kmap_kmax must be a positive finite number")
+    return float(kmap_kmax), int(kmap_cells), int(kmap_frac_bits)
+
+
+def _ring_radius(near_inertial_factor, f, Cg):
+    """|k| of _packets' initial ring (qgsw_raytrace.m:56)."""
+    return math.sqrt((near_inertial_factor ** 2 - 1) * f ** 2 / Cg ** 2)
 
 
 def _track_args(track_ids, track_every, Npackets, default_every):
@@ -289,13 +322,15 @@ def _track_args(track_ids, track_every, Npackets, default_every):
     return ids, int(track_every)
 
 
-def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False):
-    """One packet frame: its spectrum and its map recorded on the device (queued, no host
-    wait) whether or not the frame itself is written."""
+def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False):
+    """One packet frame: its spectrum, its map and its k-plane recorded on the device
+    (queued, no host wait) whether or not the frame itself is written."""
     if spectrum:
         ens.record_spectrum()
     if maps:
         ens.record_map()
+    if kmaps:
+        ens.record_kmap()
     ens.write_frame(t, out_dir, packet_files)
 
 
@@ -546,7 +581,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                   out_dir="data", nsub=4, max_steps=None, seed=146, verbose=False, r_drag=0.1,
                   packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
                   pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None, packet_files=True,
-                  map_cells=None, map_frac_bits=20, track_ids=None, track_every=None):
+                  map_cells=None, map_frac_bits=20, track_ids=None, track_every=None,
+                  kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -584,10 +620,22 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     (m x 4: Omega, zeta, sigma, D of swrt_raydiag_sample at the packets' time;
     NaN in the first frame, written before any snapshot exists),
     track_time.bin and track_ids.bin; no other output changes.
+    ``kmap_cells`` (m, 1..4096): every packet frame's m x m count plane over
+    [-K, K) x [-K, K) of the (k, l) plane and the ensemble's wavevector
+    moments are recorded on the device (swrt_kmap_series_*; K = ``kmap_kmax``,
+    default four times the initial ring's radius; moments quantised to
+    2^-``kmap_frac_bits``) and written as kmap_n.bin (int64, m x m per frame,
+    cell (i, j) at i + m*j, first index k), kmap_stats.bin (8 int64 per frame:
+    n, rejected, outside, sum q(k), sum q(l), sum q(k*k), sum q(l*l),
+    sum q(k*l)) and kmap_geom.bin (three doubles K, m, frac_bits); the frames
+    line up with packet_time.bin, and ``packet_files=False`` is allowed with
+    ``kmap_cells`` alone.
     Returns a dict of run facts (dt, Nsteps, steps run, frames written,
-    final t, spectrum_frames, map_frames, track_frames)."""
-    spectrum_edges = _spectrum_args(spectrum_edges, packet_files)
+    final t, spectrum_frames, map_frames, track_frames, kmap_frames)."""
+    spectrum_edges = _spectrum_args(spectrum_edges, packet_files, kmap_cells)
     map_args = _map_args(map_cells, map_frac_bits)
+    kmap_args = _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits,
+                           _ring_radius(near_inertial_factor, f, Cg) if kmap_cells is not None else None)
     track_args = _track_args(track_ids, track_every, Npackets, 5)  # (5: packet_steps_per_save below)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
@@ -643,12 +691,15 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     maps = ens is not None and map_args is not None
     if maps:
         ens.begin_map(*map_args, directory=out_dir)
+    kmaps = ens is not None and kmap_args is not None
+    if kmaps:
+        ens.begin_kmap(*kmap_args, directory=out_dir)
     tracks = ens is not None and track_args is not None
     if tracks:
         ens.begin_tracks(track_args[0], directory=out_dir)
         ens.record_tracks(dt * (packet_step_start - 1), 0)  # (no snapshot yet: the flow columns are NaN)
     if ens is not None:
-        _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files, maps)
+        _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files, maps, kmaps)
     if rank == 0:
         write_field(model.q(), os.path.join(out_dir, "pv"))
         write_field(np.array([[t]]), os.path.join(out_dir, "pv_time"))
@@ -676,7 +727,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                 ens.record_tracks(t, 1)
             if (step - packet_step_start + 1) % packet_steps_per_save == 0:
                 group.flush()
-                _save_frame(ens, t, out_dir, spectrum, packet_files, maps)
+                _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps)
                 frames += 1
         else:
             have_cur = False
@@ -691,26 +742,29 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     spectrum_frames = ens.write_spectrum(out_dir) if spectrum else 0
     map_frames = ens.write_maps(out_dir) if maps else 0
     track_frames = ens.write_tracks(out_dir) if tracks else 0
+    kmap_frames = ens.write_kmaps(out_dir) if kmaps else 0
     ctx.synchronize()
     ctx.set_timing(timing)
     log.finish()
     log.close()
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
-                track_frames=track_frames)
+                track_frames=track_frames, kmap_frames=kmap_frames)
 
 
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
                         out_dir="data", nsub=5, max_steps=None, seed=5, verbose=False,
                         packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
                         pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None,
-                        packet_files=True, map_cells=None, map_frac_bits=20, track_ids=None, track_every=None):
+                        packet_files=True, map_cells=None, map_frac_bits=20, track_ids=None, track_every=None,
+                        kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
     pv.bin holds the initial nx x nx x 2 frame only, as in the reference.
     ``packet_intervals``, ``integrator``, ``fresh``, ``spectrum_edges``,
-    ``packet_files``, ``map_cells``, ``map_frac_bits``, ``track_ids``,
+    ``packet_files``, ``map_cells``, ``map_frac_bits``, ``kmap_cells``,
+    ``kmap_kmax``, ``kmap_frac_bits``, ``track_ids``,
     ``track_every`` (default: this driver's packet cadence, 25): as in
     :func:`qgsw_raytrace`.
 
@@ -723,8 +777,10 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     Both write the single-process files byte for byte.  ``link_buffers``: the
     owner link's buffers ("auto": on the device with nccl, on the host with
     gloo; "device" / "host" to force one)."""
-    spectrum_edges = _spectrum_args(spectrum_edges, packet_files)
+    spectrum_edges = _spectrum_args(spectrum_edges, packet_files, kmap_cells)
     map_args = _map_args(map_cells, map_frac_bits)
+    kmap_args = _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits,
+                           _ring_radius(near_inertial_factor, f, Cg) if kmap_cells is not None else None)
     track_args = _track_args(track_ids, track_every, Npackets, 25)  # (25: packet_steps_per_save below)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
@@ -771,12 +827,15 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     maps = ens is not None and map_args is not None
     if maps:
         ens.begin_map(*map_args, directory=out_dir)
+    kmaps = ens is not None and kmap_args is not None
+    if kmaps:
+        ens.begin_kmap(*kmap_args, directory=out_dir)
     tracks = ens is not None and track_args is not None
     if tracks:
         ens.begin_tracks(track_args[0], directory=out_dir)
         ens.record_tracks(dt * (packet_step_start - 1), 0)  # (no snapshot yet: the flow columns are NaN)
     if ens is not None:
-        _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files, maps)
+        _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files, maps, kmaps)
     if rank == 0:
         write_field(model.q(), os.path.join(out_dir, "pv"))
         write_field(np.array([[t]]), os.path.join(out_dir, "pv_time"))
@@ -802,7 +861,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
             ens.record_tracks(loop.t, 1)
         if active and (loop.steps - packet_step_start + 1) % packet_steps_per_save == 0:
             loop.flush()
-            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps)
+            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps)
             frames += 1
         log.progress(loop.steps, Nsteps)
     loop.flush()
@@ -812,6 +871,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     spectrum_frames = ens.write_spectrum(out_dir) if spectrum else 0
     map_frames = ens.write_maps(out_dir) if maps else 0
     track_frames = ens.write_tracks(out_dir) if tracks else 0
+    kmap_frames = ens.write_kmaps(out_dir) if kmaps else 0
     ctx.synchronize()
     ctx.set_timing(timing)
     log.finish()
@@ -820,4 +880,4 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     U0 = getattr(loop, "U0", U0)  # (a receiving rank never sees the owner's U0)
     return dict(dt=dt, dts=dts, Nsteps=Nsteps, steps=step, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
-                track_frames=track_frames)
+                track_frames=track_frames, kmap_frames=kmap_frames)
