@@ -538,6 +538,87 @@ int swrt_track_get(swrt_ctx* ctx, int64_t first, int64_t count, double* frames_o
 /* Empty the series; the ids stay. */
 int swrt_track_reset(swrt_ctx* ctx);
 
+/* The background flow's shell spectra, kept on the device: what the
+ * reference's analysis computes from a PV frame (scratch/energy_spectrum.m:3-13:
+ * psik = -qk./(K_d2 + K2), KE = K2.*|psik|^2 summed over the shells
+ * (j - 1/2)^2 <= K^2 < (j + 1/2)^2; rsw/isospectrum.m:14-21 writes the rule
+ * floor(K + .5) == j), from one layer's spectral PV, at the packet frames'
+ * times and without a download.  The one series on the PDE side: its work runs
+ * on the QG stream (the context's stream when swrt_qg_set_stream(ctx, 0)).
+ *
+ * Geometry.  nx is a power of two, kmax = nx/2 - 1; the half plane is
+ * kx in [-kmax, kmax], ky in [0, kmax]; k_scale = 2*pi/L as a double (the
+ * one-layer model passes exactly 1); K_d2 >= 0.
+ * Shell.  The shell of (kx, ky) is the integer j >= 0 with
+ * (2j-1)^2 <= 4(kx^2 + ky^2) < (2j+1)^2, and j = 0 for the mean mode alone:
+ * floor(K + .5) on index wavenumbers, in integers.  nshell =
+ * shell(kmax, kmax) + 1 (11 at nx = 16, 45 at 64, 362 at 512): the corner
+ * shells beyond kmax are kept.
+ * Modes.  Those with ky = 0 and kx < 0 are skipped, whatever they hold
+ * (fulspec.m:16 overwrites them).  The mean mode has weight w = 0.5, every
+ * other w = 1: a shell sum is half the full-plane sum.
+ * Per mode, every operation one IEEE double operation, never contracted, in
+ * the order of grid_U's inversion:
+ *   kxs = (double)kx * k_scale;  kys = (double)ky * k_scale
+ *   K2  = kxs*kxs + kys*kys
+ *   den = K_d2 + K2
+ *   pr  = -qr/den;  pi = -qi/den          (both 0 when den == 0)
+ *   a   = pr*pr + pi*pi
+ *   E   = w * (K2 * a)
+ *   Z   = w * ((K2*K2) * a)
+ *   Q   = w * (qr*qr + qi*qi)
+ * Summation.  For each quantity and shell there are nx slots: slot kx + kmax
+ * holds the sum of row kx's modes in that shell, in ascending ky from +0.0;
+ * slots 2kmax+1 .. nx-1 are +0.0.  The slots are folded by halving: for
+ * h = nx/2, nx/4, ..., 1, P[i] = P[i] + P[i+h] for i < h; the shell's value
+ * is P[0].  A frame is
+ *   3 x nshell doubles [E(0..J), Z(0..J), Q(0..J)];
+ *   four stats doubles [t, sum E, sum Z, sum Q], each total summed in
+ *   ascending j from +0.0.
+ * The order is defined on (kx, ky), not on memory: a frame is a function of
+ * the values of qk alone.  sum E = mean(u^2 + v^2)/2 of grid_U's velocity
+ * without the shear offset, sum Z = mean((v_x - u_y)^2)/2, sum Q =
+ * mean(q^2)/2 with q = k2g(qk), the mean included.  The two-layer PDE's own
+ * inversion (the B matrix; barotropic and baroclinic energies) is not
+ * computed: every layer goes through the one-layer inversion above, which is
+ * what the packets' snapshots use. */
+
+/* Open a series and empty it.  SWRT_ERR_ARG with a message unless nx is a
+ * power of two in 8..4096 (swrt_qg_init's range), k_scale positive and finite,
+ * K_d2 finite and >= 0.  Waits for the series' stream. */
+int swrt_flow_spectrum_begin(swrt_ctx* ctx, int64_t nx, double k_scale, double K_d2);
+
+/* Append the frame of layer `layer` of the QG state's committed current qk
+ * (swrt_qg_export's view: a pending speculative step is neither waited for
+ * nor included), t the state's model time: queued on the QG stream behind the
+ * step that made that qk; the host does not wait and no packet launch does.
+ * One workgroup per shell gathers the shell's modes, each read once; nothing
+ * is added through memory.  Capacity: 64 MiB of frames (at least one, at most
+ * 4096), doubled when full; only a growing call may wait for the stream, and
+ * a failed allocation is an error return.  SWRT_ERR_STATE before
+ * swrt_flow_spectrum_begin, before swrt_qg_init, or when the state's nx
+ * differs from the series'; SWRT_ERR_ARG for a layer the state does not have. */
+int swrt_flow_spectrum_record_qg(swrt_ctx* ctx, int layer);
+
+/* The same from a host half plane in swrt_set_field_qk's layout (column-major
+ * (2kmax+1) x (kmax+1), kx fastest, interleaved complex), stamped with t: the
+ * bits swrt_flow_spectrum_record_qg gives for the same values.  Returns once
+ * the plane is copied (qk_interleaved is free); the frame itself is queued.
+ * SWRT_ERR_STATE before begin or when nx differs from the series'. */
+int swrt_flow_spectrum_record_qk(swrt_ctx* ctx, const double* qk_interleaved, int64_t nx, double t);
+
+/* Frames recorded since begin or the last reset; nshell of the open series, 0 if none. */
+int64_t swrt_flow_spectrum_frames(const swrt_ctx* ctx);
+int64_t swrt_flow_spectrum_shells(const swrt_ctx* ctx);
+
+/* Frames [first, first + count): spectra_out count x 3 x nshell and stats4_out
+ * count x 4, frame-major.  Either may be NULL, not both (SWRT_ERR_ARG).  Waits
+ * for the series' stream up to these frames, never for the packet streams. */
+int swrt_flow_spectrum_get(swrt_ctx* ctx, int64_t first, int64_t count, double* spectra_out, double* stats4_out);
+
+/* Empty the series; nx, k_scale and K_d2 stay. */
+int swrt_flow_spectrum_reset(swrt_ctx* ctx);
+
 /* ---------------------------------------------------------------------------
  * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
  * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)

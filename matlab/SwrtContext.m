@@ -153,5 +153,44 @@ classdef SwrtContext < handle
         function track_reset(obj)
             swrt_mex('track_reset', obj.id());
         end
+
+        % The background flow's shell spectra on the device (what
+        % scratch/energy_spectrum.m:3-13 computes from a PV frame): per frame
+        % nshell x 3 [E Z Q] (kinetic energy, relative-vorticity enstrophy, PV
+        % variance per shell j = floor(K + .5), each half the domain mean in
+        % total) and four stats [t; sum E; sum Z; sum Q].
+        function flow_spectrum_begin(obj, nx, k_scale, K_d2)
+            % k_scale = 2*pi/L (exactly 1 for the one-layer model)
+            swrt_mex('flow_spectrum_begin', obj.id(), nx, k_scale, K_d2);
+        end
+
+        function flow_spectrum_record_qg(obj, layer)
+            % the QG state's committed qk, layer 0-based
+            if nargin < 2, layer = 0; end
+            swrt_mex('flow_spectrum_record_qg', obj.id(), layer);
+        end
+
+        function flow_spectrum_record_qk(obj, qk, t)
+            % qk: complex (2kmax+1) x (kmax+1), g2k's half plane
+            if nargin < 3, t = 0; end
+            swrt_mex('flow_spectrum_record_qk', obj.id(), complex(qk), t);
+        end
+
+        function n = flow_spectrum_frames(obj)
+            n = swrt_mex('flow_spectrum_frames', obj.id());
+        end
+
+        function n = flow_spectrum_shells(obj)
+            n = swrt_mex('flow_spectrum_shells', obj.id());
+        end
+
+        function [spectra, stats] = flow_spectrum_get(obj)
+            % spectra: nshell x 3 x frames; stats: 4 x frames
+            [spectra, stats] = swrt_mex('flow_spectrum_get', obj.id());
+        end
+
+        function flow_spectrum_reset(obj)
+            swrt_mex('flow_spectrum_reset', obj.id());
+        end
     end
 end

@@ -60,6 +60,11 @@
 //   swrt_mex('track_record_history', h, first, count, f, gH, nslots, alphas, bump)   % alphas [] when nslots < 2
 //   frames = swrt_mex('track_get', h)                         % m x 8 x frames [x y k l Omega zeta sigma D]
 //   swrt_mex('track_reset', h)
+//   swrt_mex('flow_spectrum_begin', h, nx, k_scale, K_d2)     % shell spectra of the background flow on the device
+//   swrt_mex('flow_spectrum_record_qg', h[, layer]);  swrt_mex('flow_spectrum_record_qk', h, qk, t)
+//   n = swrt_mex('flow_spectrum_frames', h);  ns = swrt_mex('flow_spectrum_shells', h)
+//   [spectra, stats] = swrt_mex('flow_spectrum_get', h)       % nshell x 3 x frames [E Z Q], 4 x frames [t; sums]
+//   swrt_mex('flow_spectrum_reset', h)
 #include <cstring>
 #include <string>
 #include <vector>
@@ -589,6 +594,46 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   if (!strcmp(cmd, "track_reset")) {
     check(c, swrt_track_reset(c), "swrt_track_reset");
+    return;
+  }
+  if (!strcmp(cmd, "flow_spectrum_begin")) {  // (nx, k_scale, K_d2)
+    need(na, 4, cmd);
+    check(c, swrt_flow_spectrum_begin(c, (int64_t)scalar(a[1]), scalar(a[2]), scalar(a[3])),
+          "swrt_flow_spectrum_begin");
+    return;
+  }
+  if (!strcmp(cmd, "flow_spectrum_record_qg")) {  // ([layer = 0]): 0-based layer of the QG state
+    check(c, swrt_flow_spectrum_record_qg(c, na > 1 ? (int)scalar(a[1]) : 0), "swrt_flow_spectrum_record_qg");
+    return;
+  }
+  if (!strcmp(cmd, "flow_spectrum_record_qk")) {  // (qk complex (2kmax+1) x (kmax+1), t)
+    need(na, 3, cmd);
+    const double* qk = complexes(a[1], "qk");
+    const int64_t nx = (int64_t)mxGetM(a[1]) + 1;
+    if ((int64_t)mxGetN(a[1]) * 2 != nx) mexErrMsgIdAndTxt("swrt:arg", "qk must be (2kmax+1) x (kmax+1)");
+    check(c, swrt_flow_spectrum_record_qk(c, qk, nx, scalar(a[2])), "swrt_flow_spectrum_record_qk");
+    return;
+  }
+  if (!strcmp(cmd, "flow_spectrum_frames")) {
+    plhs[0] = mxCreateDoubleScalar((double)swrt_flow_spectrum_frames(c));
+    return;
+  }
+  if (!strcmp(cmd, "flow_spectrum_shells")) {
+    plhs[0] = mxCreateDoubleScalar((double)swrt_flow_spectrum_shells(c));
+    return;
+  }
+  if (!strcmp(cmd, "flow_spectrum_get")) {  // -> spectra nshell x 3 x frames [E Z Q], stats 4 x frames [t; sums]
+    const int64_t nf = swrt_flow_spectrum_frames(c), ns = swrt_flow_spectrum_shells(c);
+    const mwSize dims[3] = {(mwSize)ns, 3, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    mxArray* stats = mxCreateDoubleMatrix(4, (mwSize)nf, mxREAL);
+    if (nf > 0)
+      check(c, swrt_flow_spectrum_get(c, 0, nf, mxGetDoubles(plhs[0]), mxGetDoubles(stats)), "swrt_flow_spectrum_get");
+    if (nlhs > 1) plhs[1] = stats; else mxDestroyArray(stats);
+    return;
+  }
+  if (!strcmp(cmd, "flow_spectrum_reset")) {
+    check(c, swrt_flow_spectrum_reset(c), "swrt_flow_spectrum_reset");
     return;
   }
   mexErrMsgIdAndTxt("swrt:arg", "unknown command '%s'", cmd);

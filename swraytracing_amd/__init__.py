@@ -11,7 +11,8 @@ from .integrate import (PacketEnsemble, combine_frames, combine_kmaps, combine_m
                         ode23_packets, ode23_trajectory,
                         ode_symplectic, raytrace_sw, raytrace_xka, rsw_background, step_packet_xka)
 from .io import read_field, write_field
-from .qg import QGModel, ReceiverLoop, TwoLayerLoop, qg2layersw_raytrace, qgsw_raytrace
+from .qg import (QGModel, ReceiverLoop, TwoLayerLoop, flow_shells, flow_spectrum_fields, qg2layersw_raytrace,
+                 qgsw_raytrace)
 from .stored import read_frame, trace_stored
 from .scheme import (BUMP_QG, BUMP_SW, DifferenceScheme, FourierScheme, RaytracingScheme, SnapshotPairScheme,
                      SpectralScheme, g2k, grid_U, interpolate, interpolate_U, k2g)
@@ -22,7 +23,7 @@ __all__ = [
     "energy_spectrum", "kmap_moments", "map_fields", "ode23_packets", "ode23_trajectory",
     "ode_symplectic",
     "raytrace_sw", "raytrace_xka", "rsw_background", "step_packet_xka",
-    "read_field", "write_field", "QGModel", "ReceiverLoop", "TwoLayerLoop", "qgsw_raytrace", "qg2layersw_raytrace",
+    "flow_shells", "flow_spectrum_fields", "read_field", "write_field", "QGModel", "ReceiverLoop", "TwoLayerLoop", "qgsw_raytrace", "qg2layersw_raytrace",
     "BUMP_QG", "BUMP_SW", "DifferenceScheme", "FourierScheme", "RaytracingScheme", "SnapshotPairScheme",
     "SpectralScheme", "g2k", "grid_U", "interpolate", "interpolate_U", "k2g", "read_frame", "trace_stored",
 ]

@@ -114,6 +114,13 @@ SIGNATURES = {
     "swrt_track_ids": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64)]),
     "swrt_track_get": (_INT, [_VP, _I, _I, _P]),
     "swrt_track_reset": (_INT, [_VP]),
+    "swrt_flow_spectrum_begin": (_INT, [_VP, _I, _D, _D]),
+    "swrt_flow_spectrum_record_qg": (_INT, [_VP, _INT]),
+    "swrt_flow_spectrum_record_qk": (_INT, [_VP, _P, _I, _D]),
+    "swrt_flow_spectrum_frames": (_I, [_VP]),
+    "swrt_flow_spectrum_shells": (_I, [_VP]),
+    "swrt_flow_spectrum_get": (_INT, [_VP, _I, _I, _P, _P]),
+    "swrt_flow_spectrum_reset": (_INT, [_VP]),
     "swrt_raydiag_mark": (_INT, [_VP, _D, _D, _INT, _D, _D]),
     "swrt_raydiag_sample": (_INT, [_VP, _D, _D, _INT, _D, _D, _P, _P]),
     "swrt_raydiag_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
@@ -713,6 +720,50 @@ class Context:
 
     def track_reset(self):
         self._chk(self._L.swrt_track_reset(self._h), "swrt_track_reset")
+
+    # ---- the flow spectrum series (swrt_flow_spectrum_*: shell spectra of the background flow) ----
+    def flow_spectrum_begin(self, nx, k_scale=1.0, K_d2=0.0):
+        """Open a series of shell spectra of nx^2 spectral PV half planes
+        (k_scale = 2*pi/L; exactly 1 for the one-layer model).  Empties the series."""
+        self._chk(self._L.swrt_flow_spectrum_begin(self._h, int(nx), float(k_scale), float(K_d2)),
+                  "swrt_flow_spectrum_begin")
+
+    def flow_spectrum_record_qg(self, layer=0):
+        """Append the frame of the QG state's committed qk, layer ``layer``
+        (queued on the QG stream; no host wait)."""
+        self._chk(self._L.swrt_flow_spectrum_record_qg(self._h, int(layer)), "swrt_flow_spectrum_record_qg")
+
+    def flow_spectrum_record_qk(self, qk, t=0.0):
+        """Append the frame of a host half plane ``qk`` ((2kmax+1, kmax+1)
+        complex, set_field_qk's layout), stamped with ``t``."""
+        qk = np.asarray(qk, dtype=np.complex128)
+        nx = qk.shape[0] + 1
+        if qk.ndim != 2 or qk.shape != (nx - 1, nx // 2):
+            raise ValueError("qk must be a (2kmax+1, kmax+1) half plane")
+        buf = _f64(np.asfortranarray(qk).ravel(order="F").view(np.float64))
+        self._chk(self._L.swrt_flow_spectrum_record_qk(self._h, _p(buf), nx, float(t)),
+                  "swrt_flow_spectrum_record_qk")
+
+    def flow_spectrum_frames(self):
+        return int(self._L.swrt_flow_spectrum_frames(self._h))
+
+    def flow_spectrum_shells(self):
+        return int(self._L.swrt_flow_spectrum_shells(self._h))
+
+    def flow_spectrum_get(self, first=0, count=None, spectra=True, stats=True):
+        """Recorded frames [first, first + count) -> (spectra (count, 3, nshell)
+        float64 [E, Z, Q] per shell; stats (count, 4) [t, sum E, sum Z, sum Q]);
+        None in place of an output not asked for."""
+        count = self.flow_spectrum_frames() - first if count is None else count
+        ns = self.flow_spectrum_shells()
+        sp = np.zeros((max(count, 0), 3, ns)) if spectra else None
+        st = np.zeros((max(count, 0), 4)) if stats else None
+        self._chk(self._L.swrt_flow_spectrum_get(self._h, int(first), int(count), _p(sp), _p(st)),
+                  "swrt_flow_spectrum_get")
+        return sp, st
+
+    def flow_spectrum_reset(self):
+        self._chk(self._L.swrt_flow_spectrum_reset(self._h), "swrt_flow_spectrum_reset")
 
     # ---- the invariant and the flow along the rays (swrt_raydiag_*) ----------
     def raydiag_mark(self, f, gH, nslots=1, alpha=0.0, bump=1e-13):

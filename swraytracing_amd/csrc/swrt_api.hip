@@ -1493,6 +1493,80 @@ int swrt_track_reset(swrt_ctx* c) {
   return SWRT_OK;
 }
 
+// ---- the flow spectrum series (swrt_flowspec.hpp, swrt_host_diag.hpp) ----
+// Every call runs on the QG stream (OnQGStream) and none touches the packets.
+int swrt_flow_spectrum_begin(swrt_ctx* c, int64_t nx, double k_scale, double K_d2) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN_KEEP_CHAIN
+  OnQGStream on_qg(c);
+  if (nx < 8 || nx > 4096 || !is_pow2(nx)) return fail(c, SWRT_ERR_ARG, "nx must be a power of two, 8..4096");
+  if (!(k_scale > 0.0) || !std::isfinite(k_scale)) return fail(c, SWRT_ERR_ARG, "k_scale must be positive and finite");
+  if (!(K_d2 >= 0.0) || !std::isfinite(K_d2)) return fail(c, SWRT_ERR_ARG, "K_d2 must be finite and not negative");
+  HIPCHK(c, hipSetDevice(c->device));
+  FlowSpecState& fs = c->flow;
+  HIPCHK_RC(series_release(c, fs.series));  // (waits: a queued record_qk may still read the staged plane)
+  fs.stage.reset();
+  fs.nx = (int)nx;
+  fs.nshell = flow_shells((int)nx);
+  fs.k_scale = k_scale;
+  fs.K_d2 = K_d2;
+  fs.open = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_flow_spectrum_record_qg(swrt_ctx* c, int layer) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN_KEEP_CHAIN
+  OnQGStream on_qg(c);
+  const QGState& q = c->qg;
+  if (!c->flow.open) return fail(c, SWRT_ERR_STATE, "call swrt_flow_spectrum_begin first");
+  if (!q.init) return fail(c, SWRT_ERR_STATE, "swrt_qg_init not called");
+  if (q.g.n != c->flow.nx) return fail(c, SWRT_ERR_STATE, "the QG state's nx differs from the series'");
+  if (layer < 0 || layer >= q.g.nl) return fail(c, SWRT_ERR_ARG, "layer out of range");
+  HIPCHK(c, hipSetDevice(c->device));
+  // (a pending speculative step writes the spare buffers only, as for swrt_qg_export)
+  const int kmax = q.g.n / 2 - 1;
+  return flow_spectrum_record_frame(c, q.qk.get() + layer * q.nhalf, kmax + 1, 1, q.t);
+  GUARD_END(c)
+}
+
+int swrt_flow_spectrum_record_qk(swrt_ctx* c, const double* qk_interleaved, int64_t nx, double t) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN_KEEP_CHAIN
+  OnQGStream on_qg(c);
+  FlowSpecState& fs = c->flow;
+  if (!fs.open) return fail(c, SWRT_ERR_STATE, "call swrt_flow_spectrum_begin first");
+  if (nx != fs.nx) return fail(c, SWRT_ERR_STATE, "nx differs from the series'");
+  if (!qk_interleaved) return fail(c, SWRT_ERR_ARG, "NULL buffer (qk_interleaved)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int kmax = fs.nx / 2 - 1;
+  const size_t nhalf = (size_t)(2 * kmax + 1) * (kmax + 1);
+  if (!fs.stage) HIPCHK(c, fs.stage.alloc(nhalf));
+  HIPCHK(c, hipMemcpyAsync(fs.stage.get(), qk_interleaved, sizeof(double2) * nhalf, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's host buffer is free on return
+  return flow_spectrum_record_frame(c, fs.stage.get(), 1, 2 * kmax + 1, t);
+  GUARD_END(c)
+}
+
+int64_t swrt_flow_spectrum_frames(const swrt_ctx* c) { return c ? c->flow.series.ext.frames() : -1; }
+
+int64_t swrt_flow_spectrum_shells(const swrt_ctx* c) { return c ? (c->flow.open ? c->flow.nshell : 0) : -1; }
+
+int swrt_flow_spectrum_get(swrt_ctx* c, int64_t first, int64_t count, double* spectra_out, double* stats4_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN_KEEP_CHAIN
+  OnQGStream on_qg(c);
+  return flow_spectrum_get(c, first, count, spectra_out, stats4_out);
+  GUARD_END(c)
+}
+
+int swrt_flow_spectrum_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  c->flow.series.ext.cleared();
+  return SWRT_OK;
+}
+
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN

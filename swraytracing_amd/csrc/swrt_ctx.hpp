@@ -22,6 +22,7 @@
 #include "swrt_hazard.hpp"
 #include "swrt_map.hpp"
 #include "swrt_kmap.hpp"
+#include "swrt_flowspec.hpp"
 #include "swrt_ode23_ctl.hpp"
 #include "swrt_res.hpp"
 #include "swrt_packet_state.hpp"
@@ -386,6 +387,20 @@ struct TrackState {
   }
 };
 
+// the flow spectrum series (swrt_flow_spectrum_*, swrt_flowspec.hpp): the
+// background flow's shell spectra, the one recorder on the PDE side.  Buffers
+// of its own, as the other recorders'; its work runs on the QG stream
+// (OnQGStream), behind the step that made the qk it reads.
+struct FlowSpecState {
+  bool open = false;        // swrt_flow_spectrum_begin was called
+  int nx = 0;               // grid of the open series
+  int nshell = 0;
+  double k_scale = 0.0, K_d2 = 0.0;
+  DevBuf<double2> stage;    // swrt_flow_spectrum_record_qk's half plane on the device
+  Series<double> series;    // recorded frames, 3 x nshell doubles each, and their kFlowSpecStats stats
+  size_t frame() const { return (size_t)3 * nshell; }
+};
+
 // debug knobs (swrt_debug_set): a spin kernel queued on every extra packet
 // stream before each of its part launches (adversarial overlap of consecutive
 // calls), and the pre-third-buffer ordering after a source-gather sort
@@ -464,6 +479,7 @@ struct swrt_ctx {
   MapSeriesState map;
   KmapSeriesState kmap;
   TrackState trk;
+  FlowSpecState flow;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an
   // event marker, ~7 us of idle on each stream).  Only consecutive split
@@ -696,8 +712,9 @@ void hz_api(swrt_ctx* c) {
 
 // The host synchronised the packet stream after join_b: everything queued on
 // any packet stream before has completed.
+// (A wait for the QG stream, the flow spectrum series', says nothing about them.)
 void hz_synced(swrt_ctx* c) {
-  if (c->hz.on) c->hz.sync(0);
+  if (c->hz.on && c->stream == c->stream0.get()) c->hz.sync(0);
 }
 
 // After a host synchronisation with the packet stream: an error the device

@@ -1,10 +1,11 @@
-// swrt_host_diag.hpp — host side of the five device-side recorders: the ray
+// swrt_host_diag.hpp — host side of the six device-side recorders: the ray
 // diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp), the
-// map series (swrt_map.hpp), the wave-vector plane series (swrt_kmap.hpp) and
-// the track series (swrt_track.hpp).  Each appends frames to a Series of its
+// map series (swrt_map.hpp), the wave-vector plane series (swrt_kmap.hpp),
+// the track series (swrt_track.hpp) and the flow spectrum series
+// (swrt_flowspec.hpp).  Each appends frames to a Series of its
 // state (swrt_ctx.hpp) without a host wait: a reserve, the launches that write
 // at the series' end, a commit.  The order below (ray, spectrum, map, k-plane,
-// track) is the order their template kernels are first named in, hence
+// track, flow) is the order their template kernels are first named in, hence
 // emitted in.
 #pragma once
 #include <cmath>
@@ -17,6 +18,7 @@
 #include "swrt_map.hpp"
 #include "swrt_kmap.hpp"
 #include "swrt_track.hpp"
+#include "swrt_flowspec.hpp"
 
 namespace {
 
@@ -337,6 +339,51 @@ int track_record_frame(swrt_ctx* c, double f, double gH, int nslots, double alph
   hipLaunchKernelGGL(hist_x ? track_kernel<true> : track_kernel<false>, grid, block, 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   tr.series.ext.committed(1);
+  return SWRT_OK;
+}
+
+// ---- the flow spectrum series ----
+// One frame at the series' end on the context's current stream (the QG
+// stream inside OnQGStream) from the half plane at `qk`, mode (kx, ky) at
+// (kx + kmax)*skx + ky*sky, stamped with the time t.
+int flow_spectrum_record_frame(swrt_ctx* c, const double2* qk, int64_t skx, int64_t sky, double t) {
+  FlowSpecState& fs = c->flow;
+  HIPCHK_RC(series_reserve(c, fs.series, fs.frame(), kFlowSpecStats, 1, map_series_min(fs.frame() * sizeof(double))));
+  FlowSpecArgs a;
+  a.qk = qk;
+  a.skx = skx;
+  a.sky = sky;
+  a.nx = fs.nx;
+  a.nshell = fs.nshell;
+  a.k_scale = fs.k_scale;
+  a.K_d2 = fs.K_d2;
+  a.frame = fs.series.end_a(fs.frame());
+  hipLaunchKernelGGL(flow_spectrum_kernel, dim3((unsigned)fs.nshell), dim3(kFlowSpecThreads),
+                     sizeof(double) * 3 * (size_t)(fs.nx / 2), c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(flow_spectrum_totals_kernel, dim3(1), dim3(kFlowSpecThreads), 0, c->stream, a.frame, fs.nshell, t,
+                     fs.series.end_b(kFlowSpecStats));
+  HIPCHK(c, hipGetLastError());
+  fs.series.ext.committed(1);
+  return SWRT_OK;
+}
+
+// Frames [first, first + count) to the host, synchronously; either output may
+// be NULL, not both.
+int flow_spectrum_get(swrt_ctx* c, int64_t first, int64_t count, double* spectra_out, double* stats_out) {
+  const FlowSpecState& fs = c->flow;
+  HIPCHK_RC(frame_range_check(c, fs.series.ext, first, count, "frame range out of bounds"));
+  if (!spectra_out && !stats_out) return fail(c, SWRT_ERR_ARG, "NULL buffer (spectra_out and stats4_out)");
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t fr = fs.frame();
+  if (spectra_out)
+    HIPCHK(c, hipMemcpyAsync(spectra_out, fs.series.a.get() + fr * first, sizeof(double) * fr * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  if (stats_out)
+    HIPCHK(c, hipMemcpyAsync(stats_out, fs.series.b.get() + (size_t)kFlowSpecStats * first,
+                             sizeof(double) * kFlowSpecStats * count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return SWRT_OK;
 }
 

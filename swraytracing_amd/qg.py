@@ -136,6 +136,75 @@ class QGModel:
         snapshot(slot) this step gives once accepted (bit for bit)."""
         self.ctx.qg_snapshot_speculative(slot, ny_period)
 
+    # ---- the flow spectrum series (swrt_flow_spectrum_*) ----
+    @property
+    def kscale(self):
+        """2*pi/L as the device holds it (QGDev.kscale): exactly 1 for one layer."""
+        return 1.0 if self.nlayers == 1 else 2.0 * math.pi / self.L
+
+    def begin_flow_spectrum(self, layer=0):
+        """Open the device-side series of layer ``layer``'s shell spectra with
+        the model's own nx, kscale and K_d2.  Empties the series."""
+        if not 0 <= int(layer) < self.nlayers:
+            raise ValueError(f"layer must be 0..{self.nlayers - 1}")
+        self.flow_layer = int(layer)
+        self.ctx.flow_spectrum_begin(self.nx, self.kscale, self.params.K_d2)
+
+    def record_flow_spectrum(self):
+        """Append the committed qk's frame (queued behind the step that made
+        it, no host wait).  A pending speculative step stays pending and is
+        not included."""
+        self.ctx.flow_spectrum_record_qg(self.flow_layer)
+
+    def write_flow_spectrum(self, out_dir, first_time=None):
+        """Append the recorded frames to ``out_dir``/flow_spec.bin (float64,
+        3*nshell per frame: E, Z, Q per shell) and flow_stats.bin ([t, sum E,
+        sum Z, sum Q] per frame), and write flow_geom.bin ([nx, nshell,
+        k_scale, K_d2, layer]).  ``first_time``: the label the first frame
+        takes in place of the model time (the drivers label their first packet
+        frame, taken before the loop, dt*(packet_step_start - 1); the flow is
+        the initial one, model time 0).  Returns the number of frames."""
+        spectra, stats = self.ctx.flow_spectrum_get()
+        if first_time is not None and len(stats):
+            stats[0, 0] = first_time
+        ns = self.ctx.flow_spectrum_shells()
+        for name, a in (("flow_spec.bin", spectra), ("flow_stats.bin", stats)):
+            with open(os.path.join(out_dir, name), "ab") as fh:  # (frame-major: appended as write_field does)
+                fh.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+        with open(os.path.join(out_dir, "flow_geom.bin"), "wb") as fh:
+            fh.write(np.array([self.nx, ns, self.kscale, self.params.K_d2, self.flow_layer], dtype=np.float64).tobytes())
+        return len(stats)
+
+
+def flow_shell_count(nx):
+    """Shells of an nx^2 grid: shell(kmax, kmax) + 1 with the integer rule
+    j(j-1) < kx^2 + ky^2 <= j(j+1) (include/swrt.h)."""
+    kmax = int(nx) // 2 - 1
+    r2 = 2 * kmax * kmax
+    s = math.isqrt(r2)
+    return (s if r2 <= s * (s + 1) else s + 1) + 1
+
+
+def flow_shells(nx, L):
+    """The shell wavenumbers j*2*pi/L, j = 0..nshell-1, of the flow spectrum series."""
+    return np.arange(flow_shell_count(nx), dtype=np.float64) * (2.0 * math.pi / L)
+
+
+def flow_spectrum_fields(spectra, stats, Cg=None):
+    """Flow spectrum frames (Context.flow_spectrum_get, or flow_spec.bin and
+    flow_stats.bin reshaped to (frames, 3*nshell) and (frames, 4)) as a dict:
+    t, E, Z, Q (frames x nshell: kinetic energy, relative-vorticity enstrophy
+    and PV variance per shell, each summing to half the domain mean),
+    U_rms = sqrt(2 sum E), zeta_rms = sqrt(2 sum Z) and, with ``Cg``,
+    Fr = U_rms / Cg."""
+    stats = np.asarray(stats, dtype=np.float64).reshape(-1, 4)
+    sp = np.asarray(spectra, dtype=np.float64).reshape(len(stats), 3, -1)
+    out = dict(t=stats[:, 0].copy(), E=sp[:, 0], Z=sp[:, 1], Q=sp[:, 2],
+               U_rms=np.sqrt(2.0 * stats[:, 1]), zeta_rms=np.sqrt(2.0 * stats[:, 2]))
+    if Cg is not None:
+        out["Fr"] = out["U_rms"] / float(Cg)
+    return out
+
 
 # ----------------------------------------------------------------------------
 # Drivers
@@ -233,7 +302,7 @@ def _fresh_outputs(out_dir, fresh):
         return
     for name in ("packet_x", "packet_k", "packet_time", "pv", "pv_time", "omega_hist", "omega_stats", "omega_edges",
                  "map_n", "map_omega", "map_k", "map_l", "map_stats", "track_x", "track_k", "track_diag", "track_time",
-                 "track_ids", "kmap_n", "kmap_stats", "kmap_geom"):
+                 "track_ids", "kmap_n", "kmap_stats", "kmap_geom", "flow_spec", "flow_stats", "flow_geom"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
@@ -287,6 +356,13 @@ def _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits, ring_radius=None):
     if not real(kmap_kmax) or not math.isfinite(kmap_kmax) or not kmap_kmax > 0:
         raise ValueError("kmap_kmax must be a positive finite number")
     return float(kmap_kmax), int(kmap_cells), int(kmap_frac_bits)
+
+
+def _flow_args(flow_spectrum, Npackets):
+    """The drivers' ``flow_spectrum`` checked before anything runs: its frames
+    are the packet frames, so it needs packets."""
+    if flow_spectrum and Npackets <= 0:
+        raise ValueError("flow_spectrum records at the packet frames: it needs Npackets > 0")
 
 
 def _ring_radius(near_inertial_factor, f, Cg):
@@ -582,7 +658,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                   packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
                   pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None, packet_files=True,
                   map_cells=None, map_frac_bits=20, track_ids=None, track_every=None,
-                  kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16):
+                  kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -630,8 +706,17 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     sum q(k*l)) and kmap_geom.bin (three doubles K, m, frac_bits); the frames
     line up with packet_time.bin, and ``packet_files=False`` is allowed with
     ``kmap_cells`` alone.
+    ``flow_spectrum``: at every packet frame the rank that steps the PDE
+    (rank 0 when sharded, whether or not it holds packets) records the shell
+    spectra of layer 0's committed qk on the device (swrt_flow_spectrum_*, on
+    the QG stream, no host wait), written at the end as flow_spec.bin (float64,
+    3*nshell per frame: E, Z, Q per shell), flow_stats.bin ([t, sum E, sum Z,
+    sum Q] per frame; t lines up with packet_time.bin) and flow_geom.bin
+    ([nx, nshell, k_scale, K_d2, layer]); no other output changes.
     Returns a dict of run facts (dt, Nsteps, steps run, frames written,
-    final t, spectrum_frames, map_frames, track_frames, kmap_frames)."""
+    final t, spectrum_frames, map_frames, track_frames, kmap_frames,
+    flow_frames)."""
+    _flow_args(flow_spectrum, Npackets)
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files, kmap_cells)
     map_args = _map_args(map_cells, map_frac_bits)
     kmap_args = _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits,
@@ -698,6 +783,10 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     if tracks:
         ens.begin_tracks(track_args[0], directory=out_dir)
         ens.record_tracks(dt * (packet_step_start - 1), 0)  # (no snapshot yet: the flow columns are NaN)
+    flows = bool(flow_spectrum) and rank == 0  # (rank 0 steps the PDE in both sharded forms)
+    if flows:
+        model.begin_flow_spectrum(0)
+        model.record_flow_spectrum()
     if ens is not None:
         _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files, maps, kmaps)
     if rank == 0:
@@ -728,6 +817,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
             if (step - packet_step_start + 1) % packet_steps_per_save == 0:
                 group.flush()
                 _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps)
+                if flows:
+                    model.record_flow_spectrum()
                 frames += 1
         else:
             have_cur = False
@@ -743,13 +834,16 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     map_frames = ens.write_maps(out_dir) if maps else 0
     track_frames = ens.write_tracks(out_dir) if tracks else 0
     kmap_frames = ens.write_kmaps(out_dir) if kmaps else 0
+    if flows:
+        model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
+    flow_frames = frames if flow_spectrum else 0
     ctx.synchronize()
     ctx.set_timing(timing)
     log.finish()
     log.close()
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
-                track_frames=track_frames, kmap_frames=kmap_frames)
+                track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames)
 
 
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
@@ -757,7 +851,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                         packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
                         pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None,
                         packet_files=True, map_cells=None, map_frac_bits=20, track_ids=None, track_every=None,
-                        kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16):
+                        kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
@@ -765,8 +859,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     ``packet_intervals``, ``integrator``, ``fresh``, ``spectrum_edges``,
     ``packet_files``, ``map_cells``, ``map_frac_bits``, ``kmap_cells``,
     ``kmap_kmax``, ``kmap_frac_bits``, ``track_ids``,
-    ``track_every`` (default: this driver's packet cadence, 25): as in
-    :func:`qgsw_raytrace`.
+    ``track_every`` (default: this driver's packet cadence, 25),
+    ``flow_spectrum``: as in :func:`qgsw_raytrace`.
 
     Sharded (torch.distributed, world > 1): ``pde="owner"`` (default) — rank 0
     steps the PDE and sends each step's top-layer qk and dt to the other
@@ -782,6 +876,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     kmap_args = _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits,
                            _ring_radius(near_inertial_factor, f, Cg) if kmap_cells is not None else None)
     track_args = _track_args(track_ids, track_every, Npackets, 25)  # (25: packet_steps_per_save below)
+    _flow_args(flow_spectrum, Npackets)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
@@ -834,6 +929,10 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     if tracks:
         ens.begin_tracks(track_args[0], directory=out_dir)
         ens.record_tracks(dt * (packet_step_start - 1), 0)  # (no snapshot yet: the flow columns are NaN)
+    flows = bool(flow_spectrum) and rank == 0  # (rank 0 steps the PDE in both sharded forms)
+    if flows:
+        model.begin_flow_spectrum(0)
+        model.record_flow_spectrum()
     if ens is not None:
         _save_frame(ens, dt * (packet_step_start - 1), out_dir, spectrum, packet_files, maps, kmaps)
     if rank == 0:
@@ -862,6 +961,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
         if active and (loop.steps - packet_step_start + 1) % packet_steps_per_save == 0:
             loop.flush()
             _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps)
+            if flows:
+                model.record_flow_spectrum()  # (the committed qk at loop.t; the next step is only speculative)
             frames += 1
         log.progress(loop.steps, Nsteps)
     loop.flush()
@@ -872,6 +973,9 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     map_frames = ens.write_maps(out_dir) if maps else 0
     track_frames = ens.write_tracks(out_dir) if tracks else 0
     kmap_frames = ens.write_kmaps(out_dir) if kmaps else 0
+    if flows:
+        model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
+    flow_frames = frames if flow_spectrum else 0
     ctx.synchronize()
     ctx.set_timing(timing)
     log.finish()
@@ -880,4 +984,4 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     U0 = getattr(loop, "U0", U0)  # (a receiving rank never sees the owner's U0)
     return dict(dt=dt, dts=dts, Nsteps=Nsteps, steps=step, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
-                track_frames=track_frames, kmap_frames=kmap_frames)
+                track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames)
