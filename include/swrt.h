@@ -620,6 +620,76 @@ int swrt_flow_spectrum_get(swrt_ctx* ctx, int64_t first, int64_t count, double* 
 int swrt_flow_spectrum_reset(swrt_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * The conditional spectrum series: the energy-vs-omega distribution of the
+ * packets (analysis/load_data.m:33-52) split by a scalar of the flow at each
+ * packet (RaytracingScheme.m:18-31), kept on the device as integers.
+ *
+ * Per packet, with which = 0 (zeta), 1 (sigma) or 2 (D):
+ *   omega = sqrt(f^2 + Cg^2 (k k + l l)), the operation order of the spectrum
+ *           series (load_data.m:33);
+ *   q     = that scalar, the bits swrt_raydiag_sample returns for the same
+ *           (nslots, alpha, bump).
+ * The omega class is the spectrum series' rule over omega_edges (a row
+ * [below, bin 0 .. bin nw-1, above], the last bin closed); the q class is the
+ * same rule over q_edges with nq bins.  A frame holds
+ *   counts  (nq + 2) x (nw + 2) int64, q class major: counts[qc * (nw + 2) + wc];
+ *   sums    nq + 2 int64: per q class the sum of rint(omega * 2^frac_bits)
+ *           (round half even) over the packets counted there, so that
+ *           sums / counts is the conditional mean omega, exact to the quantum;
+ *   stats   2 int64 [n, rejected].
+ * A packet whose omega or q is NaN, or with |omega * 2^frac_bits| >= 2^38, is
+ * rejected and counted nowhere: the counts of a frame sum to n - rejected.
+ * The marginal over the q classes is the spectrum series' row of the accepted
+ * packets.  Integer addition is exact and order-free: a frame depends on the
+ * packet set alone (two contexts, a re-binning between two records, either
+ * advance call and either packet-stream setting give the same bits), and the
+ * frames of shards combine by adding.  Positions must be finite, as for every
+ * gather of the library.
+ * ------------------------------------------------------------------------- */
+
+/* Open a series: 1 <= nw, nq <= 4096 with (nq + 2) * (nw + 2) <= 65536 cells
+ * (512 KB a frame), both edge arrays finite and increasing, which 0..2,
+ * 0 <= frac_bits <= 32 (SWRT_ERR_ARG with a message otherwise).  Empties the
+ * series. */
+int swrt_cond_series_begin(swrt_ctx* ctx, double f, double Cg, const double* omega_edges, int64_t nw, int which,
+                           const double* q_edges, int64_t nq, int frac_bits);
+
+/* Append the frame of the current packets in the flow of slot 0 (nslots 1) or
+ * of slots 0 and 1 blended at alpha (nslots 2): queued on the packet stream
+ * after whatever last wrote the packets and after the snapshot writes of the
+ * slots it reads, no host wait (growing the series past its capacity, which
+ * doubles, may wait for the stream).  Up to 16384 cells every workgroup
+ * counts into a private plane in LDS and adds its non-zero cells to the frame;
+ * beyond, every packet adds through global memory: the same integers.
+ * SWRT_ERR_STATE before swrt_cond_series_begin; SWRT_ERR_ARG as for
+ * swrt_raydiag_record (nslots, an unset slot, two grids, no packets) and with
+ * more than 2^24 packets. */
+int swrt_cond_series_record(swrt_ctx* ctx, int nslots, double alpha, double bump);
+
+/* One frame per history frame in [first, first + count), frame i in the flow
+ * at alphas[i] (alphas may be NULL with one snapshot, as for
+ * swrt_raydiag_record_history): the same bits as swrt_cond_series_record on
+ * packets set to that frame.  With two snapshots the call waits for the
+ * stream once, before its launches, while alphas goes to the device.  A
+ * range out of bounds: SWRT_ERR_ARG. */
+int swrt_cond_series_record_history(swrt_ctx* ctx, int64_t first, int64_t count, int nslots, const double* alphas,
+                                    double bump);
+
+/* Frames recorded since begin or the last reset; nw and nq of the open
+ * series, 0 if none (either pointer may be NULL). */
+int64_t swrt_cond_series_frames(const swrt_ctx* ctx);
+int swrt_cond_series_bins(const swrt_ctx* ctx, int64_t* nw_out, int64_t* nq_out);
+
+/* Frames [first, first + count): counts_out count x (nq + 2) x (nw + 2),
+ * sums_out count x (nq + 2) and stats2_out count x 2, frame-major.  Each may
+ * be NULL.  Waits for the frames. */
+int swrt_cond_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                         int64_t* stats2_out);
+
+/* Empty the series; the edges, which and frac_bits stay. */
+int swrt_cond_series_reset(swrt_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
  * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)
  * ------------------------------------------------------------------------ */
@@ -1053,7 +1123,10 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
  *   records.  0: by m (the LDS kernel up to m = 128, the global one beyond);
  *   1: the global kernel for every m, as it ships; 2 / 3: the global kernel
  *   with / without its wave-level merge (tools/kmap_series_rate.py).  Every
- *   value gives the same integers. */
+ *   value gives the same integers.
+ * SWRT_DEBUG_COND_GLOBAL 0 / 1 (default 0): 1 makes the conditional spectrum
+ *   series' records take the global kernel for every shape
+ *   (tools/cond_series_rate.py).  Both values give the same integers. */
 #define SWRT_DEBUG_HAZARD_CHECK 1
 #define SWRT_DEBUG_SPIN_US 2
 #define SWRT_DEBUG_LEGACY_PARK 3
@@ -1072,6 +1145,7 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
 #define SWRT_DEBUG_MAP_TILED_FRAMES 17
 #define SWRT_DEBUG_MAP_STRAYS 18
 #define SWRT_DEBUG_KMAP_GLOBAL 19
+#define SWRT_DEBUG_COND_GLOBAL 20
 int swrt_debug_set(swrt_ctx* ctx, int key, int64_t value);
 int swrt_debug_get(swrt_ctx* ctx, int key, int64_t* value_out);
 

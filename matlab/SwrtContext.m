@@ -89,6 +89,40 @@ classdef SwrtContext < handle
             swrt_mex('map_series_reset', obj.id());
         end
 
+        % The conditional spectrum on the device: per frame the int64 counts
+        % of the packets over omega classes (load_data.m:33-52; rows
+        % [below, bins, above] over omega_edges) by the classes of a flow
+        % scalar at the packets over q_edges (which 0: vorticity, 1: strain,
+        % 2: Okubo-Weiss; RaytracingScheme.m:18-31), the per-class sums of
+        % round(omega * 2^frac_bits), and [n; rejected].
+        function cond_series_begin(obj, f, Cg, omega_edges, which, q_edges, frac_bits)
+            if nargin < 7, frac_bits = 20; end
+            swrt_mex('cond_series_begin', obj.id(), f, Cg, omega_edges, which, q_edges, frac_bits);
+        end
+
+        function cond_series_record(obj, nslots, alpha, bump)
+            swrt_mex('cond_series_record', obj.id(), nslots, alpha, bump);
+        end
+
+        function cond_series_record_history(obj, first, count, nslots, alphas, bump)
+            % history frames first .. first+count-1, 0-based; alphas [] with one snapshot
+            swrt_mex('cond_series_record_history', obj.id(), first, count, nslots, alphas, bump);
+        end
+
+        function n = cond_series_frames(obj)
+            n = swrt_mex('cond_series_frames', obj.id());
+        end
+
+        function [counts, sums, stats] = cond_series_get(obj)
+            % counts: int64 (nw+2) x (nq+2) x frames (first index the omega class);
+            % sums: int64 (nq+2) x frames; stats: int64 2 x frames
+            [counts, sums, stats] = swrt_mex('cond_series_get', obj.id());
+        end
+
+        function cond_series_reset(obj)
+            swrt_mex('cond_series_reset', obj.id());
+        end
+
         % The wave-vector plane on the device (what raytracing_figures.m:19-26,
         % 76-83 scatter packet by packet): per frame an m x m int64 count
         % plane over [-K, K) x [-K, K), first index k, and eight int64 stats

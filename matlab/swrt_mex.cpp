@@ -55,7 +55,13 @@
 //   n = swrt_mex('kmap_series_frames', h)
 //   [planes, stats] = swrt_mex('kmap_series_get', h)          % int64 m x m x frames, int64 8 x frames
 //   swrt_mex('kmap_series_reset', h)
-//   swrt_mex('track_begin', h, ids)                           % trajectories of chosen packets; ids 0-based doubles
+//   swrt_mex('cond_series_begin', h, f, Cg, omega_edges, which, q_edges[, frac_bits])   % omega classes by zeta/sigma/D classes
+//   swrt_mex('cond_series_record', h, nslots, alpha, bump)
+//   swrt_mex('cond_series_record_history', h, first, count, nslots, alphas, bump)   % alphas [] when nslots < 2
+//   n = swrt_mex('cond_series_frames', h)
+//   [counts, sums, stats] = swrt_mex('cond_series_get', h)    % int64 (nw+2) x (nq+2) x frames, (nq+2) x frames, 2 x frames
+//   swrt_mex('cond_series_reset', h)
+//   swrt_mex('track_begin', h, ids)                         % trajectories of chosen packets; ids 0-based doubles
 //   swrt_mex('track_record', h, f, gH, nslots, alpha, bump)   % nslots 0: no flow, Omega..D are NaN
 //   swrt_mex('track_record_history', h, first, count, f, gH, nslots, alphas, bump)   % alphas [] when nslots < 2
 //   frames = swrt_mex('track_get', h)                         % m x 8 x frames [x y k l Omega zeta sigma D]
@@ -555,6 +561,55 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   if (!strcmp(cmd, "kmap_series_reset")) {
     check(c, swrt_kmap_series_reset(c), "swrt_kmap_series_reset");
+    return;
+  }
+  if (!strcmp(cmd, "cond_series_begin")) {  // (f, Cg, omega_edges, which, q_edges[, frac_bits = 20])
+    need(na, 6, cmd);
+    const size_t ne = mxGetNumberOfElements(a[3]), nqe = mxGetNumberOfElements(a[5]);
+    check(c, swrt_cond_series_begin(c, scalar(a[1]), scalar(a[2]), reals(a[3], "omega_edges"), (int64_t)ne - 1,
+                                    (int)scalar(a[4]), reals(a[5], "q_edges"), (int64_t)nqe - 1,
+                                    na > 6 ? (int)scalar(a[6]) : 20),
+          "swrt_cond_series_begin");
+    return;
+  }
+  if (!strcmp(cmd, "cond_series_record")) {  // (nslots, alpha, bump)
+    need(na, 4, cmd);
+    check(c, swrt_cond_series_record(c, (int)scalar(a[1]), scalar(a[2]), scalar(a[3])), "swrt_cond_series_record");
+    return;
+  }
+  if (!strcmp(cmd, "cond_series_record_history")) {  // (first, count, nslots, alphas, bump): [] alphas = none
+    need(na, 6, cmd);
+    const int64_t count = (int64_t)scalar(a[2]);
+    const size_t nal = mxGetNumberOfElements(a[4]);
+    if (nal != 0 && (int64_t)nal != count) mexErrMsgIdAndTxt("swrt:arg", "alphas must hold one value per frame");
+    check(c, swrt_cond_series_record_history(c, (int64_t)scalar(a[1]), count, (int)scalar(a[3]),
+                                             nal ? reals(a[4], "alphas") : nullptr, scalar(a[5])),
+          "swrt_cond_series_record_history");
+    return;
+  }
+  if (!strcmp(cmd, "cond_series_frames")) {
+    plhs[0] = mxCreateDoubleScalar((double)swrt_cond_series_frames(c));
+    return;
+  }
+  if (!strcmp(cmd, "cond_series_get")) {  // -> counts (nw+2) x (nq+2) x frames, sums (nq+2) x frames, stats 2 x frames
+    const int64_t nf = swrt_cond_series_frames(c);
+    int64_t nw = 0, nq = 0;
+    check(c, swrt_cond_series_bins(c, &nw, &nq), "swrt_cond_series_bins");
+    const mwSize dims[3] = {(mwSize)(nw + 2), (mwSize)(nq + 2), (mwSize)nf}, udims[2] = {(mwSize)(nq + 2), (mwSize)nf},
+                 sdims[2] = {2, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(3, dims, mxINT64_CLASS, mxREAL);
+    mxArray* sums = mxCreateNumericArray(2, udims, mxINT64_CLASS, mxREAL);
+    mxArray* stats = mxCreateNumericArray(2, sdims, mxINT64_CLASS, mxREAL);
+    if (nf > 0)
+      check(c, swrt_cond_series_get(c, 0, nf, (int64_t*)mxGetInt64s(plhs[0]), (int64_t*)mxGetInt64s(sums),
+                                    (int64_t*)mxGetInt64s(stats)),
+            "swrt_cond_series_get");
+    if (nlhs > 1) plhs[1] = sums; else mxDestroyArray(sums);
+    if (nlhs > 2) plhs[2] = stats; else mxDestroyArray(stats);
+    return;
+  }
+  if (!strcmp(cmd, "cond_series_reset")) {
+    check(c, swrt_cond_series_reset(c), "swrt_cond_series_reset");
     return;
   }
   if (!strcmp(cmd, "track_begin")) {  // (ids): 0-based original packet indices, as doubles

@@ -6,8 +6,8 @@ CDNA4 kernels behind the C ABI in include/swrt.h, with the reference's
 MATLAB call surface mirrored in Python.
 """
 from ._lib import Context, SwrtError, load
-from .integrate import (PacketEnsemble, combine_frames, combine_kmaps, combine_maps, combine_spectra, combine_tracks,
-                        energy_spectrum, kmap_moments, map_fields,
+from .integrate import (PacketEnsemble, combine_conds, combine_frames, combine_kmaps, combine_maps, combine_spectra, combine_tracks,
+                        cond_spectra, energy_spectrum, kmap_moments, map_fields,
                         ode23_packets, ode23_trajectory,
                         ode_symplectic, raytrace_sw, raytrace_xka, rsw_background, step_packet_xka)
 from .io import read_field, write_field
@@ -19,7 +19,7 @@ from .scheme import (BUMP_QG, BUMP_SW, DifferenceScheme, FourierScheme, Raytraci
 
 __all__ = [
     "Context", "SwrtError", "load", "PacketEnsemble", "combine_frames", "combine_maps", "combine_spectra",
-    "combine_tracks", "combine_kmaps",
+    "combine_tracks", "combine_kmaps", "combine_conds", "cond_spectra",
     "energy_spectrum", "kmap_moments", "map_fields", "ode23_packets", "ode23_trajectory",
     "ode_symplectic",
     "raytrace_sw", "raytrace_xka", "rsw_background", "step_packet_xka",

@@ -106,6 +106,14 @@ SIGNATURES = {
     "swrt_kmap_series_cells": (_I, [_VP]),
     "swrt_kmap_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "swrt_kmap_series_reset": (_INT, [_VP]),
+    "swrt_cond_series_begin": (_INT, [_VP, _D, _D, _P, _I, _INT, _P, _I, _INT]),
+    "swrt_cond_series_record": (_INT, [_VP, _INT, _D, _D]),
+    "swrt_cond_series_record_history": (_INT, [_VP, _I, _I, _INT, _P, _D]),
+    "swrt_cond_series_frames": (_I, [_VP]),
+    "swrt_cond_series_bins": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_cond_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                    ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_cond_series_reset": (_INT, [_VP]),
     "swrt_track_begin": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64), _I]),
     "swrt_track_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
     "swrt_track_record_history": (_INT, [_VP, _I, _I, _D, _D, _INT, _P, _D]),
@@ -194,6 +202,8 @@ DEBUG_ODE23_DENSE_REBINS = 16
 DEBUG_MAP_TILED_FRAMES = 17
 DEBUG_MAP_STRAYS = 18
 DEBUG_KMAP_GLOBAL = 19
+DEBUG_COND_GLOBAL = 20
+COND_WHICH = {"zeta": 0, "sigma": 1, "D": 2}  # swrt_cond_series_begin's ``which``
 
 _lib = None
 
@@ -668,6 +678,64 @@ class Context:
 
     def kmap_series_reset(self):
         self._chk(self._L.swrt_kmap_series_reset(self._h), "swrt_kmap_series_reset")
+
+    # ---- the conditional spectrum series (swrt_cond_series_*: omega classes by a flow scalar's classes) ----
+    def cond_series_begin(self, f, Cg, omega_edges, which, q_edges, frac_bits=20):
+        """Open a series of (nq + 2) x (nw + 2) count planes: omega classes
+        over ``omega_edges`` (nw + 1 increasing values) by the classes of the
+        flow scalar ``which`` (0 / "zeta", 1 / "sigma", 2 / "D") at the packets
+        over ``q_edges`` (nq + 1 increasing values); the per-class omega sums
+        quantised to 2^-frac_bits.  Empties the series."""
+        wedges = _f64(np.asarray(omega_edges, dtype=np.float64).ravel())
+        qedges = _f64(np.asarray(q_edges, dtype=np.float64).ravel())
+        which = COND_WHICH.get(which, which) if isinstance(which, str) else which
+        self._chk(self._L.swrt_cond_series_begin(self._h, float(f), float(Cg), _p(wedges), wedges.size - 1, int(which),
+                                                 _p(qedges), qedges.size - 1, int(frac_bits)),
+                  "swrt_cond_series_begin")
+
+    def cond_series_record(self, nslots=1, alpha=0.0, bump=1e-13):
+        """Append the current packets' frame in the flow of slot 0 (nslots 1)
+        or slots 0 and 1 blended at ``alpha`` (queued; no host wait)."""
+        self._chk(self._L.swrt_cond_series_record(self._h, int(nslots), float(alpha), float(bump)),
+                  "swrt_cond_series_record")
+
+    def cond_series_record_history(self, first, count, nslots=1, alphas=None, bump=1e-13):
+        """One frame per history frame [first, first + count), frame i with
+        the snapshot blend ``alphas[i]`` (None with one snapshot: 0)."""
+        if alphas is not None:
+            alphas = np.ascontiguousarray(alphas, dtype=np.float64)
+            if alphas.shape != (int(count),):
+                raise ValueError("alphas must hold one value per frame")
+        self._chk(self._L.swrt_cond_series_record_history(self._h, int(first), int(count), int(nslots), _p(alphas),
+                                                          float(bump)), "swrt_cond_series_record_history")
+
+    def cond_series_frames(self):
+        return int(self._L.swrt_cond_series_frames(self._h))
+
+    def cond_series_bins(self):
+        """(nw, nq) of the open series, (0, 0) if none."""
+        nw, nq = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self._L.swrt_cond_series_bins(self._h, ctypes.byref(nw), ctypes.byref(nq)), "swrt_cond_series_bins")
+        return int(nw.value), int(nq.value)
+
+    def cond_series_get(self, first=0, count=None):
+        """Recorded frames [first, first + count) -> (counts (count, nq + 2,
+        nw + 2) int64, counts[t, qc, wc]; sums (count, nq + 2) int64, the sum
+        of rint(omega * 2^frac_bits) per q class; stats (count, 2) int64
+        [n, rejected])."""
+        count = self.cond_series_frames() - first if count is None else count
+        nw, nq = self.cond_series_bins()
+        counts = np.zeros((max(count, 0), nq + 2, nw + 2), dtype=np.int64)
+        sums = np.zeros((max(count, 0), nq + 2), dtype=np.int64)
+        stats = np.zeros((max(count, 0), 2), dtype=np.int64)
+        i64 = ctypes.POINTER(ctypes.c_int64)
+        self._chk(self._L.swrt_cond_series_get(self._h, int(first), int(count), counts.ctypes.data_as(i64),
+                                               sums.ctypes.data_as(i64), stats.ctypes.data_as(i64)),
+                  "swrt_cond_series_get")
+        return counts, sums, stats
+
+    def cond_series_reset(self):
+        self._chk(self._L.swrt_cond_series_reset(self._h), "swrt_cond_series_reset")
 
     # ---- the track series (swrt_track_*: trajectories of chosen packets) ------
     def track_begin(self, ids):

@@ -1567,6 +1567,103 @@ int swrt_flow_spectrum_reset(swrt_ctx* c) {
   return SWRT_OK;
 }
 
+// ---- the conditional spectrum series (swrt_cond.hpp, swrt_host_diag.hpp) ----
+int swrt_cond_series_begin(swrt_ctx* c, double f, double Cg, const double* omega_edges, int64_t nw, int which,
+                           const double* q_edges, int64_t nq, int frac_bits) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(omega_edges_check(c, omega_edges, nw));
+  HIPCHK_RC(omega_edges_check(c, q_edges, nq));
+  if ((nq + 2) * (nw + 2) > kCondMaxCells) return fail(c, SWRT_ERR_ARG, "(nq + 2) * (nw + 2) must be at most 65536");
+  if (which < 0 || which > 2) return fail(c, SWRT_ERR_ARG, "which must be 0 (zeta), 1 (sigma) or 2 (D)");
+  if (frac_bits < 0 || frac_bits > kCondMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
+  HIPCHK(c, hipSetDevice(c->device));
+  CondSeriesState& cs = c->cond;
+  HIPCHK_RC(series_release(c, cs.series));  // (waits: queued records read the old edges too)
+  cs.open = false;
+  HIPCHK(c, cs.edges.alloc(nw + nq + 2));
+  HIPCHK(c, hipMemcpyAsync(cs.edges.get(), omega_edges, sizeof(double) * (nw + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(cs.edges.get() + nw + 1, q_edges, sizeof(double) * (nq + 1), hipMemcpyHostToDevice,
+                           c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  cs.nw = (int)nw;
+  cs.nq = (int)nq;
+  cs.which = which;
+  cs.frac_bits = frac_bits;
+  cs.f2 = f * f;
+  cs.Cg2 = Cg * Cg;
+  cs.open = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_cond_series_record(swrt_ctx* c, int nslots, double alpha, double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c, false, track_slot_mask(nslots));
+  HIPCHK_RC(cond_series_check(c, nslots));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(cond_reserve_zeroed(c, 1));
+  return cond_launch(c, nslots, alpha, nullptr, bump, c->pk.cur.x.get(), c->pk.cur.k.get(), 0, 1);
+  GUARD_END(c)
+}
+
+int swrt_cond_series_record_history(swrt_ctx* c, int64_t first, int64_t count, int nslots, const double* alphas,
+                                    double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c, false, track_slot_mask(nslots));
+  HIPCHK_RC(cond_series_check(c, nslots));
+  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
+  if (nslots == 2 && !alphas && count > 0) return fail(c, SWRT_ERR_ARG, "NULL buffer (alphas, two snapshots)");
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  CondSeriesState& cs = c->cond;
+  const double* dalphas = nullptr;
+  if (nslots == 2) {  // the frames' alphas to the device; the caller's buffer is free on return
+    if (count > cs.acap) {  // (releasing the old buffer waits for queued readers)
+      cs.acap = 0;
+      HIPCHK(c, cs.alphas.alloc(count));
+      cs.acap = count;
+    }
+    HIPCHK(c, hipMemcpyAsync(cs.alphas.get(), alphas, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    dalphas = cs.alphas.get();
+  }
+  HIPCHK_RC(cond_reserve_zeroed(c, count));
+  for (int64_t i = 0; i < count; i += kCondHistoryChunk) {
+    const int64_t nf = std::min<int64_t>(kCondHistoryChunk, count - i), off = (first + i) * 2 * c->n;
+    HIPCHK_RC(cond_launch(c, nslots, 0.0, dalphas ? dalphas + i : nullptr, bump, c->hist.a.get() + off,
+                          c->hist.b.get() + off, 2 * c->n, nf));
+  }
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int64_t swrt_cond_series_frames(const swrt_ctx* c) { return c ? c->cond.series.ext.frames() : -1; }
+
+int swrt_cond_series_bins(const swrt_ctx* c, int64_t* nw_out, int64_t* nq_out) {
+  if (!c) return SWRT_ERR_ARG;
+  if (nw_out) *nw_out = c->cond.open ? c->cond.nw : 0;
+  if (nq_out) *nq_out = c->cond.open ? c->cond.nq : 0;
+  return SWRT_OK;
+}
+
+int swrt_cond_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                         int64_t* stats2_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  return cond_series_get(c, first, count, counts_out, sums_out, stats2_out);
+  GUARD_END(c)
+}
+
+int swrt_cond_series_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
+  c->cond.series.ext.cleared();
+  return SWRT_OK;
+}
+
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
@@ -1638,6 +1735,10 @@ int swrt_debug_set(swrt_ctx* c, int key, int64_t value) {
       if (value < 0 || value > 3) return fail(c, SWRT_ERR_ARG, "k-plane path must be 0..3");
       c->dbg.kmap_path = (int)value;
       return SWRT_OK;
+    case SWRT_DEBUG_COND_GLOBAL:
+      if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "conditional spectrum path must be 0 or 1");
+      c->dbg.cond_global = value != 0;
+      return SWRT_OK;
     case SWRT_DEBUG_QG_UPDATE_COLS:
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "QG update/column-pass fusion must be 0 or 1");
       if (c->qg.spec) return fail(c, SWRT_ERR_STATE, "a speculative QG step is pending (swrt_qg_resolve first)");
@@ -1676,6 +1777,7 @@ int swrt_debug_get(swrt_ctx* c, int key, int64_t* value_out) {
     case SWRT_DEBUG_ODE23_DENSE_REBINS: *value_out = c->o23.dense_rebins; return SWRT_OK;
     case SWRT_DEBUG_MAP_TILED_FRAMES: *value_out = c->map.tiled_frames; return SWRT_OK;
     case SWRT_DEBUG_KMAP_GLOBAL: *value_out = c->dbg.kmap_path; return SWRT_OK;
+    case SWRT_DEBUG_COND_GLOBAL: *value_out = c->dbg.cond_global ? 1 : 0; return SWRT_OK;
     case SWRT_DEBUG_MAP_STRAYS: {  // the device's counter: waits for the queued records
       unsigned long long v = 0;
       if (c->map.strays) {

@@ -401,6 +401,25 @@ struct FlowSpecState {
   size_t frame() const { return (size_t)3 * nshell; }
 };
 
+// the conditional spectrum series (swrt_cond_series_*, swrt_cond.hpp).
+// Buffers of its own, as the other recorders'; a frame is self-contained (its
+// n is in its stats), so swrt_packets_set with another N keeps the series.
+struct CondSeriesState {
+  bool open = false;        // swrt_cond_series_begin was called
+  int nw = 0, nq = 0;       // omega and q bins of the open series
+  int which = 0;            // 0 zeta, 1 sigma, 2 D
+  int frac_bits = 0;
+  double f2 = 0.0, Cg2 = 0.0;
+  DevBuf<double> edges;     // nw + 1 omega edges, then nq + 1 q edges
+  DevBuf<double> alphas;    // record_history's alphas, one per frame of the call
+  int64_t acap = 0;         // frames alphas is sized for
+  bool lds_attr = false;    // the kernels' dynamic LDS limit was raised
+  // recorded frames: (nq + 2) x (nw + 2) counts each, and their nq + 2 sums followed by [n, rejected]
+  Series<unsigned long long> series;
+  size_t frame() const { return (size_t)(nq + 2) * (nw + 2); }
+  size_t tail() const { return (size_t)nq + 4; }
+};
+
 // debug knobs (swrt_debug_set): a spin kernel queued on every extra packet
 // stream before each of its part launches (adversarial overlap of consecutive
 // calls), and the pre-third-buffer ordering after a source-gather sort
@@ -411,6 +430,7 @@ struct DebugKnobs {
   bool share_skew = false;  // test-only: the cycle-ending launch takes an uneven share (checker on only)
   int corrupt_count = 0;    // test-only: added to one tile count before the next scan (once)
   int kmap_path = 0;        // SWRT_DEBUG_KMAP_GLOBAL: 0 by m; 1 global; 2 / 3 global with / without the wave merge
+  bool cond_global = false; // SWRT_DEBUG_COND_GLOBAL: the conditional spectrum series' global kernel for every shape
 };
 }  // namespace
 
@@ -480,6 +500,7 @@ struct swrt_ctx {
   KmapSeriesState kmap;
   TrackState trk;
   FlowSpecState flow;
+  CondSeriesState cond;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an
   // event marker, ~7 us of idle on each stream).  Only consecutive split

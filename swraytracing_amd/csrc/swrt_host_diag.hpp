@@ -1,12 +1,13 @@
-// swrt_host_diag.hpp — host side of the six device-side recorders: the ray
+// swrt_host_diag.hpp — host side of the seven device-side recorders: the ray
 // diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp), the
 // map series (swrt_map.hpp), the wave-vector plane series (swrt_kmap.hpp),
-// the track series (swrt_track.hpp) and the flow spectrum series
-// (swrt_flowspec.hpp).  Each appends frames to a Series of its
+// the track series (swrt_track.hpp), the flow spectrum series
+// (swrt_flowspec.hpp) and the conditional spectrum series (swrt_cond.hpp).
+// Each appends frames to a Series of its
 // state (swrt_ctx.hpp) without a host wait: a reserve, the launches that write
 // at the series' end, a commit.  The order below (ray, spectrum, map, k-plane,
-// track, flow) is the order their template kernels are first named in, hence
-// emitted in.
+// track, flow, conditional) is the order their template kernels are first
+// named in, hence emitted in.
 #pragma once
 #include <cmath>
 
@@ -19,6 +20,7 @@
 #include "swrt_kmap.hpp"
 #include "swrt_track.hpp"
 #include "swrt_flowspec.hpp"
+#include "swrt_cond.hpp"
 
 namespace {
 
@@ -385,6 +387,101 @@ int flow_spectrum_get(swrt_ctx* c, int64_t first, int64_t count, double* spectra
                              sizeof(double) * kFlowSpecStats * count, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SWRT_OK;
+}
+
+// ---- the conditional spectrum series ----
+// The records' common checks: an open series, then swrt_raydiag_record's.
+int cond_series_check(swrt_ctx* c, int nslots) {
+  if (!c->cond.open) return fail(c, SWRT_ERR_STATE, "call swrt_cond_series_begin first");
+  HIPCHK_RC(raydiag_check(c, nslots));
+  if (c->n > kCondMaxPackets) return fail(c, SWRT_ERR_ARG, "a conditional spectrum frame takes at most 2^24 packets");
+  return SWRT_OK;
+}
+
+// Room for `count` more frames, zeroed on the stream (counts, sums and
+// stats): the launches that fill them only add.
+int cond_reserve_zeroed(swrt_ctx* c, int64_t count) {
+  CondSeriesState& cs = c->cond;
+  const size_t fr = cs.frame(), tl = cs.tail();
+  HIPCHK_RC(series_reserve(c, cs.series, fr, tl, count, map_series_min(fr * sizeof(unsigned long long))));
+  HIPCHK(c, hipMemsetAsync(cs.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
+  HIPCHK(c, hipMemsetAsync(cs.series.end_b(tl), 0, sizeof(unsigned long long) * tl * count, c->stream));
+  return SWRT_OK;
+}
+
+// `count` frames from the series' end on: frame i from the packets at
+// x + i*stride, k + i*stride (any order) and the flow at alphas[i] (device;
+// NULL: `alpha` for every frame).  The LDS kernel while the count plane fits
+// a workgroup's LDS, the global one beyond (or when SWRT_DEBUG_COND_GLOBAL
+// says so).
+int cond_launch(swrt_ctx* c, int nslots, double alpha, const double* alphas, double bump, const double* x,
+                const double* k, int64_t stride, int64_t count) {
+  CondSeriesState& cs = c->cond;
+  CondArgs a;
+  a.f0 = view_of(c->slot[0]);
+  a.f1 = nslots == 2 ? view_of(c->slot[1]) : a.f0;
+  a.nslots = nslots;
+  a.alpha = alpha;
+  a.bump = bump;
+  a.alphas = alphas;
+  a.x = x;
+  a.k = k;
+  a.stride = stride;
+  a.n = c->n;
+  a.f2 = cs.f2;
+  a.Cg2 = cs.Cg2;
+  a.wedges = cs.edges.get();
+  a.qedges = cs.edges.get() + cs.nw + 1;
+  a.nw = cs.nw;
+  a.nq = cs.nq;
+  a.which = cs.which;
+  a.scale = std::ldexp(1.0, cs.frac_bits);
+  a.counts = cs.series.end_a(cs.frame());
+  a.tail = cs.series.end_b(cs.tail());
+  const bool lds = !c->dbg.cond_global && cs.frame() <= (size_t)kCondLdsCells;
+  const size_t bytes = cond_lds_bytes(cs.nw, cs.nq, lds);
+  if (bytes > ((size_t)64 << 10) && !cs.lds_attr) {  // (above 64 KB of dynamic LDS a kernel has to ask once)
+    constexpr int kMost = 128 << 10;  // edges 33 KB at most, sums 32 KB at most (never both), the plane 64 KB
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&cond_kernel<true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kMost));
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&cond_kernel<false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kMost));
+    cs.lds_attr = true;
+  }
+  const int most = bytes > kCondBigPlaneBytes ? kCondBigPlaneBlocks : kCondBlocks;
+  const int nblk = (int)std::min<int64_t>(most, nblocks(c->n, kCondThreads));
+  hipLaunchKernelGGL(lds ? cond_kernel<true> : cond_kernel<false>, dim3(nblk, (unsigned)count), dim3(kCondThreads),
+                     bytes, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  cs.series.ext.committed(count);
+  return SWRT_OK;
+}
+
+// Frames [first, first + count) to the host, synchronously; every output may
+// be NULL.  The sums and the stats share the series' second column.
+int cond_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                    int64_t* stats_out) {
+  const CondSeriesState& cs = c->cond;
+  HIPCHK_RC(frame_range_check(c, cs.series.ext, first, count, "frame range out of bounds"));
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t fr = cs.frame(), tl = cs.tail(), nqs = (size_t)cs.nq + 2;
+  std::vector<int64_t> tails;
+  if (counts_out)
+    HIPCHK(c, hipMemcpyAsync(counts_out, cs.series.a.get() + fr * first, sizeof(int64_t) * fr * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  if (sums_out || stats_out) {
+    tails.resize(tl * count);
+    HIPCHK(c, hipMemcpyAsync(tails.data(), cs.series.b.get() + tl * first, sizeof(int64_t) * tl * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int64_t t = 0; t < count && !tails.empty(); ++t) {
+    const int64_t* row = tails.data() + tl * t;
+    if (sums_out) std::copy(row, row + nqs, sums_out + nqs * t);
+    if (stats_out) std::copy(row + nqs, row + tl, stats_out + (size_t)kCondStats * t);
+  }
+  return dev_err_check(c);
 }
 
 }  // namespace

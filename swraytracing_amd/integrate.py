@@ -162,6 +162,48 @@ def kmap_moments(stats, frac_bits):
     return dict(n_used=n_used, mean=m1, cov=cov)
 
 
+def combine_conds(parts):
+    """The conditional spectrum series of an ensemble from its shards' series
+    (swrt_cond_series_*).  ``parts``: a sequence of (counts, sums, stats)
+    triples, one per shard, counts (T, nq + 2, nw + 2) int64, sums (T, nq + 2)
+    int64 and stats (T, 2) int64 [n, rejected]: the element-wise sum (integer,
+    exact and order-free).  A shard without packets stands as zeros."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no series to combine")
+    shapes = {tuple(np.shape(a) for a in p) for p in parts}
+    if len(shapes) != 1:
+        raise ValueError("every shard must give counts, sums and stats of the same shapes")
+    counts = np.stack([np.asarray(p[0], dtype=np.int64) for p in parts])
+    sums = np.stack([np.asarray(p[1], dtype=np.int64) for p in parts])
+    stats = np.stack([np.asarray(p[2], dtype=np.int64) for p in parts])
+    if counts.ndim != 4 or sums.shape != counts.shape[:3] or stats.shape != counts.shape[:2] + (2,):
+        raise ValueError("every shard must give counts (T, nq + 2, nw + 2), sums (T, nq + 2) and stats (T, 2)")
+    return counts.sum(axis=0), sums.sum(axis=0), stats.sum(axis=0)
+
+
+def cond_spectra(counts, sums, frac_bits):
+    """Conditional spectra of frames counts (..., nq + 2, nw + 2) and sums
+    (..., nq + 2) int64 as fp64: ``n`` (..., nq + 2) the packets of each q
+    class, ``spectrum`` (..., nq + 2, nw + 2) each class's omega row divided by
+    its n, ``omega_mean`` (..., nq + 2) the class's mean omega; the last two
+    NaN where the class is empty."""
+    counts = np.asarray(counts)
+    sums = np.asarray(sums)
+    if counts.ndim < 2 or sums.shape != counts.shape[:-1]:
+        raise ValueError("counts must be (..., nq + 2, nw + 2) and sums (..., nq + 2)")
+    if not 0 <= int(frac_bits) <= 32:
+        raise ValueError("frac_bits must be 0..32")
+    n = counts.sum(axis=-1).astype(np.float64)
+    empty = n == 0
+    count = np.where(empty, 1.0, n)
+    spectrum = counts.astype(np.float64) / count[..., None]
+    omega_mean = sums.astype(np.float64) / count * 2.0 ** -int(frac_bits)
+    spectrum[empty] = np.nan
+    omega_mean[empty] = np.nan
+    return dict(n=n, spectrum=spectrum, omega_mean=omega_mean)
+
+
 def track_ids_array(ids, n_total):
     """``ids`` as a checked int64 array: a one-dimensional, non-empty sequence
     of distinct integers in 0..n_total-1 (ValueError otherwise)."""
@@ -872,6 +914,140 @@ class PacketEnsemble:
                 st["kept"] = []
             with open(os.path.join(directory, "kmap_geom.bin"), "wb") as fh:
                 fh.write(np.array([st["K"], st["m"], st["frac_bits"]], dtype=np.float64).tobytes())
+        return st["frames"]
+
+    def begin_cond(self, omega_edges, which, q_edges, frac_bits=20, directory=None):
+        """Open the conditional spectrum series of this run
+        (swrt_cond_series_begin with the ensemble's f, Cg): omega classes over
+        ``omega_edges`` by the classes of the flow scalar ``which`` ("zeta",
+        "sigma" or "D") at the packets over ``q_edges``.  ``directory``: where
+        record_cond drains the device series when it grows large (default: the
+        drained frames wait in host memory for write_conds)."""
+        from ._lib import COND_WHICH
+        if which not in COND_WHICH:
+            raise ValueError('the conditioning scalar must be "zeta", "sigma" or "D"')
+        wedges = np.array(omega_edges, dtype=np.float64).ravel()
+        qedges = np.array(q_edges, dtype=np.float64).ravel()
+        for name, e in (("omega", wedges), ("q", qedges)):
+            if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+                raise ValueError(f"the {name} edges must be at least two finite increasing values")
+        frac_bits = int(frac_bits)
+        if not 0 <= frac_bits <= 32:
+            raise ValueError("conditional spectrum frac_bits must be 0..32")
+        if (qedges.size + 1) * (wedges.size + 1) > 65536:
+            raise ValueError("a conditional spectrum frame holds at most 65536 cells, (nq + 2) * (nw + 2)")
+        self._cond = dict(which=COND_WHICH[which], wedges=wedges, qedges=qedges, frac_bits=frac_bits,
+                          directory=directory, frames=0, pending=0, kept=[])
+        if self.n > 0:
+            self.ctx.cond_series_begin(self.f, self.Cg, wedges, COND_WHICH[which], qedges, frac_bits)
+
+    def record_cond(self, alpha=None):
+        """Append this shard's conditional spectrum frame at the current state
+        to the device-side series (queued, no host wait), in the flow of slot 0
+        (``alpha`` None) or of slots 0 and 1 blended at ``alpha``.  An empty
+        shard records nothing.  When the device series holds more than 256 MB
+        it is drained (get, combine, append, reset): a collective when
+        sharded, at the same frame on every rank."""
+        st = getattr(self, "_cond", None)
+        if st is None:
+            raise SwrtError("record_cond: call begin_cond first")
+        st["frames"] += 1
+        st["pending"] += 1
+        if self.n > 0:
+            if alpha is None:
+                self.ctx.cond_series_record(nslots=1, bump=self.bump)
+            else:
+                self.ctx.cond_series_record(nslots=2, alpha=alpha, bump=self.bump)
+        nqs, nws = st["qedges"].size + 1, st["wedges"].size + 1
+        if st["pending"] * 8 * (nqs * nws + nqs + 2) > MAP_DRAIN_BYTES:
+            self._drain_conds()
+
+    def _drain_conds(self):
+        """The frames on the device, summed over the shards, to the files or
+        the host list of rank 0; the device series emptied."""
+        st = self._cond
+        T, nqs, nws = st["pending"], st["qedges"].size + 1, st["wedges"].size + 1
+        if T == 0:
+            return
+        if self.n > 0:
+            part = self.ctx.cond_series_get(0, T)
+            self.ctx.cond_series_reset()
+        else:
+            part = (np.zeros((T, nqs, nws), dtype=np.int64), np.zeros((T, nqs), dtype=np.int64),
+                    np.zeros((T, 2), dtype=np.int64))
+        st["pending"] = 0
+        if self.world > 1:
+            import torch
+            import torch.distributed as dist
+
+            from .dist import _device_for
+            dev = _device_for(dist.get_backend())
+            gathered = []
+            for a in part:
+                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                out = [torch.empty_like(buf) for _ in range(self.world)]
+                dist.all_gather(out, buf)
+                gathered.append([o.cpu().numpy() for o in out])
+            if self.rank != 0:
+                return
+            part = combine_conds(zip(*gathered))
+        if st["directory"] is None:
+            st["kept"].append(part)
+        else:
+            self._append_conds(st["directory"], *part)
+
+    @staticmethod
+    def _append_conds(directory, counts, sums, stats):
+        with open(os.path.join(directory, "cond_hist.bin"), "ab") as fc, \
+                open(os.path.join(directory, "cond_sums.bin"), "ab") as fs, \
+                open(os.path.join(directory, "cond_stats.bin"), "ab") as ft:
+            for fr, s, t in zip(counts, sums, stats):
+                fc.write(np.ascontiguousarray(fr, dtype=np.int64).tobytes())  # (cell (qc, wc) at qc*(nw + 2) + wc)
+                fs.write(np.ascontiguousarray(s, dtype=np.int64).tobytes())
+                ft.write(np.ascontiguousarray(t, dtype=np.int64).tobytes())
+
+    def cond_series(self):
+        """(counts (T, nq + 2, nw + 2), sums (T, nq + 2), stats (T, 2)), all
+        int64, of the ensemble's frames still held (not yet drained into
+        files).  Sharded: a collective; rank 0 gets combine_conds() of the
+        shards' frames, the others None."""
+        st = getattr(self, "_cond", None)
+        if st is None:
+            raise SwrtError("cond_series: call begin_cond first")
+        if st["directory"] is not None:
+            raise ValueError("cond_series: begin_cond drains into a directory (read its files)")
+        self._drain_conds()
+        if self.rank != 0:
+            return None
+        nqs, nws = st["qedges"].size + 1, st["wedges"].size + 1
+        if not st["kept"]:
+            return (np.zeros((0, nqs, nws), dtype=np.int64), np.zeros((0, nqs), dtype=np.int64),
+                    np.zeros((0, 2), dtype=np.int64))
+        return tuple(np.concatenate([p[i] for p in st["kept"]]) for i in range(3))
+
+    def write_conds(self, directory):
+        """The run's conditional spectrum series as raw native-endian files:
+        cond_hist.bin (int64, one (nq + 2) x (nw + 2) plane per frame, cell
+        (qc, wc) at qc*(nw + 2) + wc), cond_sums.bin (nq + 2 int64 per frame),
+        cond_stats.bin (2 int64 per frame: n, rejected) and cond_geom.bin
+        (doubles [which, nq, nw, frac_bits], the nq + 1 q edges, the nw + 1
+        omega edges).  Sharded: a collective; rank 0 writes.  Returns the
+        frames recorded."""
+        st = getattr(self, "_cond", None)
+        if st is None:
+            raise SwrtError("write_conds: call begin_cond first")
+        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
+            raise ValueError("write_conds: begin_cond drained into another directory")
+        self._drain_conds()
+        if self.rank == 0:
+            if st["directory"] is None:
+                for part in st["kept"]:
+                    self._append_conds(directory, *part)
+                st["kept"] = []
+            with open(os.path.join(directory, "cond_geom.bin"), "wb") as fh:
+                head = np.array([st["which"], st["qedges"].size - 1, st["wedges"].size - 1, st["frac_bits"]],
+                                dtype=np.float64)
+                fh.write(np.concatenate([head, st["qedges"], st["wedges"]]).tobytes())
         return st["frames"]
 
     def begin_tracks(self, ids, directory=None):

@@ -302,7 +302,8 @@ def _fresh_outputs(out_dir, fresh):
         return
     for name in ("packet_x", "packet_k", "packet_time", "pv", "pv_time", "omega_hist", "omega_stats", "omega_edges",
                  "map_n", "map_omega", "map_k", "map_l", "map_stats", "track_x", "track_k", "track_diag", "track_time",
-                 "track_ids", "kmap_n", "kmap_stats", "kmap_geom", "flow_spec", "flow_stats", "flow_geom"):
+                 "track_ids", "kmap_n", "kmap_stats", "kmap_geom", "flow_spec", "flow_stats", "flow_geom", "cond_hist",
+                 "cond_sums", "cond_stats", "cond_geom"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
@@ -358,6 +359,30 @@ def _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits, ring_radius=None):
     return float(kmap_kmax), int(kmap_cells), int(kmap_frac_bits)
 
 
+def _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges):
+    """The drivers' ``cond_by`` / ``cond_edges`` / ``cond_frac_bits`` checked
+    before anything runs: (which, q edges, frac_bits), or None without
+    ``cond_by``.  The omega classes are the run's ``spectrum_edges``."""
+    if cond_by is None:
+        return None
+    if not isinstance(cond_by, str) or cond_by not in ("zeta", "sigma", "D"):
+        raise ValueError('cond_by must be None, "zeta", "sigma" or "D"')
+    if spectrum_edges is None:
+        raise ValueError("cond_by needs spectrum_edges: they are the conditional spectra's omega classes")
+    if cond_edges is None:
+        raise ValueError("cond_by needs cond_edges, the classes of the flow scalar")
+    edges = np.array(cond_edges, dtype=np.float64).ravel()
+    if edges.size < 2 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
+        raise ValueError("cond_edges must be at least two finite increasing values")
+    if isinstance(cond_frac_bits, (bool, np.bool_)) or not isinstance(cond_frac_bits, numbers.Real) \
+            or int(cond_frac_bits) != cond_frac_bits or not 0 <= int(cond_frac_bits) <= 32:
+        raise ValueError("cond_frac_bits must be an integer 0..32")
+    nw = np.asarray(spectrum_edges).size - 1
+    if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
+        raise ValueError("cond_edges: at most 4096 classes and (nq + 2) * (nbins + 2) <= 65536 cells a frame")
+    return cond_by, edges, int(cond_frac_bits)
+
+
 def _flow_args(flow_spectrum, Npackets):
     """The drivers' ``flow_spectrum`` checked before anything runs: its frames
     are the packet frames, so it needs packets."""
@@ -398,15 +423,19 @@ def _track_args(track_ids, track_every, Npackets, default_every):
     return ids, int(track_every)
 
 
-def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False):
-    """One packet frame: its spectrum, its map and its k-plane recorded on the device
-    (queued, no host wait) whether or not the frame itself is written."""
+def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False, conds=False):
+    """One packet frame: its spectrum, its map, its k-plane and its conditional
+    spectrum (in the flow of slot 0, the snapshot at the packets' time)
+    recorded on the device (queued, no host wait) whether or not the frame
+    itself is written."""
     if spectrum:
         ens.record_spectrum()
     if maps:
         ens.record_map()
     if kmaps:
         ens.record_kmap()
+    if conds:
+        ens.record_cond()
     ens.write_frame(t, out_dir, packet_files)
 
 
@@ -658,7 +687,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                   packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
                   pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None, packet_files=True,
                   map_cells=None, map_frac_bits=20, track_ids=None, track_every=None,
-                  kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False):
+                  kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False,
+                  cond_by=None, cond_edges=None, cond_frac_bits=20):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -713,15 +743,28 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     3*nshell per frame: E, Z, Q per shell), flow_stats.bin ([t, sum E, sum Z,
     sum Q] per frame; t lines up with packet_time.bin) and flow_geom.bin
     ([nx, nshell, k_scale, K_d2, layer]); no other output changes.
+    ``cond_by`` ("zeta", "sigma" or "D"; needs ``spectrum_edges`` and
+    ``cond_edges``, the nq + 1 increasing class edges of that scalar): beside
+    every packet frame but the first (written before any snapshot exists) the
+    counts of the packets over the omega classes of ``spectrum_edges`` by the
+    classes of the flow's vorticity, strain or Okubo-Weiss at each packet are
+    recorded on the device (swrt_cond_series_*; the snapshot at the packets'
+    time) and written as cond_hist.bin (int64, (nq + 2) x (nw + 2) per frame,
+    cell (qc, wc) at qc*(nw + 2) + wc), cond_sums.bin (nq + 2 int64 per frame:
+    the sum of rint(omega * 2^``cond_frac_bits``) per q class), cond_stats.bin
+    (n, rejected per frame) and cond_geom.bin (doubles: which, nq, nw,
+    frac_bits, the q edges, the omega edges); frame i belongs to packet frame
+    i + 1; no other output changes.
     Returns a dict of run facts (dt, Nsteps, steps run, frames written,
     final t, spectrum_frames, map_frames, track_frames, kmap_frames,
-    flow_frames)."""
+    flow_frames, cond_frames)."""
     _flow_args(flow_spectrum, Npackets)
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files, kmap_cells)
     map_args = _map_args(map_cells, map_frac_bits)
     kmap_args = _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits,
                            _ring_radius(near_inertial_factor, f, Cg) if kmap_cells is not None else None)
     track_args = _track_args(track_ids, track_every, Npackets, 5)  # (5: packet_steps_per_save below)
+    cond_args = _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
@@ -779,6 +822,9 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     kmaps = ens is not None and kmap_args is not None
     if kmaps:
         ens.begin_kmap(*kmap_args, directory=out_dir)
+    conds = ens is not None and cond_args is not None
+    if conds:  # (no frame beside the first packet frame: no snapshot exists yet)
+        ens.begin_cond(spectrum_edges, cond_args[0], cond_args[1], cond_args[2], directory=out_dir)
     tracks = ens is not None and track_args is not None
     if tracks:
         ens.begin_tracks(track_args[0], directory=out_dir)
@@ -816,7 +862,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                 ens.record_tracks(t, 1)
             if (step - packet_step_start + 1) % packet_steps_per_save == 0:
                 group.flush()
-                _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps)
+                _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps, conds)
                 if flows:
                     model.record_flow_spectrum()
                 frames += 1
@@ -834,6 +880,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     map_frames = ens.write_maps(out_dir) if maps else 0
     track_frames = ens.write_tracks(out_dir) if tracks else 0
     kmap_frames = ens.write_kmaps(out_dir) if kmaps else 0
+    cond_frames = ens.write_conds(out_dir) if conds else 0
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -843,7 +890,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     log.close()
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
-                track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames)
+                track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames)
 
 
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
@@ -851,7 +898,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                         packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
                         pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None,
                         packet_files=True, map_cells=None, map_frac_bits=20, track_ids=None, track_every=None,
-                        kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False):
+                        kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False,
+                        cond_by=None, cond_edges=None, cond_frac_bits=20):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
@@ -860,7 +908,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     ``packet_files``, ``map_cells``, ``map_frac_bits``, ``kmap_cells``,
     ``kmap_kmax``, ``kmap_frac_bits``, ``track_ids``,
     ``track_every`` (default: this driver's packet cadence, 25),
-    ``flow_spectrum``: as in :func:`qgsw_raytrace`.
+    ``flow_spectrum``, ``cond_by``, ``cond_edges``, ``cond_frac_bits``: as in
+    :func:`qgsw_raytrace`.
 
     Sharded (torch.distributed, world > 1): ``pde="owner"`` (default) — rank 0
     steps the PDE and sends each step's top-layer qk and dt to the other
@@ -876,6 +925,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     kmap_args = _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits,
                            _ring_radius(near_inertial_factor, f, Cg) if kmap_cells is not None else None)
     track_args = _track_args(track_ids, track_every, Npackets, 25)  # (25: packet_steps_per_save below)
+    cond_args = _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges)
     _flow_args(flow_spectrum, Npackets)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
@@ -925,6 +975,9 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     kmaps = ens is not None and kmap_args is not None
     if kmaps:
         ens.begin_kmap(*kmap_args, directory=out_dir)
+    conds = ens is not None and cond_args is not None
+    if conds:  # (no frame beside the first packet frame: no snapshot exists yet)
+        ens.begin_cond(spectrum_edges, cond_args[0], cond_args[1], cond_args[2], directory=out_dir)
     tracks = ens is not None and track_args is not None
     if tracks:
         ens.begin_tracks(track_args[0], directory=out_dir)
@@ -960,7 +1013,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
             ens.record_tracks(loop.t, 1)
         if active and (loop.steps - packet_step_start + 1) % packet_steps_per_save == 0:
             loop.flush()
-            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps)
+            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps, conds)
             if flows:
                 model.record_flow_spectrum()  # (the committed qk at loop.t; the next step is only speculative)
             frames += 1
@@ -973,6 +1026,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     map_frames = ens.write_maps(out_dir) if maps else 0
     track_frames = ens.write_tracks(out_dir) if tracks else 0
     kmap_frames = ens.write_kmaps(out_dir) if kmaps else 0
+    cond_frames = ens.write_conds(out_dir) if conds else 0
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -984,4 +1038,4 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     U0 = getattr(loop, "U0", U0)  # (a receiving rank never sees the owner's U0)
     return dict(dt=dt, dts=dts, Nsteps=Nsteps, steps=step, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
-                track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames)
+                track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames)
