@@ -690,6 +690,86 @@ int swrt_cond_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* c
 int swrt_cond_series_reset(swrt_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * The transition series: the energy-vs-omega distribution of the packets
+ * (analysis/load_data.m:33-52, the Energy_versus_omega_* figures) split by a
+ * source value the device keeps per packet, by ORIGINAL packet index: the
+ * packet's omega at an earlier mark (how energy moves along the omega axis,
+ * a two-time statistic) or any value the caller gives, such as the ring a
+ * packet started on (parameters.txt's near_inertial_factor sweep in one run).
+ *
+ * Per packet, with scale = 2^frac_bits:
+ *   omega = sqrt(f^2 + Cg^2 (k k + l l)), the spectrum series' bits;
+ *   s     = the source value of the packet;
+ *   d     = omega - s (one subtraction), d2 = d * d (one multiplication).
+ * A packet is rejected, and counted nowhere else, if omega, s or d is NaN or
+ * any of |omega * scale|, |d * scale|, |d2 * scale| is not below 2^38.
+ * Otherwise its source class is the spectrum series' rule over src_edges (a
+ * row [below, bin 0 .. bin ns-1, above], the last bin closed) and its omega
+ * class the same rule over omega_edges.  A frame holds
+ *   counts  (ns + 2) x (nw + 2) int64, source class major:
+ *           counts[sc * (nw + 2) + wc];
+ *   sums    (ns + 2) x 3 int64: per source class the sums of
+ *           rint(omega * scale), rint(d * scale) and rint(d2 * scale) (round
+ *           half even; signed sums in two's complement), so that the drift
+ *           <d> / tau and the diffusivity <d2> / (2 tau) follow per source
+ *           class, exact to the quantum;
+ *   stats   3 int64 [n, rejected, mark serial]; the serial counts the marks
+ *           since swrt_trans_series_begin.
+ * With n <= 2^24 every sum stays below 2^62.  Integer addition is exact and
+ * order-free: a frame depends on the packet set and the source values alone
+ * (a re-binning between the mark and the record, either advance call and
+ * either packet-stream setting give the same bits), and the frames of shards
+ * that marked together combine by adding.
+ * ------------------------------------------------------------------------- */
+
+/* Open a series: 1 <= nw, ns <= 4096 with (ns + 2) * (nw + 2) <= 65536 cells,
+ * both edge arrays finite and increasing, 0 <= frac_bits <= 32 (SWRT_ERR_ARG
+ * with a message otherwise).  Empties the series, drops the mark and sets the
+ * mark serial to 0. */
+int swrt_trans_series_begin(swrt_ctx* ctx, double f, double Cg, const double* omega_edges, int64_t nw,
+                            const double* src_edges, int64_t ns, int frac_bits);
+
+/* The source of every packet := its current omega (begin's f and Cg): queued
+ * on the packet stream after whatever last wrote the packets, no host wait
+ * (the first mark, or one for more packets, allocates).  The mark belongs to
+ * the packet set: swrt_packets_set drops it.  SWRT_ERR_STATE before begin;
+ * SWRT_ERR_ARG without packets or with more than 2^24. */
+int swrt_trans_series_mark(swrt_ctx* ctx);
+
+/* The source of the packet with original index i := v[i]; n must equal the
+ * packet count (SWRT_ERR_ARG).  NaN values are allowed: those packets are
+ * rejected at every record.  v is free on return. */
+int swrt_trans_series_mark_values(swrt_ctx* ctx, const double* v, int64_t n);
+
+/* Append the frame of the current packets against the mark: queued on the
+ * packet stream after whatever last wrote the packets, no host wait (growing
+ * the series past its capacity, which doubles, may wait for the stream).  Up
+ * to 16384 cells every workgroup counts into a private plane in LDS and adds
+ * its non-zero cells to the frame; beyond, every packet adds through global
+ * memory: the same integers.  SWRT_ERR_STATE before begin or without a valid
+ * mark; SWRT_ERR_ARG without packets or with more than 2^24. */
+int swrt_trans_series_record(swrt_ctx* ctx);
+
+/* One frame per history frame in [first, first + count), each joined to the
+ * current mark: the same bits as swrt_trans_series_record on packets set to
+ * that frame and marked alike.  A range out of bounds: SWRT_ERR_ARG. */
+int swrt_trans_series_record_history(swrt_ctx* ctx, int64_t first, int64_t count);
+
+/* Frames recorded since begin or the last reset; nw and ns of the open
+ * series, 0 if none (either pointer may be NULL). */
+int64_t swrt_trans_series_frames(const swrt_ctx* ctx);
+int swrt_trans_series_bins(const swrt_ctx* ctx, int64_t* nw_out, int64_t* ns_out);
+
+/* Frames [first, first + count): counts_out count x (ns + 2) x (nw + 2),
+ * sums_out count x (ns + 2) x 3 and stats3_out count x 3, frame-major.  Each
+ * may be NULL.  Waits for the frames. */
+int swrt_trans_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                          int64_t* stats3_out);
+
+/* Empty the series; the mark, its serial, the edges and frac_bits stay. */
+int swrt_trans_series_reset(swrt_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
  * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)
  * ------------------------------------------------------------------------ */
@@ -1126,7 +1206,10 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
  *   value gives the same integers.
  * SWRT_DEBUG_COND_GLOBAL 0 / 1 (default 0): 1 makes the conditional spectrum
  *   series' records take the global kernel for every shape
- *   (tools/cond_series_rate.py).  Both values give the same integers. */
+ *   (tools/cond_series_rate.py).  Both values give the same integers.
+ * SWRT_DEBUG_TRANS_GLOBAL 0 / 1 (default 0): 1 makes the transition series'
+ *   records take the global kernel for every shape
+ *   (tools/trans_series_rate.py).  Both values give the same integers. */
 #define SWRT_DEBUG_HAZARD_CHECK 1
 #define SWRT_DEBUG_SPIN_US 2
 #define SWRT_DEBUG_LEGACY_PARK 3
@@ -1146,6 +1229,7 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
 #define SWRT_DEBUG_MAP_STRAYS 18
 #define SWRT_DEBUG_KMAP_GLOBAL 19
 #define SWRT_DEBUG_COND_GLOBAL 20
+#define SWRT_DEBUG_TRANS_GLOBAL 21
 int swrt_debug_set(swrt_ctx* ctx, int key, int64_t value);
 int swrt_debug_get(swrt_ctx* ctx, int key, int64_t* value_out);
 

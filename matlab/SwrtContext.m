@@ -123,6 +123,51 @@ classdef SwrtContext < handle
             swrt_mex('cond_series_reset', obj.id());
         end
 
+        % The transition series on the device: per frame the int64 counts of
+        % the packets over omega classes (load_data.m:33-52; rows
+        % [below, bins, above] over omega_edges) by the classes of a source
+        % value kept per packet over src_edges (omega at the last mark, or
+        % the values given to mark_values, e.g. the ring a packet started
+        % on), per source class the sums of round(omega * 2^frac_bits),
+        % round(d * ...) and round(d^2 * ...) with d = omega - source, and
+        % [n; rejected; mark serial].
+        function trans_series_begin(obj, f, Cg, omega_edges, src_edges, frac_bits)
+            if nargin < 6, frac_bits = 20; end
+            swrt_mex('trans_series_begin', obj.id(), f, Cg, omega_edges, src_edges, frac_bits);
+        end
+
+        function trans_series_mark(obj)
+            swrt_mex('trans_series_mark', obj.id());
+        end
+
+        function trans_series_mark_values(obj, v)
+            % one value per packet, in the order of packets_set
+            swrt_mex('trans_series_mark_values', obj.id(), v);
+        end
+
+        function trans_series_record(obj)
+            swrt_mex('trans_series_record', obj.id());
+        end
+
+        function trans_series_record_history(obj, first, count)
+            % history frames first .. first+count-1, 0-based, against the current mark
+            swrt_mex('trans_series_record_history', obj.id(), first, count);
+        end
+
+        function n = trans_series_frames(obj)
+            n = swrt_mex('trans_series_frames', obj.id());
+        end
+
+        function [counts, sums, stats] = trans_series_get(obj)
+            % counts: int64 (nw+2) x (ns+2) x frames (first index the omega class);
+            % sums: int64 3 x (ns+2) x frames; stats: int64 3 x frames
+            [counts, sums, stats] = swrt_mex('trans_series_get', obj.id());
+        end
+
+        function trans_series_reset(obj)
+            swrt_mex('trans_series_reset', obj.id());
+        end
+
         % The wave-vector plane on the device (what raytracing_figures.m:19-26,
         % 76-83 scatter packet by packet): per frame an m x m int64 count
         % plane over [-K, K) x [-K, K), first index k, and eight int64 stats

@@ -61,6 +61,14 @@
 //   n = swrt_mex('cond_series_frames', h)
 //   [counts, sums, stats] = swrt_mex('cond_series_get', h)    % int64 (nw+2) x (nq+2) x frames, (nq+2) x frames, 2 x frames
 //   swrt_mex('cond_series_reset', h)
+//   swrt_mex('trans_series_begin', h, f, Cg, omega_edges, src_edges[, frac_bits])   % omega classes by a per-packet source value's classes
+//   swrt_mex('trans_series_mark', h)                          % source := the packets' omega now
+//   swrt_mex('trans_series_mark_values', h, v)                % source := v, one per packet in the original order
+//   swrt_mex('trans_series_record', h)
+//   swrt_mex('trans_series_record_history', h, first, count)
+//   n = swrt_mex('trans_series_frames', h)
+//   [counts, sums, stats] = swrt_mex('trans_series_get', h)   % int64 (nw+2) x (ns+2) x frames, 3 x (ns+2) x frames, 3 x frames
+//   swrt_mex('trans_series_reset', h)
 //   swrt_mex('track_begin', h, ids)                         % trajectories of chosen packets; ids 0-based doubles
 //   swrt_mex('track_record', h, f, gH, nslots, alpha, bump)   % nslots 0: no flow, Omega..D are NaN
 //   swrt_mex('track_record_history', h, first, count, f, gH, nslots, alphas, bump)   % alphas [] when nslots < 2
@@ -610,6 +618,59 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   if (!strcmp(cmd, "cond_series_reset")) {
     check(c, swrt_cond_series_reset(c), "swrt_cond_series_reset");
+    return;
+  }
+  if (!strcmp(cmd, "trans_series_begin")) {  // (f, Cg, omega_edges, src_edges[, frac_bits = 20])
+    need(na, 5, cmd);
+    const size_t ne = mxGetNumberOfElements(a[3]), nse = mxGetNumberOfElements(a[4]);
+    check(c, swrt_trans_series_begin(c, scalar(a[1]), scalar(a[2]), reals(a[3], "omega_edges"), (int64_t)ne - 1,
+                                     reals(a[4], "src_edges"), (int64_t)nse - 1, na > 5 ? (int)scalar(a[5]) : 20),
+          "swrt_trans_series_begin");
+    return;
+  }
+  if (!strcmp(cmd, "trans_series_mark")) {
+    check(c, swrt_trans_series_mark(c), "swrt_trans_series_mark");
+    return;
+  }
+  if (!strcmp(cmd, "trans_series_mark_values")) {  // (v): one value per packet, original order
+    need(na, 2, cmd);
+    check(c, swrt_trans_series_mark_values(c, reals(a[1], "v"), (int64_t)mxGetNumberOfElements(a[1])),
+          "swrt_trans_series_mark_values");
+    return;
+  }
+  if (!strcmp(cmd, "trans_series_record")) {
+    check(c, swrt_trans_series_record(c), "swrt_trans_series_record");
+    return;
+  }
+  if (!strcmp(cmd, "trans_series_record_history")) {  // (first, count)
+    need(na, 3, cmd);
+    check(c, swrt_trans_series_record_history(c, (int64_t)scalar(a[1]), (int64_t)scalar(a[2])),
+          "swrt_trans_series_record_history");
+    return;
+  }
+  if (!strcmp(cmd, "trans_series_frames")) {
+    plhs[0] = mxCreateDoubleScalar((double)swrt_trans_series_frames(c));
+    return;
+  }
+  if (!strcmp(cmd, "trans_series_get")) {  // -> counts (nw+2) x (ns+2) x frames, sums 3 x (ns+2) x frames, stats 3 x frames
+    const int64_t nf = swrt_trans_series_frames(c);
+    int64_t nw = 0, ns = 0;
+    check(c, swrt_trans_series_bins(c, &nw, &ns), "swrt_trans_series_bins");
+    const mwSize dims[3] = {(mwSize)(nw + 2), (mwSize)(ns + 2), (mwSize)nf},
+                 udims[3] = {3, (mwSize)(ns + 2), (mwSize)nf}, sdims[2] = {3, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(3, dims, mxINT64_CLASS, mxREAL);
+    mxArray* sums = mxCreateNumericArray(3, udims, mxINT64_CLASS, mxREAL);
+    mxArray* stats = mxCreateNumericArray(2, sdims, mxINT64_CLASS, mxREAL);
+    if (nf > 0)
+      check(c, swrt_trans_series_get(c, 0, nf, (int64_t*)mxGetInt64s(plhs[0]), (int64_t*)mxGetInt64s(sums),
+                                     (int64_t*)mxGetInt64s(stats)),
+            "swrt_trans_series_get");
+    if (nlhs > 1) plhs[1] = sums; else mxDestroyArray(sums);
+    if (nlhs > 2) plhs[2] = stats; else mxDestroyArray(stats);
+    return;
+  }
+  if (!strcmp(cmd, "trans_series_reset")) {
+    check(c, swrt_trans_series_reset(c), "swrt_trans_series_reset");
     return;
   }
   if (!strcmp(cmd, "track_begin")) {  // (ids): 0-based original packet indices, as doubles

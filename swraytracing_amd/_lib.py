@@ -114,6 +114,16 @@ SIGNATURES = {
     "swrt_cond_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                     ctypes.POINTER(ctypes.c_int64)]),
     "swrt_cond_series_reset": (_INT, [_VP]),
+    "swrt_trans_series_begin": (_INT, [_VP, _D, _D, _P, _I, _P, _I, _INT]),
+    "swrt_trans_series_mark": (_INT, [_VP]),
+    "swrt_trans_series_mark_values": (_INT, [_VP, _P, _I]),
+    "swrt_trans_series_record": (_INT, [_VP]),
+    "swrt_trans_series_record_history": (_INT, [_VP, _I, _I]),
+    "swrt_trans_series_frames": (_I, [_VP]),
+    "swrt_trans_series_bins": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_trans_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                     ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_trans_series_reset": (_INT, [_VP]),
     "swrt_track_begin": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64), _I]),
     "swrt_track_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
     "swrt_track_record_history": (_INT, [_VP, _I, _I, _D, _D, _INT, _P, _D]),
@@ -203,6 +213,7 @@ DEBUG_MAP_TILED_FRAMES = 17
 DEBUG_MAP_STRAYS = 18
 DEBUG_KMAP_GLOBAL = 19
 DEBUG_COND_GLOBAL = 20
+DEBUG_TRANS_GLOBAL = 21
 COND_WHICH = {"zeta": 0, "sigma": 1, "D": 2}  # swrt_cond_series_begin's ``which``
 
 _lib = None
@@ -736,6 +747,67 @@ class Context:
 
     def cond_series_reset(self):
         self._chk(self._L.swrt_cond_series_reset(self._h), "swrt_cond_series_reset")
+
+    # ---- the transition series (swrt_trans_series_*: omega classes by a per-packet source value's classes) ----
+    def trans_series_begin(self, f, Cg, omega_edges, src_edges, frac_bits=20):
+        """Open a series of (ns + 2) x (nw + 2) count planes: omega classes
+        over ``omega_edges`` (nw + 1 increasing values) by the classes of each
+        packet's source value over ``src_edges`` (ns + 1 increasing values);
+        the per-class sums quantised to 2^-frac_bits.  Empties the series and
+        drops the mark."""
+        wedges = _f64(np.asarray(omega_edges, dtype=np.float64).ravel())
+        sedges = _f64(np.asarray(src_edges, dtype=np.float64).ravel())
+        self._chk(self._L.swrt_trans_series_begin(self._h, float(f), float(Cg), _p(wedges), wedges.size - 1,
+                                                  _p(sedges), sedges.size - 1, int(frac_bits)),
+                  "swrt_trans_series_begin")
+
+    def trans_series_mark(self):
+        """Source of every packet := its current omega (queued; no host wait)."""
+        self._chk(self._L.swrt_trans_series_mark(self._h), "swrt_trans_series_mark")
+
+    def trans_series_mark_values(self, values):
+        """Source of the packet with original index i := ``values[i]``."""
+        v = _f64(np.asarray(values, dtype=np.float64).ravel())
+        self._chk(self._L.swrt_trans_series_mark_values(self._h, _p(v), v.size), "swrt_trans_series_mark_values")
+
+    def trans_series_record(self):
+        """Append the current packets' frame against the mark (queued; no host wait)."""
+        self._chk(self._L.swrt_trans_series_record(self._h), "swrt_trans_series_record")
+
+    def trans_series_record_history(self, first, count):
+        """One frame per history frame [first, first + count), joined to the current mark."""
+        self._chk(self._L.swrt_trans_series_record_history(self._h, int(first), int(count)),
+                  "swrt_trans_series_record_history")
+
+    def trans_series_frames(self):
+        return int(self._L.swrt_trans_series_frames(self._h))
+
+    def trans_series_bins(self):
+        """(nw, ns) of the open series, (0, 0) if none."""
+        nw, ns = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self._L.swrt_trans_series_bins(self._h, ctypes.byref(nw), ctypes.byref(ns)),
+                  "swrt_trans_series_bins")
+        return int(nw.value), int(ns.value)
+
+    def trans_series_get(self, first=0, count=None):
+        """Recorded frames [first, first + count) -> (counts (count, ns + 2,
+        nw + 2) int64, counts[t, sc, wc]; sums (count, ns + 2, 3) int64, per
+        source class the sums of rint(omega * 2^frac_bits), rint(d * ...) and
+        rint(d^2 * ...) with d = omega - source; stats (count, 3) int64
+        [n, rejected, mark serial])."""
+        count = self.trans_series_frames() - first if count is None else count
+        nw, ns = self.trans_series_bins()
+        counts = np.zeros((max(count, 0), ns + 2, nw + 2), dtype=np.int64)
+        sums = np.zeros((max(count, 0), ns + 2, 3), dtype=np.int64)
+        stats = np.zeros((max(count, 0), 3), dtype=np.int64)
+        i64 = ctypes.POINTER(ctypes.c_int64)
+        self._chk(self._L.swrt_trans_series_get(self._h, int(first), int(count), counts.ctypes.data_as(i64),
+                                                sums.ctypes.data_as(i64), stats.ctypes.data_as(i64)),
+                  "swrt_trans_series_get")
+        return counts, sums, stats
+
+    def trans_series_reset(self):
+        self._chk(self._L.swrt_trans_series_reset(self._h), "swrt_trans_series_reset")
 
     # ---- the track series (swrt_track_*: trajectories of chosen packets) ------
     def track_begin(self, ids):

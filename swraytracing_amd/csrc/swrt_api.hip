@@ -438,6 +438,7 @@ int swrt_packets_set(swrt_ctx* c, const double* x, const double* k, int64_t n) {
   if (!c->bins.buf) HIPCHK(c, c->bins.alloc());
   if (n != c->n) c->rd.drop();  // Omega_0 and the frame series belong to an ensemble of the old size
   if (n != c->n) c->trk.drop();  // (the tracked ids too)
+  c->trans.drop();  // the transition series' mark belongs to the packet set it was taken on
   c->n = n;
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(c->pk.cur.x.get(), x, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
@@ -1664,6 +1665,120 @@ int swrt_cond_series_reset(swrt_ctx* c) {
   return SWRT_OK;
 }
 
+// ---- the transition series (swrt_trans.hpp, swrt_host_diag.hpp) ----
+int swrt_trans_series_begin(swrt_ctx* c, double f, double Cg, const double* omega_edges, int64_t nw,
+                            const double* src_edges, int64_t ns, int frac_bits) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(omega_edges_check(c, omega_edges, nw));
+  HIPCHK_RC(omega_edges_check(c, src_edges, ns));
+  if ((ns + 2) * (nw + 2) > kTransMaxCells) return fail(c, SWRT_ERR_ARG, "(ns + 2) * (nw + 2) must be at most 65536");
+  if (frac_bits < 0 || frac_bits > kTransMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
+  HIPCHK(c, hipSetDevice(c->device));
+  TransSeriesState& ts = c->trans;
+  HIPCHK_RC(series_release(c, ts.series));  // (waits: queued records read the old edges too)
+  ts.open = false;
+  ts.marked = false;  // (a mark of omega belongs to the f and Cg it was taken with)
+  ts.serial = 0;
+  HIPCHK(c, ts.edges.alloc(nw + ns + 2));
+  HIPCHK(c, hipMemcpyAsync(ts.edges.get(), omega_edges, sizeof(double) * (nw + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(ts.edges.get() + nw + 1, src_edges, sizeof(double) * (ns + 1), hipMemcpyHostToDevice,
+                           c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  ts.nw = (int)nw;
+  ts.ns = (int)ns;
+  ts.frac_bits = frac_bits;
+  ts.f2 = f * f;
+  ts.Cg2 = Cg * Cg;
+  ts.open = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_trans_series_mark(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(trans_series_check(c, false));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(trans_src_reserve(c));
+  TransSeriesState& ts = c->trans;
+  hipLaunchKernelGGL(trans_mark_kernel, dim3(nblocks(c->n, kTransThreads)), dim3(kTransThreads), 0, c->stream,
+                     c->pk.cur.k.get(), c->pk.cur.perm.get(), c->n, ts.f2, ts.Cg2, ts.src.get());
+  HIPCHK(c, hipGetLastError());
+  ++ts.serial;
+  ts.marked = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_trans_series_mark_values(swrt_ctx* c, const double* v, int64_t n) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(trans_series_check(c, false));
+  if (n != c->n) return fail(c, SWRT_ERR_ARG, "one source value per packet: n must equal the packet count");
+  if (!v) return fail(c, SWRT_ERR_ARG, "NULL buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(trans_src_reserve(c));
+  TransSeriesState& ts = c->trans;
+  // (the stream orders the upload after the queued records that read the old mark)
+  HIPCHK(c, hipMemcpyAsync(ts.src.get(), v, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's buffer is free on return
+  ++ts.serial;
+  ts.marked = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_trans_series_record(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(trans_series_check(c, true));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(trans_reserve_zeroed(c, 1));
+  return trans_launch(c, c->pk.cur.k.get(), c->pk.cur.perm.get(), 0, 1);
+  GUARD_END(c)
+}
+
+int swrt_trans_series_record_history(swrt_ctx* c, int64_t first, int64_t count) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(trans_series_check(c, true));
+  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(trans_reserve_zeroed(c, count));
+  for (int64_t i = 0; i < count; i += kTransHistoryChunk) {
+    const int64_t nf = std::min<int64_t>(kTransHistoryChunk, count - i);
+    HIPCHK_RC(trans_launch(c, c->hist.b.get() + (first + i) * 2 * c->n, nullptr, 2 * c->n, nf));
+  }
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int64_t swrt_trans_series_frames(const swrt_ctx* c) { return c ? c->trans.series.ext.frames() : -1; }
+
+int swrt_trans_series_bins(const swrt_ctx* c, int64_t* nw_out, int64_t* ns_out) {
+  if (!c) return SWRT_ERR_ARG;
+  if (nw_out) *nw_out = c->trans.open ? c->trans.nw : 0;
+  if (ns_out) *ns_out = c->trans.open ? c->trans.ns : 0;
+  return SWRT_OK;
+}
+
+int swrt_trans_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                          int64_t* stats3_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  return trans_series_get(c, first, count, counts_out, sums_out, stats3_out);
+  GUARD_END(c)
+}
+
+int swrt_trans_series_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
+  c->trans.series.ext.cleared();
+  return SWRT_OK;
+}
+
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
@@ -1739,6 +1854,10 @@ int swrt_debug_set(swrt_ctx* c, int key, int64_t value) {
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "conditional spectrum path must be 0 or 1");
       c->dbg.cond_global = value != 0;
       return SWRT_OK;
+    case SWRT_DEBUG_TRANS_GLOBAL:
+      if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "transition series path must be 0 or 1");
+      c->dbg.trans_global = value != 0;
+      return SWRT_OK;
     case SWRT_DEBUG_QG_UPDATE_COLS:
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "QG update/column-pass fusion must be 0 or 1");
       if (c->qg.spec) return fail(c, SWRT_ERR_STATE, "a speculative QG step is pending (swrt_qg_resolve first)");
@@ -1778,6 +1897,7 @@ int swrt_debug_get(swrt_ctx* c, int key, int64_t* value_out) {
     case SWRT_DEBUG_MAP_TILED_FRAMES: *value_out = c->map.tiled_frames; return SWRT_OK;
     case SWRT_DEBUG_KMAP_GLOBAL: *value_out = c->dbg.kmap_path; return SWRT_OK;
     case SWRT_DEBUG_COND_GLOBAL: *value_out = c->dbg.cond_global ? 1 : 0; return SWRT_OK;
+    case SWRT_DEBUG_TRANS_GLOBAL: *value_out = c->dbg.trans_global ? 1 : 0; return SWRT_OK;
     case SWRT_DEBUG_MAP_STRAYS: {  // the device's counter: waits for the queued records
       unsigned long long v = 0;
       if (c->map.strays) {

@@ -420,6 +420,28 @@ struct CondSeriesState {
   size_t tail() const { return (size_t)nq + 4; }
 };
 
+// the transition series (swrt_trans_series_*, swrt_trans.hpp).  Buffers of its
+// own, as the other recorders'.  The mark (src, one value per packet by
+// original index) belongs to the packet set: swrt_packets_set drops it, the
+// recorded frames stay (each holds its n and its mark's serial).
+struct TransSeriesState {
+  bool open = false;        // swrt_trans_series_begin was called
+  bool marked = false;      // src holds a value for every packet of the current set
+  int nw = 0, ns = 0;       // omega and source bins of the open series
+  int frac_bits = 0;
+  double f2 = 0.0, Cg2 = 0.0;
+  int64_t serial = 0;       // marks since begin
+  DevBuf<double> edges;     // nw + 1 omega edges, then ns + 1 source edges
+  DevBuf<double> src;       // the source value by original packet index
+  int64_t scap = 0;         // packets src is sized for
+  bool lds_attr = false;    // the kernels' dynamic LDS limit was raised
+  // recorded frames: (ns + 2) x (nw + 2) counts each, and their 3 (ns + 2) sums followed by [n, rejected, serial]
+  Series<unsigned long long> series;
+  size_t frame() const { return (size_t)(ns + 2) * (nw + 2); }
+  size_t tail() const { return (size_t)3 * (ns + 2) + 3; }
+  void drop() { marked = false; }  // another packet set: the mark describes the old one
+};
+
 // debug knobs (swrt_debug_set): a spin kernel queued on every extra packet
 // stream before each of its part launches (adversarial overlap of consecutive
 // calls), and the pre-third-buffer ordering after a source-gather sort
@@ -431,6 +453,7 @@ struct DebugKnobs {
   int corrupt_count = 0;    // test-only: added to one tile count before the next scan (once)
   int kmap_path = 0;        // SWRT_DEBUG_KMAP_GLOBAL: 0 by m; 1 global; 2 / 3 global with / without the wave merge
   bool cond_global = false; // SWRT_DEBUG_COND_GLOBAL: the conditional spectrum series' global kernel for every shape
+  bool trans_global = false; // SWRT_DEBUG_TRANS_GLOBAL: the transition series' global kernel for every shape
 };
 }  // namespace
 
@@ -501,6 +524,7 @@ struct swrt_ctx {
   TrackState trk;
   FlowSpecState flow;
   CondSeriesState cond;
+  TransSeriesState trans;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an
   // event marker, ~7 us of idle on each stream).  Only consecutive split

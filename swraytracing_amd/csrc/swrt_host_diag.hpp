@@ -1,12 +1,13 @@
-// swrt_host_diag.hpp — host side of the seven device-side recorders: the ray
+// swrt_host_diag.hpp — host side of the eight device-side recorders: the ray
 // diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp), the
 // map series (swrt_map.hpp), the wave-vector plane series (swrt_kmap.hpp),
 // the track series (swrt_track.hpp), the flow spectrum series
-// (swrt_flowspec.hpp) and the conditional spectrum series (swrt_cond.hpp).
+// (swrt_flowspec.hpp), the conditional spectrum series (swrt_cond.hpp) and
+// the transition series (swrt_trans.hpp).
 // Each appends frames to a Series of its
 // state (swrt_ctx.hpp) without a host wait: a reserve, the launches that write
 // at the series' end, a commit.  The order below (ray, spectrum, map, k-plane,
-// track, flow, conditional) is the order their template kernels are first
+// track, flow, conditional, transition) is the order their template kernels are first
 // named in, hence emitted in.
 #pragma once
 #include <cmath>
@@ -21,6 +22,7 @@
 #include "swrt_track.hpp"
 #include "swrt_flowspec.hpp"
 #include "swrt_cond.hpp"
+#include "swrt_trans.hpp"
 
 namespace {
 
@@ -480,6 +482,109 @@ int cond_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_o
     const int64_t* row = tails.data() + tl * t;
     if (sums_out) std::copy(row, row + nqs, sums_out + nqs * t);
     if (stats_out) std::copy(row + nqs, row + tl, stats_out + (size_t)kCondStats * t);
+  }
+  return dev_err_check(c);
+}
+
+// ---- the transition series ----
+// The records' common checks: an open series, packets, a valid mark.
+int trans_series_check(swrt_ctx* c, bool need_mark) {
+  if (!c->trans.open) return fail(c, SWRT_ERR_STATE, "call swrt_trans_series_begin first");
+  HIPCHK_RC(packets_check(c));
+  if (c->n > kTransMaxPackets) return fail(c, SWRT_ERR_ARG, "a transition frame takes at most 2^24 packets");
+  if (need_mark && !c->trans.marked)
+    return fail(c, SWRT_ERR_STATE, "no mark for this packet set (swrt_trans_series_mark or _mark_values first)");
+  return SWRT_OK;
+}
+
+// Room in src for every packet of the set.  Growing releases the old buffer,
+// which waits for its queued readers; the old mark is gone either way.
+int trans_src_reserve(swrt_ctx* c) {
+  TransSeriesState& ts = c->trans;
+  ts.marked = false;
+  if (c->n <= ts.scap) return SWRT_OK;
+  ts.scap = 0;
+  HIPCHK(c, ts.src.alloc(c->n));
+  ts.scap = c->n;
+  if (c->hz.on) c->hz.name(ts.src.get(), "transition source values");
+  return SWRT_OK;
+}
+
+// Room for `count` more frames, zeroed on the stream (counts, sums and
+// stats): the launches that fill them only add.
+int trans_reserve_zeroed(swrt_ctx* c, int64_t count) {
+  TransSeriesState& ts = c->trans;
+  const size_t fr = ts.frame(), tl = ts.tail();
+  HIPCHK_RC(series_reserve(c, ts.series, fr, tl, count, map_series_min(fr * sizeof(unsigned long long))));
+  HIPCHK(c, hipMemsetAsync(ts.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
+  HIPCHK(c, hipMemsetAsync(ts.series.end_b(tl), 0, sizeof(unsigned long long) * tl * count, c->stream));
+  return SWRT_OK;
+}
+
+// `count` frames from the series' end on: frame i from the k at k + i*stride
+// in the order `perm` names (NULL: the original order), joined to the mark.
+// The LDS kernel while the count plane fits a workgroup's LDS, the global one
+// beyond (or when SWRT_DEBUG_TRANS_GLOBAL says so).
+int trans_launch(swrt_ctx* c, const double* k, const int* perm, int64_t stride, int64_t count) {
+  TransSeriesState& ts = c->trans;
+  TransArgs a;
+  a.k = k;
+  a.perm = perm;
+  a.src = ts.src.get();
+  a.stride = stride;
+  a.n = c->n;
+  a.f2 = ts.f2;
+  a.Cg2 = ts.Cg2;
+  a.wedges = ts.edges.get();
+  a.sedges = ts.edges.get() + ts.nw + 1;
+  a.nw = ts.nw;
+  a.ns = ts.ns;
+  a.scale = std::ldexp(1.0, ts.frac_bits);
+  a.serial = (unsigned long long)ts.serial;
+  a.counts = ts.series.end_a(ts.frame());
+  a.tail = ts.series.end_b(ts.tail());
+  const bool lds = !c->dbg.trans_global && ts.frame() <= (size_t)kCondLdsCells;
+  const size_t bytes = trans_lds_bytes(ts.nw, ts.ns, lds);
+  if (bytes > ((size_t)64 << 10) && !ts.lds_attr) {  // (above 64 KB of dynamic LDS a kernel has to ask once)
+    constexpr int kMost = 128 << 10;  // edges 33 KB at most, sums 24 KB at most, the plane 64 KB
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&trans_kernel<true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kMost));
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&trans_kernel<false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kMost));
+    ts.lds_attr = true;
+  }
+  const int most = bytes > kTransBigPlaneBytes ? kTransBigPlaneBlocks : kTransBlocks;
+  const int nblk = (int)std::min<int64_t>(most, nblocks(c->n, kTransThreads));
+  hipLaunchKernelGGL(lds ? trans_kernel<true> : trans_kernel<false>, dim3(nblk, (unsigned)count), dim3(kTransThreads),
+                     bytes, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  ts.series.ext.committed(count);
+  return SWRT_OK;
+}
+
+// Frames [first, first + count) to the host, synchronously; every output may
+// be NULL.  The sums and the stats share the series' second column.
+int trans_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                     int64_t* stats_out) {
+  const TransSeriesState& ts = c->trans;
+  HIPCHK_RC(frame_range_check(c, ts.series.ext, first, count, "frame range out of bounds"));
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t fr = ts.frame(), tl = ts.tail(), nsum = (size_t)kTransSums * (ts.ns + 2);
+  std::vector<int64_t> tails;
+  if (counts_out)
+    HIPCHK(c, hipMemcpyAsync(counts_out, ts.series.a.get() + fr * first, sizeof(int64_t) * fr * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  if (sums_out || stats_out) {
+    tails.resize(tl * count);
+    HIPCHK(c, hipMemcpyAsync(tails.data(), ts.series.b.get() + tl * first, sizeof(int64_t) * tl * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int64_t t = 0; t < count && !tails.empty(); ++t) {
+    const int64_t* row = tails.data() + tl * t;
+    if (sums_out) std::copy(row, row + nsum, sums_out + nsum * t);
+    if (stats_out) std::copy(row + nsum, row + tl, stats_out + (size_t)kTransStats * t);
   }
   return dev_err_check(c);
 }

@@ -204,6 +204,64 @@ def cond_spectra(counts, sums, frac_bits):
     return dict(n=n, spectrum=spectrum, omega_mean=omega_mean)
 
 
+def combine_transitions(parts):
+    """The transition series of an ensemble from its shards' series
+    (swrt_trans_series_*).  ``parts``: a sequence of (counts, sums, stats)
+    triples, one per shard, counts (T, ns + 2, nw + 2) int64, sums
+    (T, ns + 2, 3) int64 and stats (T, 3) int64 [n, rejected, mark serial]:
+    counts, sums, n and rejected add (integer, exact and order-free); the
+    serial is the shards' common one.  Frames whose shards marked a different
+    number of times describe different lags and are refused.  A shard without
+    packets stands as zeros (its serial does not count)."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no series to combine")
+    shapes = {tuple(np.shape(a) for a in p) for p in parts}
+    if len(shapes) != 1:
+        raise ValueError("every shard must give counts, sums and stats of the same shapes")
+    counts = np.stack([np.asarray(p[0], dtype=np.int64) for p in parts])
+    sums = np.stack([np.asarray(p[1], dtype=np.int64) for p in parts])
+    stats = np.stack([np.asarray(p[2], dtype=np.int64) for p in parts])
+    if counts.ndim != 4 or sums.shape != counts.shape[:3] + (3,) or stats.shape != counts.shape[:2] + (3,):
+        raise ValueError("every shard must give counts (T, ns + 2, nw + 2), sums (T, ns + 2, 3) and stats (T, 3)")
+    holds = stats[..., 0] > 0                       # (shard, frame): the shard had packets
+    serial = np.where(holds, stats[..., 2], 0).max(axis=0)
+    if np.any(holds & (stats[..., 2] != serial[None, :])):
+        raise ValueError("the shards' mark serials differ: their frames describe different marks")
+    out = stats.sum(axis=0)
+    out[..., 2] = serial
+    return counts.sum(axis=0), sums.sum(axis=0), out
+
+
+def trans_moments(counts, sums, frac_bits):
+    """Per source class of frames counts (..., ns + 2, nw + 2) and sums
+    (..., ns + 2, 3) int64, as fp64: ``n`` (..., ns + 2) the packets of the
+    class, ``omega_mean``, ``delta_mean`` and ``delta_var`` (..., ns + 2) the
+    means of omega and of d = omega - source and the variance <d^2> - <d>^2
+    (each mean exact to the quantum 2^-frac_bits), ``spectrum``
+    (..., ns + 2, nw + 2) the class's omega row divided by its n: the
+    conditional spectrum, a row of the propagator.  All but ``n`` are NaN where
+    the class is empty.  The drift is delta_mean / tau and the diffusivity
+    (delta_var + delta_mean^2) / (2 tau) for the lag tau of the frame."""
+    counts = np.asarray(counts)
+    sums = np.asarray(sums)
+    if counts.ndim < 2 or sums.shape != counts.shape[:-1] + (3,):
+        raise ValueError("counts must be (..., ns + 2, nw + 2) and sums (..., ns + 2, 3)")
+    if not 0 <= int(frac_bits) <= 32:
+        raise ValueError("frac_bits must be 0..32")
+    unit = 2.0 ** -int(frac_bits)
+    n = counts.sum(axis=-1).astype(np.float64)
+    empty = n == 0
+    count = np.where(empty, 1.0, n)
+    spectrum = counts.astype(np.float64) / count[..., None]
+    omega_mean = sums[..., 0].astype(np.float64) * unit / count
+    delta_mean = sums[..., 1].astype(np.float64) * unit / count
+    delta_var = sums[..., 2].astype(np.float64) * unit / count - delta_mean * delta_mean
+    for a in (spectrum, omega_mean, delta_mean, delta_var):
+        a[empty] = np.nan
+    return dict(n=n, omega_mean=omega_mean, delta_mean=delta_mean, delta_var=delta_var, spectrum=spectrum)
+
+
 def track_ids_array(ids, n_total):
     """``ids`` as a checked int64 array: a one-dimensional, non-empty sequence
     of distinct integers in 0..n_total-1 (ValueError otherwise)."""
@@ -1048,6 +1106,167 @@ class PacketEnsemble:
                 head = np.array([st["which"], st["qedges"].size - 1, st["wedges"].size - 1, st["frac_bits"]],
                                 dtype=np.float64)
                 fh.write(np.concatenate([head, st["qedges"], st["wedges"]]).tobytes())
+        return st["frames"]
+
+    def begin_trans(self, omega_edges, src_edges, frac_bits=20, by=0, directory=None):
+        """Open the transition series of this run (swrt_trans_series_begin
+        with the ensemble's f, Cg): omega classes over ``omega_edges`` by the
+        classes of each packet's source value over ``src_edges``.  ``by`` (0:
+        the source is omega at a mark, 1: a ring index) only goes into
+        trans_geom.bin.  ``directory``: where record_trans drains the device
+        series when it grows large (default: the drained frames wait in host
+        memory for write_trans)."""
+        wedges = np.array(omega_edges, dtype=np.float64).ravel()
+        sedges = np.array(src_edges, dtype=np.float64).ravel()
+        for name, e in (("omega", wedges), ("source", sedges)):
+            if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+                raise ValueError(f"the {name} edges must be at least two finite increasing values")
+        frac_bits = int(frac_bits)
+        if not 0 <= frac_bits <= 32:
+            raise ValueError("transition series frac_bits must be 0..32")
+        if (sedges.size + 1) * (wedges.size + 1) > 65536:
+            raise ValueError("a transition frame holds at most 65536 cells, (ns + 2) * (nw + 2)")
+        if by not in (0, 1):
+            raise ValueError("by must be 0 (omega at the mark) or 1 (ring)")
+        self._trans = dict(wedges=wedges, sedges=sedges, frac_bits=frac_bits, by=int(by), directory=directory,
+                           frames=0, pending=0, kept=[], times=[], t_mark=None)
+        if self.n > 0:
+            self.ctx.trans_series_begin(self.f, self.Cg, wedges, sedges, frac_bits)
+
+    def mark_trans(self, values=None, t=None):
+        """Set every packet's source value: its current omega (``values``
+        None; queued, no host wait) or ``values``, one per packet of the
+        **whole** ensemble in the original order (a shard takes its own).
+        ``t``: the time of the mark, kept for trans_time.bin.  Every rank
+        calls it at the same frame, so the shards' mark serials agree."""
+        st = getattr(self, "_trans", None)
+        if st is None:
+            raise SwrtError("mark_trans: call begin_trans first")
+        if values is not None:
+            values = np.asarray(values, dtype=np.float64).ravel()
+            if values.size != self.n_total:
+                raise ValueError("mark_trans: one source value per packet of the whole ensemble")
+            lo, hi = self.bounds[self.rank] if self.bounds is not None else (0, self.n_total)
+            values = values[lo:hi]
+        if self.n > 0:
+            if values is None:
+                self.ctx.trans_series_mark()
+            else:
+                self.ctx.trans_series_mark_values(values)
+        st["t_mark"] = np.nan if t is None else float(t)
+
+    def record_trans(self, t=None):
+        """Append this shard's transition frame at the current state to the
+        device-side series (queued, no host wait).  An empty shard records
+        nothing.  When the device series holds more than 256 MB it is drained
+        (get, combine, append, reset; the mark stays): a collective when
+        sharded, at the same frame on every rank."""
+        st = getattr(self, "_trans", None)
+        if st is None:
+            raise SwrtError("record_trans: call begin_trans first")
+        if st["t_mark"] is None:
+            raise SwrtError("record_trans: call mark_trans first")
+        st["frames"] += 1
+        st["pending"] += 1
+        st["times"].append((np.nan if t is None else float(t), st["t_mark"]))
+        if self.n > 0:
+            self.ctx.trans_series_record()
+        nss, nws = st["sedges"].size + 1, st["wedges"].size + 1
+        if st["pending"] * 8 * (nss * nws + 3 * nss + 3) > MAP_DRAIN_BYTES:
+            self._drain_trans()
+
+    def _drain_trans(self):
+        """The frames on the device, combined over the shards, to the files or
+        the host list of rank 0; the device series emptied."""
+        st = self._trans
+        T, nss, nws = st["pending"], st["sedges"].size + 1, st["wedges"].size + 1
+        if T == 0:
+            return
+        if self.n > 0:
+            part = self.ctx.trans_series_get(0, T)
+            self.ctx.trans_series_reset()
+        else:
+            part = (np.zeros((T, nss, nws), dtype=np.int64), np.zeros((T, nss, 3), dtype=np.int64),
+                    np.zeros((T, 3), dtype=np.int64))
+        st["pending"] = 0
+        times, st["times"] = np.array(st["times"], dtype=np.float64).reshape(T, 2), []
+        if self.world > 1:
+            import torch
+            import torch.distributed as dist
+
+            from .dist import _device_for
+            dev = _device_for(dist.get_backend())
+            gathered = []
+            for a in part:
+                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                out = [torch.empty_like(buf) for _ in range(self.world)]
+                dist.all_gather(out, buf)
+                gathered.append([o.cpu().numpy() for o in out])
+            if self.rank != 0:
+                return
+            part = combine_transitions(zip(*gathered))
+        part = tuple(part) + (times,)
+        if st["directory"] is None:
+            st["kept"].append(part)
+        else:
+            self._append_trans(st["directory"], *part)
+
+    @staticmethod
+    def _append_trans(directory, counts, sums, stats, times):
+        with open(os.path.join(directory, "trans_hist.bin"), "ab") as fc, \
+                open(os.path.join(directory, "trans_sums.bin"), "ab") as fs, \
+                open(os.path.join(directory, "trans_stats.bin"), "ab") as ft, \
+                open(os.path.join(directory, "trans_time.bin"), "ab") as fm:
+            for fr, s, t, tm in zip(counts, sums, stats, times):
+                fc.write(np.ascontiguousarray(fr, dtype=np.int64).tobytes())  # (cell (sc, wc) at sc*(nw + 2) + wc)
+                fs.write(np.ascontiguousarray(s, dtype=np.int64).tobytes())
+                ft.write(np.ascontiguousarray(t, dtype=np.int64).tobytes())
+                fm.write(np.ascontiguousarray(tm, dtype=np.float64).tobytes())
+
+    def trans_series(self):
+        """(counts (T, ns + 2, nw + 2), sums (T, ns + 2, 3), stats (T, 3)), all
+        int64, and times (T, 2) fp64 [t, t_mark] of the ensemble's frames still
+        held (not yet drained into files).  Sharded: a collective; rank 0 gets
+        combine_transitions() of the shards' frames, the others None."""
+        st = getattr(self, "_trans", None)
+        if st is None:
+            raise SwrtError("trans_series: call begin_trans first")
+        if st["directory"] is not None:
+            raise ValueError("trans_series: begin_trans drains into a directory (read its files)")
+        self._drain_trans()
+        if self.rank != 0:
+            return None
+        nss, nws = st["sedges"].size + 1, st["wedges"].size + 1
+        if not st["kept"]:
+            return (np.zeros((0, nss, nws), dtype=np.int64), np.zeros((0, nss, 3), dtype=np.int64),
+                    np.zeros((0, 3), dtype=np.int64), np.zeros((0, 2)))
+        return tuple(np.concatenate([p[i] for p in st["kept"]]) for i in range(4))
+
+    def write_trans(self, directory):
+        """The run's transition series as raw native-endian files:
+        trans_hist.bin (int64, one (ns + 2) x (nw + 2) plane per frame, cell
+        (sc, wc) at sc*(nw + 2) + wc), trans_sums.bin (3 (ns + 2) int64 per
+        frame: per source class the sums of omega, d and d^2 in quanta),
+        trans_stats.bin (3 int64 per frame: n, rejected, mark serial),
+        trans_time.bin (2 doubles per frame: t, t_mark) and trans_geom.bin
+        (doubles [ns, nw, frac_bits, by], the ns + 1 source edges, the nw + 1
+        omega edges).  Sharded: a collective; rank 0 writes.  Returns the
+        frames recorded."""
+        st = getattr(self, "_trans", None)
+        if st is None:
+            raise SwrtError("write_trans: call begin_trans first")
+        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
+            raise ValueError("write_trans: begin_trans drained into another directory")
+        self._drain_trans()
+        if self.rank == 0:
+            if st["directory"] is None:
+                for part in st["kept"]:
+                    self._append_trans(directory, *part)
+                st["kept"] = []
+            with open(os.path.join(directory, "trans_geom.bin"), "wb") as fh:
+                head = np.array([st["sedges"].size - 1, st["wedges"].size - 1, st["frac_bits"], st["by"]],
+                                dtype=np.float64)
+                fh.write(np.concatenate([head, st["sedges"], st["wedges"]]).tobytes())
         return st["frames"]
 
     def begin_tracks(self, ids, directory=None):

@@ -230,11 +230,48 @@ def initial_q(nx, L, a_g, K_d2, k_min, k_max, rng, ndgrid=False):
     return a_g / np.sqrt((U ** 2 + V ** 2).max()) * q
 
 
+def _ring_factors(near_inertial_factor):
+    """``near_inertial_factor`` as (factors, several): a scalar is one ring on
+    today's path; a sequence of R factors (parameters.txt sweeps 2, 4, 8, 16
+    over one PDE) puts R rings into one run."""
+    if np.ndim(near_inertial_factor) == 0:
+        return [near_inertial_factor], False
+    factors = [float(v) for v in np.asarray(near_inertial_factor, dtype=np.float64).ravel()]
+    if not factors or not all(math.isfinite(v) and v > 1 for v in factors):
+        raise ValueError("near_inertial_factor: a scalar or a non-empty sequence of finite factors above 1")
+    return factors, True
+
+
+def _ring_bounds(N, R):
+    """Ring r of R holds the packets [r * N // R, (r + 1) * N // R)."""
+    return [(r * N // R, (r + 1) * N // R) for r in range(R)]
+
+
+def _ring_index(N, R):
+    """The ring of every packet, as doubles (the source values of trans_by="ring")."""
+    ring = np.empty(N, dtype=np.float64)
+    for r, (lo, hi) in enumerate(_ring_bounds(N, R)):
+        ring[lo:hi] = r
+    return ring
+
+
 def _packets(N, L, near_inertial_factor, f, Cg, rng):
-    """qgsw_raytrace.m:54-60."""
-    wf = math.sqrt((near_inertial_factor ** 2 - 1) * f ** 2 / Cg ** 2)
-    i = np.arange(1, N + 1, dtype=np.float64)
-    k = np.stack([wf * np.cos(2 * np.pi * i / N), wf * np.sin(2 * np.pi * i / N)], axis=1)
+    """qgsw_raytrace.m:54-60.  With a sequence of R factors the packets go to
+    R rings in contiguous blocks (_ring_bounds), ring r with the radius of
+    factor r and the angles 2 pi j / N_r, j = 1..N_r: qgsw_raytrace.m's formula
+    per ring.  The positions take the same draws either way."""
+    factors, several = _ring_factors(near_inertial_factor)
+    if not several:
+        wf = math.sqrt((near_inertial_factor ** 2 - 1) * f ** 2 / Cg ** 2)
+        i = np.arange(1, N + 1, dtype=np.float64)
+        k = np.stack([wf * np.cos(2 * np.pi * i / N), wf * np.sin(2 * np.pi * i / N)], axis=1)
+    else:
+        k = np.empty((N, 2), dtype=np.float64)
+        for fac, (lo, hi) in zip(factors, _ring_bounds(N, len(factors))):
+            wf = _ring_radius(fac, f, Cg)
+            j = np.arange(1, hi - lo + 1, dtype=np.float64)
+            k[lo:hi, 0] = wf * np.cos(2 * np.pi * j / (hi - lo))
+            k[lo:hi, 1] = wf * np.sin(2 * np.pi * j / (hi - lo))
     x = L * rng.random((N, 2)) - L / 2
     return x, k
 
@@ -303,7 +340,8 @@ def _fresh_outputs(out_dir, fresh):
     for name in ("packet_x", "packet_k", "packet_time", "pv", "pv_time", "omega_hist", "omega_stats", "omega_edges",
                  "map_n", "map_omega", "map_k", "map_l", "map_stats", "track_x", "track_k", "track_diag", "track_time",
                  "track_ids", "kmap_n", "kmap_stats", "kmap_geom", "flow_spec", "flow_stats", "flow_geom", "cond_hist",
-                 "cond_sums", "cond_stats", "cond_geom"):
+                 "cond_sums", "cond_stats", "cond_geom", "trans_hist", "trans_sums", "trans_stats", "trans_time",
+                 "trans_geom"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
@@ -383,6 +421,58 @@ def _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges):
     return cond_by, edges, int(cond_frac_bits)
 
 
+def _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, nrings):
+    """The drivers' ``trans_src_edges`` / ``trans_by`` / ``trans_lag`` /
+    ``trans_frac_bits`` checked before anything runs: (by, source edges, lag,
+    frac_bits), or None without the first two.  The omega classes are the
+    run's ``spectrum_edges``."""
+    if trans_src_edges is None and trans_by is None:
+        if trans_lag is not None:
+            raise ValueError("trans_lag needs trans_src_edges")
+        return None
+    if trans_by not in (None, "omega", "ring"):
+        raise ValueError('trans_by must be None, "omega" or "ring"')
+    if spectrum_edges is None:
+        raise ValueError("the transition series needs spectrum_edges: they are its omega classes")
+    if trans_by == "ring":
+        if trans_src_edges is not None:
+            raise ValueError('trans_by="ring" sets its own source edges: leave trans_src_edges out')
+        if trans_lag is not None:
+            raise ValueError('trans_by="ring" is never re-marked: leave trans_lag out')
+        edges = np.arange(nrings + 1, dtype=np.float64) - 0.5
+    else:
+        if trans_src_edges is None:
+            raise ValueError('trans_by="omega" needs trans_src_edges, the classes of omega at the mark')
+        edges = np.array(trans_src_edges, dtype=np.float64).ravel()
+        if edges.size < 2 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
+            raise ValueError("trans_src_edges must be at least two finite increasing values")
+    if trans_lag is not None and (isinstance(trans_lag, (bool, np.bool_)) or not isinstance(trans_lag, numbers.Integral)
+                                  or trans_lag < 1):
+        raise ValueError("trans_lag must be None or an integer >= 1")
+    if isinstance(trans_frac_bits, (bool, np.bool_)) or not isinstance(trans_frac_bits, numbers.Real) \
+            or int(trans_frac_bits) != trans_frac_bits or not 0 <= int(trans_frac_bits) <= 32:
+        raise ValueError("trans_frac_bits must be an integer 0..32")
+    nw = np.asarray(spectrum_edges).size - 1
+    if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
+        raise ValueError("the transition series: at most 4096 source classes and (ns + 2) * (nbins + 2) <= 65536 "
+                         "cells a frame")
+    return (1 if trans_by == "ring" else 0), edges, (None if trans_lag is None else int(trans_lag)), \
+        int(trans_frac_bits)
+
+
+def _begin_trans(ens, trans_args, spectrum_edges, out_dir, t, Npackets, nrings):
+    """Open the run's transition series and take its first mark, at the first
+    packet frame (time t)."""
+    by, edges, _, frac_bits = trans_args
+    ens.begin_trans(spectrum_edges, edges, frac_bits, by=by, directory=out_dir)
+    ens.mark_trans(_ring_index(Npackets, nrings) if by == 1 else None, t=t)
+
+
+def _rings_line(factors, f, Cg):
+    """The one extra log line of a run with several rings."""
+    return "Rings: " + ", ".join(f"omega0 = {fac * f:g} (radius {_ring_radius(fac, f, Cg):g})" for fac in factors)
+
+
 def _flow_args(flow_spectrum, Npackets):
     """The drivers' ``flow_spectrum`` checked before anything runs: its frames
     are the packet frames, so it needs packets."""
@@ -423,11 +513,13 @@ def _track_args(track_ids, track_every, Npackets, default_every):
     return ids, int(track_every)
 
 
-def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False, conds=False):
-    """One packet frame: its spectrum, its map, its k-plane and its conditional
-    spectrum (in the flow of slot 0, the snapshot at the packets' time)
-    recorded on the device (queued, no host wait) whether or not the frame
-    itself is written."""
+def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False, conds=False, trans=None, index=0):
+    """One packet frame: its spectrum, its map, its k-plane, its conditional
+    spectrum (in the flow of slot 0, the snapshot at the packets' time) and its
+    transition frame recorded on the device (queued, no host wait) whether or
+    not the frame itself is written.  ``trans``: the run's lag (0: never
+    re-marked); packet frame ``index`` records against the mark, and re-marks
+    after the record when the lag divides its index."""
     if spectrum:
         ens.record_spectrum()
     if maps:
@@ -436,6 +528,10 @@ def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False
         ens.record_kmap()
     if conds:
         ens.record_cond()
+    if trans is not None:
+        ens.record_trans(t)
+        if trans and index % trans == 0:
+            ens.mark_trans(t=t)
     ens.write_frame(t, out_dir, packet_files)
 
 
@@ -688,7 +784,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                   pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None, packet_files=True,
                   map_cells=None, map_frac_bits=20, track_ids=None, track_every=None,
                   kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False,
-                  cond_by=None, cond_edges=None, cond_frac_bits=20):
+                  cond_by=None, cond_edges=None, cond_frac_bits=20,
+                  trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -755,16 +852,39 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     (n, rejected per frame) and cond_geom.bin (doubles: which, nq, nw,
     frac_bits, the q edges, the omega edges); frame i belongs to packet frame
     i + 1; no other output changes.
+    ``near_inertial_factor`` may be a sequence of R factors: the packets start
+    on R rings in contiguous blocks [r N // R, (r + 1) N // R), one PDE run
+    carrying the reference's whole omega0 sweep (the packets do not interact);
+    a scalar takes exactly the one-ring path.  The parameter block keeps the
+    first ring's value and one line after it lists all rings.
+    ``trans_src_edges`` (the ns + 1 increasing class edges of omega at the
+    mark; needs ``spectrum_edges``) or ``trans_by="ring"`` (source = the ring
+    index, edges -0.5 .. R - 0.5, never re-marked): the transition series
+    (swrt_trans_series_*).  The mark is taken at the first packet frame, every
+    later packet frame records the counts of the packets over (source class,
+    omega class) with the per-class sums of omega, d = omega - source and d^2
+    in quanta of 2^-``trans_frac_bits``, and with ``trans_lag`` = m the source
+    is re-marked after the record of every packet frame whose index m divides.
+    Written as trans_hist.bin (int64, (ns + 2) x (nw + 2) per frame),
+    trans_sums.bin (3 (ns + 2) int64), trans_stats.bin (n, rejected, mark
+    serial), trans_time.bin (doubles t, t_mark) and trans_geom.bin (doubles:
+    ns, nw, frac_bits, by (0 omega / 1 ring), the source edges, the omega
+    edges); frame i belongs to packet frame i + 1; no other output changes and
+    ``packet_files=False`` is allowed with it.
     Returns a dict of run facts (dt, Nsteps, steps run, frames written,
     final t, spectrum_frames, map_frames, track_frames, kmap_frames,
-    flow_frames, cond_frames)."""
+    flow_frames, cond_frames, trans_frames)."""
     _flow_args(flow_spectrum, Npackets)
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files, kmap_cells)
     map_args = _map_args(map_cells, map_frac_bits)
+    ring_factors, several_rings = _ring_factors(near_inertial_factor)
     kmap_args = _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits,
-                           _ring_radius(near_inertial_factor, f, Cg) if kmap_cells is not None else None)
+                           _ring_radius(max(ring_factors), f, Cg) if kmap_cells is not None else None)
     track_args = _track_args(track_ids, track_every, Npackets, 5)  # (5: packet_steps_per_save below)
     cond_args = _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges)
+    trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
+    if trans_args is not None and Npackets <= 0:
+        raise ValueError("the transition series needs packets")
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
@@ -800,8 +920,10 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     dt = CFL_fraction * dx / U0
     Nsteps = math.ceil(T / dt)
     packet_step_start = math.ceil(packet_delay / dt)
-    log(parameter_block(nx, Npackets, near_inertial_factor * f, dt, T, packet_delay, steps_per_save,
+    log(parameter_block(nx, Npackets, ring_factors[0] * f, dt, T, packet_delay, steps_per_save,
                         packet_steps_per_save, f, Cg, U_g, U0, Fr, K_d2))
+    if several_rings:
+        log(_rings_line(ring_factors, f, Cg))
     ens = PacketEnsemble(x, k, L, f, Cg, nx, K_d2, shear=0.0, k_scale=1.0, nlayers=1, bump=BUMP_QG, ctx=ctx,
                          shard=(rank, world), bounds=bounds) \
         if Npackets > 0 else None
@@ -825,6 +947,11 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     conds = ens is not None and cond_args is not None
     if conds:  # (no frame beside the first packet frame: no snapshot exists yet)
         ens.begin_cond(spectrum_edges, cond_args[0], cond_args[1], cond_args[2], directory=out_dir)
+    trans = None  # (the lag, 0: never re-marked; None: no transition series)
+    if ens is not None and trans_args is not None:  # (the mark beside the first packet frame; frames from the second on)
+        _begin_trans(ens, trans_args, spectrum_edges, out_dir, dt * (packet_step_start - 1), Npackets,
+                     len(ring_factors))
+        trans = trans_args[2] or 0
     tracks = ens is not None and track_args is not None
     if tracks:
         ens.begin_tracks(track_args[0], directory=out_dir)
@@ -862,7 +989,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                 ens.record_tracks(t, 1)
             if (step - packet_step_start + 1) % packet_steps_per_save == 0:
                 group.flush()
-                _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps, conds)
+                _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames)
                 if flows:
                     model.record_flow_spectrum()
                 frames += 1
@@ -881,6 +1008,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     track_frames = ens.write_tracks(out_dir) if tracks else 0
     kmap_frames = ens.write_kmaps(out_dir) if kmaps else 0
     cond_frames = ens.write_conds(out_dir) if conds else 0
+    trans_frames = ens.write_trans(out_dir) if trans is not None else 0
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -890,7 +1018,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     log.close()
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
-                track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames)
+                track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames,
+                trans_frames=trans_frames)
 
 
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
@@ -899,7 +1028,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                         pde="owner", owner_weight=None, link_buffers="auto", spectrum_edges=None,
                         packet_files=True, map_cells=None, map_frac_bits=20, track_ids=None, track_every=None,
                         kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False,
-                        cond_by=None, cond_edges=None, cond_frac_bits=20):
+                        cond_by=None, cond_edges=None, cond_frac_bits=20,
+                        trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
@@ -908,7 +1038,9 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     ``packet_files``, ``map_cells``, ``map_frac_bits``, ``kmap_cells``,
     ``kmap_kmax``, ``kmap_frac_bits``, ``track_ids``,
     ``track_every`` (default: this driver's packet cadence, 25),
-    ``flow_spectrum``, ``cond_by``, ``cond_edges``, ``cond_frac_bits``: as in
+    ``flow_spectrum``, ``cond_by``, ``cond_edges``, ``cond_frac_bits``,
+    ``trans_src_edges``, ``trans_by``, ``trans_lag``, ``trans_frac_bits`` and a
+    sequence of factors as ``near_inertial_factor``: as in
     :func:`qgsw_raytrace`.
 
     Sharded (torch.distributed, world > 1): ``pde="owner"`` (default) — rank 0
@@ -922,10 +1054,14 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     gloo; "device" / "host" to force one)."""
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files, kmap_cells)
     map_args = _map_args(map_cells, map_frac_bits)
+    ring_factors, several_rings = _ring_factors(near_inertial_factor)
     kmap_args = _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits,
-                           _ring_radius(near_inertial_factor, f, Cg) if kmap_cells is not None else None)
+                           _ring_radius(max(ring_factors), f, Cg) if kmap_cells is not None else None)
     track_args = _track_args(track_ids, track_every, Npackets, 25)  # (25: packet_steps_per_save below)
     cond_args = _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges)
+    trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
+    if trans_args is not None and Npackets <= 0:
+        raise ValueError("the transition series needs packets")
     _flow_args(flow_spectrum, Npackets)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
@@ -960,8 +1096,10 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     dt = CFL_fraction * dx / U0
     Nsteps = math.ceil(T / dt)
     packet_step_start = math.ceil(packet_delay_steps / dt)
-    log(parameter_block(nx, Npackets, near_inertial_factor * f, dt, T, packet_delay_steps, steps_per_save,
+    log(parameter_block(nx, Npackets, ring_factors[0] * f, dt, T, packet_delay_steps, steps_per_save,
                         packet_steps_per_save, f, Cg, U_g, U0, Fr, K_d2, two_layer=True))
+    if several_rings:
+        log(_rings_line(ring_factors, f, Cg))
     ens = PacketEnsemble(x, k, L, f, Cg, nx, K_d2, shear=shear, k_scale=2 * math.pi / L, nlayers=2,
                          bump=BUMP_QG, ctx=ctx, shard=(rank, world), bounds=bounds) if Npackets > 0 else None
     t = 0.0
@@ -978,6 +1116,11 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     conds = ens is not None and cond_args is not None
     if conds:  # (no frame beside the first packet frame: no snapshot exists yet)
         ens.begin_cond(spectrum_edges, cond_args[0], cond_args[1], cond_args[2], directory=out_dir)
+    trans = None  # (the lag, 0: never re-marked; None: no transition series)
+    if ens is not None and trans_args is not None:  # (the mark beside the first packet frame; frames from the second on)
+        _begin_trans(ens, trans_args, spectrum_edges, out_dir, dt * (packet_step_start - 1), Npackets,
+                     len(ring_factors))
+        trans = trans_args[2] or 0
     tracks = ens is not None and track_args is not None
     if tracks:
         ens.begin_tracks(track_args[0], directory=out_dir)
@@ -1013,7 +1156,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
             ens.record_tracks(loop.t, 1)
         if active and (loop.steps - packet_step_start + 1) % packet_steps_per_save == 0:
             loop.flush()
-            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps, conds)
+            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames)
             if flows:
                 model.record_flow_spectrum()  # (the committed qk at loop.t; the next step is only speculative)
             frames += 1
@@ -1027,6 +1170,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     track_frames = ens.write_tracks(out_dir) if tracks else 0
     kmap_frames = ens.write_kmaps(out_dir) if kmaps else 0
     cond_frames = ens.write_conds(out_dir) if conds else 0
+    trans_frames = ens.write_trans(out_dir) if trans is not None else 0
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -1038,4 +1182,5 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     U0 = getattr(loop, "U0", U0)  # (a receiving rank never sees the owner's U0)
     return dict(dt=dt, dts=dts, Nsteps=Nsteps, steps=step, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
-                track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames)
+                track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames,
+                trans_frames=trans_frames)
