@@ -57,7 +57,8 @@ __global__ void __launch_bounds__(256) bin_count_kernel(BinGeom g, const double*
 
 constexpr int kOrderBuckets = 16;  // workgroup rounds told apart by the tile order
 
-// Pass 2: exclusive scan of counts -> cursor (single workgroup, nbins <= 16384).
+// Pass 2: exclusive scan of counts -> cursor (single workgroup of 1024 threads,
+// nbins <= 16384; wave shuffles, one barrier).
 // Also clears counts (each thread its own bins, after reading them) so the next
 // fused count in the tile kernel starts from zero without a memset launch.
 // Guard: the counts must be >= 0 and sum to n (the packets binned).  If not
@@ -76,9 +77,10 @@ constexpr int kOrderBuckets = 16;  // workgroup rounds told apart by the tile or
 __global__ void __launch_bounds__(1024) bin_scan_kernel(int* counts, int nbins, int* cursor,
                                                         int* starts, int64_t n, int* err, int* order = nullptr,
                                                         int lanes = 512) {
-  __shared__ int part[1024];
+  __shared__ int wtot[16];  // the 16 waves' sums
   const int per = (nbins + 1023) / 1024;
   const int b0 = threadIdx.x * per;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   int s = 0;
   int neg = 0;
   for (int i = 0; i < per; ++i) {
@@ -89,16 +91,26 @@ __global__ void __launch_bounds__(1024) bin_scan_kernel(int* counts, int nbins, 
       s += c;
     }
   }
-  part[threadIdx.x] = s;
-  neg = __syncthreads_or(neg);
-  // Hillis-Steele inclusive scan over the 1024 partials
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int v = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-    __syncthreads();
-    part[threadIdx.x] += v;
-    __syncthreads();
+  // inclusive scan of the 1024 partials: each wave scans its 64 with
+  // shuffles, then every wave scans the 16 wave sums for itself (one barrier)
+  int incl = s;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int v = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += v;
   }
-  if (neg || (int64_t)part[1023] != n) {
+  if (lane == 63) wtot[wave] = incl;
+  neg = __syncthreads_or(neg);
+  const int wt = lane < 16 ? wtot[lane] : 0;
+  int wincl = wt;
+#pragma unroll
+  for (int off = 1; off < 16; off <<= 1) {
+    const int v = __shfl_up(wincl, off, 64);
+    if (lane >= off) wincl += v;
+  }
+  const int total = __shfl(wincl, 15, 64);
+  incl += __shfl(wincl - wt, wave, 64);  // + the sums of the waves below
+  if (neg || (int64_t)total != n) {
     for (int b = threadIdx.x; b < nbins; b += blockDim.x) {
       cursor[b] = (int)n;
       starts[b] = 0;
@@ -113,7 +125,7 @@ __global__ void __launch_bounds__(1024) bin_scan_kernel(int* counts, int nbins, 
       for (int b = threadIdx.x; b < nbins; b += blockDim.x) order[b] = b;
     return;
   }
-  int run = threadIdx.x ? part[threadIdx.x - 1] : 0;
+  int run = incl - s;
   for (int i = 0; i < per; ++i) {
     const int b = b0 + i;
     if (b < nbins) {
@@ -123,10 +135,9 @@ __global__ void __launch_bounds__(1024) bin_scan_kernel(int* counts, int nbins, 
       counts[b] = 0;
     }
   }
-  if (threadIdx.x == 1023) starts[nbins] = part[1023];
+  if (threadIdx.x == 1023) starts[nbins] = total;
   if (order == nullptr) return;
   __syncthreads();  // every start written (workgroup scope)
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (nbins % 8 != 0) {
     for (int b = threadIdx.x; b < nbins; b += blockDim.x) order[b] = b;
     return;
@@ -162,8 +173,10 @@ __global__ void __launch_bounds__(1024) bin_scan_kernel(int* counts, int nbins, 
   }
 }
 
-// Pass 3: scatter.  Each block ranks its packets per bin in LDS, reserves one
-// contiguous range per occupied bin with a single global atomic, then writes.
+// Pass 3: scatter.  Each block ranks its packets per bin in LDS (one atomic
+// per run of equal keys in a wave), reserves one contiguous range per occupied
+// bin with a single global atomic, then writes.  The order of the packets
+// inside a bin is free (perm carries their identity).
 // INDEX: write only the source index of every destination slot (src[d] = p,
 // 4 B instead of the 36 B packet): the next tile launch reads its packets
 // through it and writes them in binned order itself.
@@ -178,16 +191,29 @@ __global__ void __launch_bounds__(256) bin_scatter_kernel(const double* x, const
   for (int b = threadIdx.x; b < nbins; b += blockDim.x) cnt[b] = 0;
   __syncthreads();
   const int64_t b0 = (int64_t)blockIdx.x * blockDim.x * kBinPerThread;
+  // Rank by runs: the input is in the previous binning's order, so the keys
+  // of consecutive packets (the lanes of a wave) mostly agree.  The head lane
+  // of each run of equal keys takes one LDS atomic for the whole run and every
+  // lane of the run the head's base plus its offset in the run.  The shuffles
+  // and the ballot run in all 64 lanes (packets beyond n carry key -1, which
+  // ends a run and takes no atomic).
+  const int lane = threadIdx.x & 63;
+  const uint64_t upto = (2ull << lane) - 1;  // lanes 0..lane (all ones for lane 63)
   int key[kBinPerThread], local[kBinPerThread];
 #pragma unroll
   for (int q = 0; q < kBinPerThread; ++q) {
     const int64_t p = b0 + (int64_t)q * blockDim.x + threadIdx.x;
-    key[q] = 0;
-    local[q] = 0;
-    if (p < n) {
-      key[q] = keys[p];
-      local[q] = atomicAdd(&cnt[key[q]], 1);
-    }
+    key[q] = p < n ? keys[p] : -1;
+    const int prev = __shfl_up(key[q], 1, 64);
+    const bool head = lane == 0 || prev != key[q];
+    const uint64_t heads = __ballot(head);
+    const int hl = 63 - __clzll((long long)(heads & upto));  // this lane's run head (bit 0 is always set)
+    const uint64_t above = heads & ~upto;
+    const int next = above ? __ffsll((unsigned long long)above) - 1 : 64;  // the next run's head
+    int base_q = 0;
+    if (head && key[q] >= 0) base_q = atomicAdd(&cnt[key[q]], next - lane);
+    local[q] = __shfl(base_q, hl, 64) + (lane - hl);
+    if (key[q] < 0) key[q] = 0;
   }
   __syncthreads();
   for (int b = threadIdx.x; b < nbins; b += blockDim.x) {

@@ -70,6 +70,9 @@ FieldView view_of(const Slot& s) {
   v.ipx = (int)s.nx;
   v.ipy = (int)s.ny_period;
   v.inv_dx = 1.0 / v.dx;
+  const auto pow2 = [](int p) { return p > 0 && (p & (p - 1)) == 0; };
+  v.inv_exact = pow2(v.ipx) && pow2(v.ipy);
+  v.ywrap1 = v.ipy == v.nx;
   return v;
 }
 

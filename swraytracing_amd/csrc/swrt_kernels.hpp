@@ -33,6 +33,9 @@ struct FieldView {
   double inv_px, inv_py;
   int ipx, ipy;          // the periods as ints
   double inv_dx;        // RN(1/dx): locality keys, and x/dx via div_rn (correctly rounded)
+  // launch-uniform short paths of cell_frac (view_of; 0 = the general path):
+  int inv_exact;        // px and py are powers of two: inv_px and inv_py are exact
+  int ywrap1;           // ipy == nx: one wrap reduces the y cell (ipx == nx always)
 };
 
 // a / b correctly rounded (== IEEE a/b) from rb = RN(1/b), in one multiply
@@ -183,10 +186,24 @@ __device__ __forceinline__ int cvt_i32_sat(double v) {
 // two inv_period is exact, q0 = q*inv_period is already the quotient and the
 // correction adds r = 0 (a zero of either sign gives the same cell and
 // offset), so no per-lane select between a plain multiply and div_rn is needed.
-__device__ __forceinline__ int cell_frac(double x, double dx, double inv_dx, double period,
-                                         double inv_period, int iperiod, int nx, double& a) {
+// exact_inv (uniform; the caller's promise that the period is a power of two)
+// skips that correction: the fused q0 + (q - q0*period)*inv_period rounds the
+// exact q/period, which q0 already is.  one_wrap (uniform; iperiod == nx):
+// c <= nx, so the first unsigned-min subtraction already reduces it.
+//
+// Split in two so that stencil_at corrects both directions' quotients under
+// one branch: cell_quot gives q = x/dx and q0 = q*inv_period, cell_quot_fix
+// the correctly rounded q/period from them, cell_tail the cell and offset.
+__device__ __forceinline__ double cell_quot(double x, double dx, double inv_dx, double inv_period, double& r) {
   const double q = div_rn(x, dx, inv_dx);
-  const double r = div_rn(q, period, inv_period);
+  r = q * inv_period;
+  return q;
+}
+__device__ __forceinline__ double cell_quot_fix(double q, double r, double period, double inv_period) {
+  return __builtin_fma(__builtin_fma(-r, period, q), inv_period, r);  // div_rn(q, period, inv_period)
+}
+__device__ __forceinline__ int cell_tail(double q, double r, double period, int iperiod, int nx, double& a,
+                                         bool one_wrap) {
   const double xl = q - floor(r) * period;   // MATLAB mod (a - floor(a/m)*m)
   const double fl = floor(xl);
   a = (1.0 + xl) - (1.0 + fl);
@@ -200,9 +217,18 @@ __device__ __forceinline__ int cell_frac(double x, double dx, double inv_dx, dou
   // subtractions (c - nx wraps above c when c < nx) reduce c <= 3nx - 1;
   // wider generic periods (uniform) take the integer remainder.
   c = (int)min((unsigned)c, (unsigned)(c - nx));
+  if (one_wrap) return c;
   c = (int)min((unsigned)c, (unsigned)(c - nx));
   if (iperiod >= 3 * nx) c %= nx;
   return c;
+}
+__device__ __forceinline__ int cell_frac(double x, double dx, double inv_dx, double period,
+                                         double inv_period, int iperiod, int nx, double& a,
+                                         bool exact_inv = false, bool one_wrap = false) {
+  double r;
+  const double q = cell_quot(x, dx, inv_dx, inv_period, r);
+  if (!exact_inv) r = cell_quot_fix(q, r, period, inv_period);
+  return cell_tail(q, r, period, iperiod, nx, a, one_wrap);
 }
 
 // x / d for a small integer constant d, correctly rounded (== IEEE x/d).
@@ -248,12 +274,62 @@ constexpr double kScale() {
   return c;
 }
 
+
+// kScale<I> carried by the running product itself instead of a trailing
+// multiply.  Its magnitude 2^-e rides in the constants of weight I's first
+// Markstein step (divisor A in {3, 5}):
+//   q0' = x*(R*2^-e);  r = fma(-q0', A*2^e, x);  q' = fma(r, R*2^-e, q0'),
+// where q0' = 2^-e*q0 and q0'*(A*2^e) = q0*A exactly, so r is the same exact
+// remainder and q' = 2^-e*q: the scaling by a power of two commutes with
+// every rounding, here and in the later steps, under the same stays-normal
+// argument as above.  A zero x gives q' = +0 like the unscaled step.  Its
+// sign is the negated operand of the last step's multiply, (-w)*t == -(w*t)
+// for every operand; for the three weights with a negative kScale that last
+// step has a power-of-two divisor, so no Markstein step (which turns a zero
+// of either sign into +0) comes after the negation and the sign of a zero
+// weight stays what w*kScale gives.
+// Weight I = 1 keeps its trailing multiply: its only Markstein step is the
+// first of the product, and with a = 2^-1074 and bump = 0 the later factor
+// t = a drives the product subnormal, where scaling before and after the
+// rounding differ (-0 against -2^-1073).  cell_frac never produces that
+// offset (its a is a multiple of 2^-53), but the weights stay equal to the
+// trailing-multiply form on every input of tests/test_weight_scale_fold.py.
+template <int I>
+constexpr bool fold_scale() { return I != 1; }
+template <int I>
+constexpr int fold_step() {  // the first step of weight I with divisor odd part 3 or 5
+  for (int j = -2; j <= 3; ++j)
+    if (j != I && odd_part(j - I) != 1) return j;
+  return 99;
+}
+template <int I>
+constexpr int last_step() { return I == 3 ? 2 : 3; }
+constexpr double abs_c(double v) { return v < 0 ? -v : v; }
+
+// S * (x / A) for A in {3, 5} and S = 2^-e: div_const's Markstein step with
+// the scale in its constants.
+template <int A>
+__device__ __forceinline__ double div_const_scaled(double x, double S) {
+  static_assert(A == 3 || A == 5, "divisor");
+  const double R = (1.0 / (double)A) * S;  // RN(1/A) * 2^-e, exact
+  const double q0 = x * R;
+  const double r = __builtin_fma(-q0, (double)A / S, x);
+  return __builtin_fma(r, R, q0);
+}
+
 template <int I, int J>
 __device__ __forceinline__ double wstep(double w, const double* t) {
   if constexpr (I == J) {
     return w;
   } else {
-    return div_const<odd_part(J - I)>(w * t[J + 2]);
+    constexpr double S = kScale<I>();
+    constexpr bool neg = fold_scale<I>() && S < 0 && J == last_step<I>();
+    static_assert(!neg || odd_part(J - I) == 1, "the sign rides on a step without a Markstein correction");
+    const double x = neg ? (-w) * t[J + 2] : w * t[J + 2];
+    if constexpr (fold_scale<I>() && J == fold_step<I>())
+      return div_const_scaled<odd_part(J - I)>(x, abs_c(S));
+    else
+      return div_const<odd_part(J - I)>(x);
   }
 }
 
@@ -267,7 +343,7 @@ __device__ __forceinline__ double lagrange_wi(const double* t) {
   w = wstep<I, 2>(w, t);
   w = wstep<I, 3>(w, t);
   constexpr double S = kScale<I>();
-  return S == 1.0 ? w : w * S;
+  return (fold_scale<I>() || S == 1.0) ? w : w * S;
 }
 
 __device__ __forceinline__ void lagrange_w(double a, double bump, double w[kNT]) {
@@ -304,8 +380,18 @@ struct Stencil {
 __device__ __forceinline__ void stencil_at(const FieldView& fv, double x, double y, double bump,
                                            Stencil& s) {
   double ax, ay;
-  s.ic = cell_frac(x, fv.dx, fv.inv_dx, fv.px, fv.inv_px, fv.ipx, fv.nx, ax);
-  s.jc = cell_frac(y, fv.dx, fv.inv_dx, fv.py, fv.inv_py, fv.ipy, fv.nx, ay);
+  // (the x period of a FieldView is nx: view_of, so x takes one wrap)
+  double rx, ry;
+  const double qx = cell_quot(x, fv.dx, fv.inv_dx, fv.inv_px, rx);
+  const double qy = cell_quot(y, fv.dx, fv.inv_dx, fv.inv_py, ry);
+  if (!fv.inv_exact) {
+    rx = cell_quot_fix(qx, rx, fv.px, fv.inv_px);
+    ry = cell_quot_fix(qy, ry, fv.py, fv.inv_py);
+    // (a real uniform branch: as a per-lane select both forms would be computed)
+    asm volatile("" : "+v"(rx), "+v"(ry));
+  }
+  s.ic = cell_tail(qx, rx, fv.px, fv.nx, fv.nx, ax, true);
+  s.jc = cell_tail(qy, ry, fv.py, fv.ipy, fv.nx, ay, fv.ywrap1 != 0);
   lagrange_w(ax, bump, s.wx);
   lagrange_w(ay, bump, s.wy);
 }

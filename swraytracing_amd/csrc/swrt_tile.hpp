@@ -368,6 +368,8 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
   const int tx = tile / ta.ntx, ty = tile % ta.ntx;
   const int nx = a.f0.nx, npad = a.f0.npad;
   const int ox = tx * T, oy = ty * T;  // tile origin (cells)
+  // the window's first cell (origin - M) on the ring [0, nx)
+  const int oxm = ((ox - M) % nx + nx) % nx, oym = ((oy - M) % nx + nx) % nx;
   if (tid < 9) nbr[tid] = 0;
 #ifdef SWRT_PHASE_TIMING
   if (tid == 0) nfall = 0;
@@ -528,17 +530,22 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
         const double y1 = y0 + hcy;
         Stencil sc;
         stencil_at(a.f0, x1, y1, a.bump, sc);
-        const int dx_ = ring_diff(sc.ic, ox, nx), dy_ = ring_diff(sc.jc, oy, nx);
+        // window row and column of the stencil's first node: (cell - origin +
+        // M) mod nx, from the origins reduced to [0, nx) once per workgroup
+        // (the difference lies in (-nx, nx): one unsigned-min wrap).  Every
+        // position below T + 2M has its six taps inside the staged window.
+        const int d0 = sc.ic - oxm, d1 = sc.jc - oym;
+        const unsigned ux = min((unsigned)d0, (unsigned)(d0 + nx)), uy = min((unsigned)d1, (unsigned)(d1 + nx));
         double I[kRec], J[kRec];
-        const bool inwin = dx_ >= -M && dx_ < T + M && dy_ >= -M && dy_ < T + M;
+        const bool inwin = max(ux, uy) < (unsigned)(T + 2 * M);
 #ifdef SWRT_PHASE_TIMING
         if (!inwin) atomicAdd(&nfall, 1);
 #endif
         if (inwin) {
           if constexpr (V5)
-            gather5_lds<TWO, WS, WNP, FMA, PF>(win, (dx_ + M) * WS + (dy_ + M), sc, I, J);
+            gather5_lds<TWO, WS, WNP, FMA, PF>(win, (int)(ux * WS + uy), sc, I, J);
           else
-            gather6_lds<TWO, WS, WNP>(win, (dx_ + M) * WS + (dy_ + M), sc, I, J);
+            gather6_lds<TWO, WS, WNP>(win, (int)(ux * WS + uy), sc, I, J);
         } else {
           gather6_lean<TWO, FMA>(fa.nodes, fb.nodes, npad, sc, I, J);
         }
