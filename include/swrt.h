@@ -770,6 +770,86 @@ int swrt_trans_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* 
 int swrt_trans_series_reset(swrt_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * Packet recycling: at chosen moments every packet whose omega has reached
+ * omega_cut is absorbed and re-injected in the same slot, with its own home
+ * wavevector and a fresh uniform position.  N stays fixed, so a long run holds
+ * a source at omega_0, a sink at omega_cut and a flux between them, and each
+ * event's tally is kept as an integer frame on the device.
+ *
+ * State per packet, by ORIGINAL index (as the transition series keeps its
+ * source): home (2 doubles), gen (int32, the re-injections so far) and born
+ * (int32, the serial of the event that last injected it; 0 at begin).
+ *
+ * One event (swrt_recycle_apply), its serial counting from 1 since begin or
+ * reset.  Per packet p in storage order, o its original index,
+ *   w = sqrt(f^2 + Cg^2 (k k + l l)), the spectrum series' bits:
+ *   1. rejected when w is not finite or w * 2^frac_bits >= 2^38: counted and
+ *      left untouched, as the other series reject such packets (a blow-up
+ *      stays visible);
+ *   2. otherwise absorbed when w >= omega_cut: the frame tallies
+ *      rint(w * 2^fb), rint(omega(home[o]) * 2^fb) and age = serial - born[o];
+ *      then gen[o] += 1, born[o] = serial, (k, l) = home[o],
+ *      x = (u1 - 0.5) * L, y = (u2 - 0.5) * L;
+ *   3. otherwise untouched.
+ * The position comes from a counter-based hash, a function of (seed, global
+ * id, generation) only (uint64, wrapping):
+ *   mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z>>30)) * 0xBF58476D1CE4E5B9;
+ *           z = (z ^ (z>>27)) * 0x94D049BB133111EB; return z ^ (z>>31)
+ *   h1 = mix(mix(seed ^ mix(index_base + o)) + gen_after_increment)
+ *   h2 = mix(h1);   u = (h >> 11) * 2^-53
+ * (mix(0) = 0xE220A8397B1DCDAF, mix(0x9E3779B97F4A7C15) = 0x6E789E6AA1B965F4).
+ *
+ * A frame is 8 int64: [n, absorbed, rejected, sum rint(w * 2^fb) of the
+ * absorbed, sum rint(omega(home) * 2^fb) of the absorbed, sum age, max age,
+ * serial].  Integer sums and a max are order-free: a frame, and the packets
+ * after it, depend on the packet set alone, whatever the storage order, and
+ * the frames of shards with index_base = the shard's first global id combine
+ * by adding (the max age by the max).
+ *
+ * The marks of other subsystems are not touched: a re-injected packet keeps
+ * its ray-diagnostics Omega_0 and its transition source value.
+ * ------------------------------------------------------------------------- */
+
+/* Begin recycling the current packets.  home_k: n x 2 column-major home
+ * wavevectors in the original order, or NULL for the packets' k now.  Sets
+ * gen = born = 0, the serial to 0 and empties the frames.  SWRT_ERR_ARG with
+ * a message: L not finite and positive; f, Cg or omega_cut not finite;
+ * omega_cut <= |f|; frac_bits outside 0..32; no packets; a home wavevector
+ * whose omega is >= omega_cut or would be rejected (its packet would be
+ * absorbed at every event: checked on the device, one read-back of a flag,
+ * the call's only host wait). */
+int swrt_recycle_begin(swrt_ctx* ctx, double f, double Cg, double omega_cut, double L, uint64_t seed,
+                       int64_t index_base, int frac_bits, const double* home_k);
+
+/* One event on the current packets, in place, and its frame appended: queued
+ * on the packet stream after whatever last wrote the packets, no host wait
+ * (growing the frame buffer past its capacity, which doubles, may wait).  A
+ * queued ode23 chain is dropped, and the packet binning is invalidated:
+ * re-injected packets jump across tiles, so the next packet call re-bins.
+ * SWRT_ERR_STATE before begin, after a swrt_packets_set (which drops the
+ * recycle state as it drops the transition mark) or inside an ode23 hook. */
+int swrt_recycle_apply(swrt_ctx* ctx);
+
+/* Frames recorded since begin or the last reset. */
+int64_t swrt_recycle_frames(const swrt_ctx* ctx);
+
+/* Frames [first, first + count) -> stats8_out, count x 8, frame-major.  Waits
+ * for the frames.  A range out of bounds: SWRT_ERR_ARG; SWRT_ERR_STATE before
+ * begin. */
+int swrt_recycle_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* stats8_out);
+
+/* gen and born of every packet in the original order (n values each; either
+ * pointer may be NULL).  Waits.  SWRT_ERR_STATE as swrt_recycle_apply. */
+int swrt_recycle_state(swrt_ctx* ctx, int32_t* gen_out, int32_t* born_out);
+
+/* Drop the frames, set the serial to 0 and gen and born to 0; home, the cut
+ * and the seed stay: the next event equals a fresh begin's. */
+int swrt_recycle_reset(swrt_ctx* ctx);
+
+/* Release the recycle state and its frames. */
+int swrt_recycle_end(swrt_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
  * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)
  * ------------------------------------------------------------------------ */

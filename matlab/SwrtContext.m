@@ -168,6 +168,49 @@ classdef SwrtContext < handle
             swrt_mex('trans_series_reset', obj.id());
         end
 
+        % Packet recycling on the device: at every recycle_apply a packet
+        % whose omega has reached omega_cut is absorbed and re-injected in
+        % place with its home wavevector (home_k, n x 2 in the order of
+        % packets_set; []: the packets' k at begin) and a fresh uniform
+        % position in [-L/2, L/2)^2 from a hash of (seed, index_base + its
+        % index, its generation).  Per event one int64 frame [n; absorbed;
+        % rejected; sum round(omega_out * 2^frac_bits); sum round(omega_home
+        % * 2^frac_bits); sum age; max age; serial].
+        function recycle_begin(obj, f, Cg, omega_cut, L, seed, index_base, frac_bits, home_k)
+            if nargin < 6, seed = 0; end
+            if nargin < 7, index_base = 0; end
+            if nargin < 8, frac_bits = 20; end
+            if nargin < 9, home_k = []; end
+            swrt_mex('recycle_begin', obj.id(), f, Cg, omega_cut, L, seed, index_base, frac_bits, home_k);
+        end
+
+        function recycle_apply(obj)
+            swrt_mex('recycle_apply', obj.id());
+        end
+
+        function n = recycle_frames(obj)
+            n = swrt_mex('recycle_frames', obj.id());
+        end
+
+        function stats = recycle_get(obj)
+            % int64 8 x frames
+            stats = swrt_mex('recycle_get', obj.id());
+        end
+
+        function [gen, born] = recycle_state(obj)
+            % int64 n x 1 each, in the order of packets_set
+            [gen, born] = swrt_mex('recycle_state', obj.id());
+        end
+
+        function recycle_reset(obj)
+            % frames dropped, serial and gen and born back to 0; home stays
+            swrt_mex('recycle_reset', obj.id());
+        end
+
+        function recycle_end(obj)
+            swrt_mex('recycle_end', obj.id());
+        end
+
         % The wave-vector plane on the device (what raytracing_figures.m:19-26,
         % 76-83 scatter packet by packet): per frame an m x m int64 count
         % plane over [-K, K) x [-K, K), first index k, and eight int64 stats

@@ -69,6 +69,13 @@
 //   n = swrt_mex('trans_series_frames', h)
 //   [counts, sums, stats] = swrt_mex('trans_series_get', h)   % int64 (nw+2) x (ns+2) x frames, 3 x (ns+2) x frames, 3 x frames
 //   swrt_mex('trans_series_reset', h)
+//   swrt_mex('recycle_begin', h, f, Cg, omega_cut, L[, seed, index_base, frac_bits, home_k])   % absorb at omega_cut, re-inject at home; home_k n x 2 ([]: the packets' k now)
+//   swrt_mex('recycle_apply', h)                              % one event on the packets, in place; its frame appended
+//   n = swrt_mex('recycle_frames', h)
+//   stats = swrt_mex('recycle_get', h)                        % int64 8 x frames: n, absorbed, rejected, sum q(omega_out), sum q(omega_home), sum age, max age, serial
+//   [gen, born] = swrt_mex('recycle_state', h)                % int64 n x 1 each, original order
+//   swrt_mex('recycle_reset', h)
+//   swrt_mex('recycle_end', h)
 //   swrt_mex('track_begin', h, ids)                         % trajectories of chosen packets; ids 0-based doubles
 //   swrt_mex('track_record', h, f, gH, nslots, alpha, bump)   % nslots 0: no flow, Omega..D are NaN
 //   swrt_mex('track_record_history', h, first, count, f, gH, nslots, alphas, bump)   % alphas [] when nslots < 2
@@ -671,6 +678,56 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   if (!strcmp(cmd, "trans_series_reset")) {
     check(c, swrt_trans_series_reset(c), "swrt_trans_series_reset");
+    return;
+  }
+  if (!strcmp(cmd, "recycle_begin")) {  // (f, Cg, omega_cut, L[, seed = 0, index_base = 0, frac_bits = 20, home_k = []])
+    need(na, 5, cmd);
+    const double* home = nullptr;
+    if (na > 8 && mxGetNumberOfElements(a[8]) > 0) {
+      if ((int64_t)mxGetNumberOfElements(a[8]) != 2 * swrt_packets_count(c))
+        mexErrMsgIdAndTxt("swrt:arg", "home_k must be n x 2, one home wavevector per packet");
+      home = reals(a[8], "home_k");
+    }
+    check(c, swrt_recycle_begin(c, scalar(a[1]), scalar(a[2]), scalar(a[3]), scalar(a[4]),
+                                na > 5 ? (uint64_t)scalar(a[5]) : 0, na > 6 ? (int64_t)scalar(a[6]) : 0,
+                                na > 7 ? (int)scalar(a[7]) : 20, home),
+          "swrt_recycle_begin");
+    return;
+  }
+  if (!strcmp(cmd, "recycle_apply")) {
+    check(c, swrt_recycle_apply(c), "swrt_recycle_apply");
+    return;
+  }
+  if (!strcmp(cmd, "recycle_frames")) {
+    plhs[0] = mxCreateDoubleScalar((double)swrt_recycle_frames(c));
+    return;
+  }
+  if (!strcmp(cmd, "recycle_get")) {  // -> stats 8 x frames (int64)
+    const int64_t nf = swrt_recycle_frames(c);
+    const mwSize dims[2] = {8, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(2, dims, mxINT64_CLASS, mxREAL);
+    // (with no frame the call still runs: before begin it is an error)
+    check(c, swrt_recycle_get(c, 0, nf, (int64_t*)mxGetInt64s(plhs[0])), "swrt_recycle_get");
+    return;
+  }
+  if (!strcmp(cmd, "recycle_state")) {  // -> gen, born n x 1 (int64), original order
+    const int64_t n = swrt_packets_count(c);
+    std::vector<int32_t> gen((size_t)n), born((size_t)n);
+    check(c, swrt_recycle_state(c, gen.data(), born.data()), "swrt_recycle_state");
+    const mwSize dims[2] = {(mwSize)n, 1};
+    plhs[0] = mxCreateNumericArray(2, dims, mxINT64_CLASS, mxREAL);
+    mxArray* b = mxCreateNumericArray(2, dims, mxINT64_CLASS, mxREAL);
+    int64_t *pg = (int64_t*)mxGetInt64s(plhs[0]), *pb = (int64_t*)mxGetInt64s(b);
+    for (int64_t i = 0; i < n; ++i) pg[i] = gen[(size_t)i], pb[i] = born[(size_t)i];
+    if (nlhs > 1) plhs[1] = b; else mxDestroyArray(b);
+    return;
+  }
+  if (!strcmp(cmd, "recycle_reset")) {
+    check(c, swrt_recycle_reset(c), "swrt_recycle_reset");
+    return;
+  }
+  if (!strcmp(cmd, "recycle_end")) {
+    check(c, swrt_recycle_end(c), "swrt_recycle_end");
     return;
   }
   if (!strcmp(cmd, "track_begin")) {  // (ids): 0-based original packet indices, as doubles

@@ -124,6 +124,13 @@ SIGNATURES = {
     "swrt_trans_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                      ctypes.POINTER(ctypes.c_int64)]),
     "swrt_trans_series_reset": (_INT, [_VP]),
+    "swrt_recycle_begin": (_INT, [_VP, _D, _D, _D, _D, ctypes.c_uint64, _I, _INT, _P]),
+    "swrt_recycle_apply": (_INT, [_VP]),
+    "swrt_recycle_frames": (_I, [_VP]),
+    "swrt_recycle_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_recycle_state": (_INT, [_VP, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "swrt_recycle_reset": (_INT, [_VP]),
+    "swrt_recycle_end": (_INT, [_VP]),
     "swrt_track_begin": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64), _I]),
     "swrt_track_record": (_INT, [_VP, _D, _D, _INT, _D, _D]),
     "swrt_track_record_history": (_INT, [_VP, _I, _I, _D, _D, _INT, _P, _D]),
@@ -808,6 +815,55 @@ class Context:
 
     def trans_series_reset(self):
         self._chk(self._L.swrt_trans_series_reset(self._h), "swrt_trans_series_reset")
+
+    # ---- packet recycling (swrt_recycle_*: absorb at an omega cut, re-inject at home) ----
+    def recycle_begin(self, f, Cg, omega_cut, L, seed=0, index_base=0, frac_bits=20, home_k=None):
+        """Begin recycling the current packets: at every recycle_apply a packet
+        whose omega has reached ``omega_cut`` gets its home wavevector back
+        (``home_k``, n x 2 in the original order; None: the packets' k now) and
+        a fresh uniform position in [-L/2, L/2)^2 from a hash of (``seed``,
+        ``index_base`` + original index, generation)."""
+        home = None
+        if home_k is not None:
+            home = np.asfortranarray(home_k, dtype=np.float64)
+            if home.ndim != 2 or home.shape != (self.packets_count(), 2):
+                raise ValueError("home_k must be n x 2, one home wavevector per packet")
+        self._chk(self._L.swrt_recycle_begin(self._h, float(f), float(Cg), float(omega_cut), float(L),
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF, int(index_base), int(frac_bits),
+                                             _p(home)), "swrt_recycle_begin")
+
+    def recycle_apply(self):
+        """One event on the current packets (queued; no host wait)."""
+        self._chk(self._L.swrt_recycle_apply(self._h), "swrt_recycle_apply")
+
+    def recycle_frames(self):
+        return int(self._L.swrt_recycle_frames(self._h))
+
+    def recycle_get(self, first=0, count=None):
+        """Recorded frames [first, first + count) -> (count, 8) int64 [n,
+        absorbed, rejected, sum q(omega_out), sum q(omega_home), sum age, max
+        age, serial]."""
+        count = self.recycle_frames() - first if count is None else count
+        stats = np.zeros((max(count, 0), 8), dtype=np.int64)
+        self._chk(self._L.swrt_recycle_get(self._h, int(first), int(count),
+                                           stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), "swrt_recycle_get")
+        return stats
+
+    def recycle_state(self):
+        """(gen, born), int32 per packet in the original order."""
+        n = self.packets_count()
+        gen = np.zeros(n, dtype=np.int32)
+        born = np.zeros(n, dtype=np.int32)
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        self._chk(self._L.swrt_recycle_state(self._h, gen.ctypes.data_as(i32), born.ctypes.data_as(i32)),
+                  "swrt_recycle_state")
+        return gen, born
+
+    def recycle_reset(self):
+        self._chk(self._L.swrt_recycle_reset(self._h), "swrt_recycle_reset")
+
+    def recycle_end(self):
+        self._chk(self._L.swrt_recycle_end(self._h), "swrt_recycle_end")
 
     # ---- the track series (swrt_track_*: trajectories of chosen packets) ------
     def track_begin(self, ids):

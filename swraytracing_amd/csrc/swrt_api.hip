@@ -439,6 +439,7 @@ int swrt_packets_set(swrt_ctx* c, const double* x, const double* k, int64_t n) {
   if (n != c->n) c->rd.drop();  // Omega_0 and the frame series belong to an ensemble of the old size
   if (n != c->n) c->trk.drop();  // (the tracked ids too)
   c->trans.drop();  // the transition series' mark belongs to the packet set it was taken on
+  c->recycle.drop();  // (home, gen and born too)
   c->n = n;
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(c->pk.cur.x.get(), x, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
@@ -1777,6 +1778,129 @@ int swrt_trans_series_reset(swrt_ctx* c) {
   c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
   c->trans.series.ext.cleared();
   return SWRT_OK;
+}
+
+// ---- packet recycling (swrt_recycle.hpp, swrt_host_diag.hpp) ----
+int swrt_recycle_begin(swrt_ctx* c, double f, double Cg, double omega_cut, double L, uint64_t seed, int64_t index_base,
+                       int frac_bits, const double* home_k) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  if (!std::isfinite(f) || !std::isfinite(Cg) || !std::isfinite(omega_cut))
+    return fail(c, SWRT_ERR_ARG, "f, Cg and omega_cut must be finite");
+  if (!std::isfinite(L) || !(L > 0.0)) return fail(c, SWRT_ERR_ARG, "L must be finite and positive");
+  if (!(omega_cut > std::fabs(f))) return fail(c, SWRT_ERR_ARG, "omega_cut must be above |f|: no wave lies below it");
+  if (frac_bits < 0 || frac_bits > kRecycleMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
+  HIPCHK_RC(packets_check(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  RecycleState& rs = c->recycle;
+  HIPCHK_RC(series_release(c, rs.series));  // (waits: queued events use the old state too)
+  rs.open = rs.live = false;
+  rs.n = 0;
+  const int64_t n = c->n;
+  HIPCHK(c, rs.home.alloc(2 * n));
+  HIPCHK(c, rs.marks.alloc(2 * n));
+  if (!rs.bad) HIPCHK(c, rs.bad.alloc(1));
+  rs.n = n;
+  if (c->hz.on) {
+    c->hz.name(rs.home.get(), "recycle home wavevectors");
+    c->hz.name(rs.gen(), "recycle generation and birth marks");
+  }
+  const dim3 grid(nblocks(n, kRecycleThreads)), block(kRecycleThreads);
+  if (home_k) {
+    HIPCHK(c, hipMemcpyAsync(rs.home.get(), home_k, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+  } else {
+    hipLaunchKernelGGL(recycle_home_kernel, grid, block, 0, c->stream, c->pk.cur.k.get(), c->pk.cur.perm.get(), n,
+                       rs.home.get());
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipMemsetAsync(rs.marks.get(), 0, sizeof(int) * 2 * n, c->stream));
+  HIPCHK(c, hipMemsetAsync(rs.bad.get(), 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(recycle_home_check_kernel, grid, block, 0, c->stream, rs.home.get(), n, f * f, Cg * Cg, omega_cut,
+                     std::ldexp(1.0, frac_bits), rs.bad.get());
+  HIPCHK(c, hipGetLastError());
+  int bad = 0;
+  HIPCHK(c, hipMemcpyAsync(&bad, rs.bad.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the one read-back; the caller's home_k is free on return
+  hz_synced(c);
+  if (bad)
+    return fail(c, SWRT_ERR_ARG,
+                "a home wavevector's omega is at or above omega_cut, or too large for the frame: its packet would be "
+                "absorbed at every event");
+  rs.f2 = f * f;
+  rs.Cg2 = Cg * Cg;
+  rs.cut = omega_cut;
+  rs.L = L;
+  rs.seed = seed;
+  rs.base = index_base;
+  rs.frac_bits = frac_bits;
+  rs.serial = 0;
+  rs.open = rs.live = true;
+  return dev_err_check(c);
+  GUARD_END(c)
+}
+
+int swrt_recycle_apply(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(recycle_check(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  return recycle_launch(c);
+  GUARD_END(c)
+}
+
+int64_t swrt_recycle_frames(const swrt_ctx* c) { return c ? c->recycle.series.ext.frames() : -1; }
+
+int swrt_recycle_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* stats8_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  if (!c->recycle.open) return fail(c, SWRT_ERR_STATE, "call swrt_recycle_begin first");
+  return series_get(c, c->recycle.series, kRecycleFrame, 0, first, count, stats8_out, nullptr,
+                    "frame range out of bounds");
+  GUARD_END(c)
+}
+
+int swrt_recycle_state(swrt_ctx* c, int32_t* gen_out, int32_t* born_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(recycle_check(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  const RecycleState& rs = c->recycle;
+  if (gen_out)
+    HIPCHK(c, hipMemcpyAsync(gen_out, rs.gen(), sizeof(int32_t) * rs.n, hipMemcpyDeviceToHost, c->stream));
+  if (born_out)
+    HIPCHK(c, hipMemcpyAsync(born_out, rs.born(), sizeof(int32_t) * rs.n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return dev_err_check(c);
+  GUARD_END(c)
+}
+
+int swrt_recycle_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN_KEEP_CHAIN  // (the packets stay as they are)
+  RecycleState& rs = c->recycle;
+  rs.series.ext.cleared();
+  rs.serial = 0;
+  if (rs.live) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemsetAsync(rs.marks.get(), 0, sizeof(int) * 2 * rs.n, c->stream));
+  }
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_recycle_end(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN_KEEP_CHAIN
+  RecycleState& rs = c->recycle;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(series_release(c, rs.series));  // (waits: nothing queued uses the buffers below any more)
+  rs.open = rs.live = false;
+  rs.serial = 0;
+  rs.n = 0;
+  rs.home.reset();
+  rs.marks.reset();
+  return SWRT_OK;
+  GUARD_END(c)
 }
 
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {

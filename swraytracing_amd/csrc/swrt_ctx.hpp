@@ -442,6 +442,28 @@ struct TransSeriesState {
   void drop() { marked = false; }  // another packet set: the mark describes the old one
 };
 
+// packet recycling (swrt_recycle_*, swrt_recycle.hpp).  The per-packet state
+// (home, gen, born, by original index) belongs to the packet set:
+// swrt_packets_set drops it (live), the recorded frames stay readable until
+// swrt_recycle_end or the next begin.
+struct RecycleState {
+  bool open = false;        // swrt_recycle_begin was called: the frames can be read
+  bool live = false;        // home, gen and born describe the current packet set
+  int frac_bits = 0;
+  double f2 = 0.0, Cg2 = 0.0, cut = 0.0, L = 0.0;
+  uint64_t seed = 0;
+  int64_t base = 0;         // index_base
+  int64_t serial = 0;       // events since begin or reset
+  int64_t n = 0;            // packets the state was built for
+  DevBuf<double> home;      // n x 2 column-major
+  DevBuf<int> marks;        // gen (n), then born (n)
+  DevBuf<int> bad;          // begin's home check: one flag
+  Series<unsigned long long> series;  // recorded frames, kRecycleFrame words each
+  int* gen() const { return marks.get(); }
+  int* born() const { return marks.get() + n; }
+  void drop() { live = false; }  // another packet set: the state describes the old one
+};
+
 // debug knobs (swrt_debug_set): a spin kernel queued on every extra packet
 // stream before each of its part launches (adversarial overlap of consecutive
 // calls), and the pre-third-buffer ordering after a source-gather sort
@@ -525,6 +547,7 @@ struct swrt_ctx {
   FlowSpecState flow;
   CondSeriesState cond;
   TransSeriesState trans;
+  RecycleState recycle;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an
   // event marker, ~7 us of idle on each stream).  Only consecutive split

@@ -1,4 +1,5 @@
-// swrt_host_diag.hpp — host side of the eight device-side recorders: the ray
+// swrt_host_diag.hpp — host side of the eight device-side recorders and of
+// the packet recycling (swrt_recycle.hpp, last below): the ray
 // diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp), the
 // map series (swrt_map.hpp), the wave-vector plane series (swrt_kmap.hpp),
 // the track series (swrt_track.hpp), the flow spectrum series
@@ -23,6 +24,7 @@
 #include "swrt_flowspec.hpp"
 #include "swrt_cond.hpp"
 #include "swrt_trans.hpp"
+#include "swrt_recycle.hpp"
 
 namespace {
 
@@ -587,6 +589,53 @@ int trans_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_
     if (stats_out) std::copy(row + nsum, row + tl, stats_out + (size_t)kTransStats * t);
   }
   return dev_err_check(c);
+}
+
+// ---- packet recycling ----
+int recycle_check(swrt_ctx* c) {
+  if (!c->recycle.open) return fail(c, SWRT_ERR_STATE, "call swrt_recycle_begin first");
+  if (!c->recycle.live)
+    return fail(c, SWRT_ERR_STATE, "the recycle state belonged to an earlier packet set (swrt_recycle_begin again)");
+  return packets_check(c);
+}
+
+// One event: a zeroed frame at the series' end, the pass over the packets in
+// place, the binning told that packets jumped.
+int recycle_launch(swrt_ctx* c) {
+  RecycleState& rs = c->recycle;
+  HIPCHK_RC(series_reserve(c, rs.series, kRecycleFrame, 0, 1, kRecycleSeriesMin));
+  RecycleArgs a;
+  a.x = c->pk.cur.x.get();
+  a.k = c->pk.cur.k.get();
+  a.perm = c->pk.cur.perm.get();
+  a.n = c->n;
+  a.f2 = rs.f2;
+  a.Cg2 = rs.Cg2;
+  a.cut = rs.cut;
+  a.L = rs.L;
+  a.scale = std::ldexp(1.0, rs.frac_bits);
+  a.seed = rs.seed;
+  a.base = (uint64_t)rs.base;
+  a.serial = (int)(rs.serial + 1);
+  a.home = rs.home.get();
+  a.gen = rs.gen();
+  a.born = rs.born();
+  a.frame = rs.series.end_a(kRecycleFrame);
+  if (c->hz.on) {
+    HazardChecker& h = c->hz;
+    const uint64_t t = h.op(0);
+    const char* what = "the recycle launch";
+    if (!(hz_whole(h, t, kHzWrite, what, {a.x, a.k, a.gen, a.home}) && hz_whole(h, t, kHzRead, what, {a.perm})))
+      return fail(c, SWRT_ERR_STATE, h.err);
+  }
+  HIPCHK(c, hipMemsetAsync(a.frame, 0, sizeof(unsigned long long) * kRecycleFrame, c->stream));
+  const int nblk = (int)std::min<int64_t>(kRecycleBlocks, nblocks(c->n, kRecycleThreads));
+  hipLaunchKernelGGL(recycle_kernel, dim3(nblk), dim3(kRecycleThreads), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  ++rs.serial;
+  rs.series.ext.committed(1);
+  c->bin.invalidate();  // re-injected packets jump across tiles: the next packet call re-bins
+  return SWRT_OK;
 }
 
 }  // namespace

@@ -262,6 +262,57 @@ def trans_moments(counts, sums, frac_bits):
     return dict(n=n, omega_mean=omega_mean, delta_mean=delta_mean, delta_var=delta_var, spectrum=spectrum)
 
 
+def combine_recycles(parts):
+    """The recycle frames of an ensemble from its shards' (swrt_recycle_*).
+    ``parts``: a sequence of (T, 8) int64 arrays [n, absorbed, rejected,
+    sum q(omega_out), sum q(omega_home), sum age, max age, serial], one per
+    shard: columns 0-5 add (integer, exact and order-free), the max age takes
+    the max and the serial is the shards' common one.  Frames whose shards
+    counted a different number of events are refused.  A shard without packets
+    stands as zeros (its serial does not count)."""
+    parts = [np.asarray(p, dtype=np.int64) for p in parts]
+    if not parts:
+        raise ValueError("no series to combine")
+    if any(p.ndim != 2 or p.shape != parts[0].shape or p.shape[1] != 8 for p in parts):
+        raise ValueError("every shard must give (T, 8) frames of the same length")
+    stats = np.stack(parts)
+    holds = stats[..., 0] > 0                       # (shard, frame): the shard had packets
+    serial = np.where(holds, stats[..., 7], 0).max(axis=0)
+    if np.any(holds & (stats[..., 7] != serial[None, :])):
+        raise ValueError("the shards' event serials differ: their frames describe different events")
+    out = stats.sum(axis=0)
+    out[:, 6] = stats[..., 6].max(axis=0)
+    out[:, 7] = serial
+    return out
+
+
+def recycle_flux(stats, times, frac_bits, t0=None):
+    """Per event of frames ``stats`` (T, 8) int64 at the times ``times`` (T),
+    as fp64: ``fraction`` absorbed / n, ``energy_out`` and ``energy_in`` the
+    sums of omega of the absorbed packets as they left and as they came back
+    (each exact to the quantum 2^-frac_bits) per unit time since the event
+    before (``t0``: the time the first event's interval starts at; without it
+    the first event's two rates are NaN), and ``mean_age`` the mean number of
+    events an absorbed packet lived (NaN where none was absorbed).  The flux
+    through the sink is energy_out - energy_in."""
+    stats = np.asarray(stats, dtype=np.int64)
+    times = np.asarray(times, dtype=np.float64).ravel()
+    if stats.ndim != 2 or stats.shape[1] != 8 or times.size != stats.shape[0]:
+        raise ValueError("stats must be (T, 8) with one time per frame")
+    if not 0 <= int(frac_bits) <= 32:
+        raise ValueError("frac_bits must be 0..32")
+    unit = 2.0 ** -int(frac_bits)
+    n = stats[:, 0].astype(np.float64)
+    absorbed = stats[:, 1].astype(np.float64)
+    dt = np.diff(times, prepend=np.nan if t0 is None else float(t0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fraction = np.where(n > 0, absorbed / np.where(n > 0, n, 1.0), np.nan)
+        mean_age = np.where(absorbed > 0, stats[:, 5] / np.where(absorbed > 0, absorbed, 1.0), np.nan)
+        energy_out = stats[:, 3].astype(np.float64) * unit / dt
+        energy_in = stats[:, 4].astype(np.float64) * unit / dt
+    return dict(fraction=fraction, energy_out=energy_out, energy_in=energy_in, mean_age=mean_age)
+
+
 def track_ids_array(ids, n_total):
     """``ids`` as a checked int64 array: a one-dimensional, non-empty sequence
     of distinct integers in 0..n_total-1 (ValueError otherwise)."""
@@ -641,6 +692,7 @@ class PacketEnsemble:
             x, k = x[lo:hi], k[lo:hi]
         self.ctx.packets_set(x, k)
         self.n = x.shape[0]
+        self._k0 = k  # (this shard's initial wavevectors: begin_recycle's home)
         self._rebin = None
 
     def set_snapshots(self, prev_qk, qk):
@@ -1268,6 +1320,105 @@ class PacketEnsemble:
                                 dtype=np.float64)
                 fh.write(np.concatenate([head, st["sedges"], st["wedges"]]).tobytes())
         return st["frames"]
+
+    def begin_recycle(self, omega_cut, seed=0, frac_bits=20, directory=None, every=1):
+        """Begin recycling this run's packets (swrt_recycle_begin with the
+        ensemble's f, Cg and L): at every recycle() a packet whose omega has
+        reached ``omega_cut`` is re-injected with its initial wavevector and a
+        fresh uniform position.  A shard passes its first global id as
+        index_base, so the ensemble's packets and frames do not depend on the
+        sharding.  ``directory``: where write_recycle writes (default: given
+        there).  ``every`` only goes into recycle_geom.bin."""
+        omega_cut, frac_bits = float(omega_cut), int(frac_bits)
+        if not math.isfinite(omega_cut) or not omega_cut > abs(self.f):
+            raise ValueError("omega_cut must be finite and above |f|")
+        if not 0 <= frac_bits <= 32:
+            raise ValueError("recycle frac_bits must be 0..32")
+        lo = self.bounds[self.rank][0] if self.bounds is not None else 0
+        self._recycle = dict(omega_cut=omega_cut, seed=int(seed), frac_bits=frac_bits, directory=directory,
+                             every=int(every), times=[])
+        if self.n > 0:
+            self.ctx.recycle_begin(self.f, self.Cg, omega_cut, self.L, seed=seed, index_base=lo, frac_bits=frac_bits,
+                                   home_k=self._k0)
+
+    def recycle(self, t):
+        """One recycle event on this shard's packets at the time ``t``
+        (queued, no host wait).  An empty shard only remembers t.  Every rank
+        calls it at the same frame, so the shards' serials agree."""
+        st = getattr(self, "_recycle", None)
+        if st is None:
+            raise SwrtError("recycle: call begin_recycle first")
+        st["times"].append(float(t))
+        if self.n > 0:
+            self.ctx.recycle_apply()
+
+    def _gather_shards(self, a, sizes):
+        """``a`` of every shard, in rank order (a collective); ``sizes``: the
+        shards' first dimensions."""
+        import torch
+        import torch.distributed as dist
+
+        from .dist import _device_for
+        dev = _device_for(dist.get_backend())
+        padded = np.zeros((max(sizes),) + a.shape[1:], dtype=a.dtype)
+        padded[:a.shape[0]] = a
+        buf = torch.from_numpy(padded).to(dev)
+        out = [torch.empty_like(buf) for _ in range(self.world)]
+        dist.all_gather(out, buf)
+        return [o.cpu().numpy()[:s] for o, s in zip(out, sizes)]
+
+    def recycle_series(self):
+        """(stats (T, 8) int64, times (T,) fp64) of the ensemble's events.
+        Sharded: a collective; rank 0 gets combine_recycles() of the shards'
+        frames, the others None."""
+        st = getattr(self, "_recycle", None)
+        if st is None:
+            raise SwrtError("recycle_series: call begin_recycle first")
+        T = len(st["times"])
+        stats = self.ctx.recycle_get(0, T) if self.n > 0 else np.zeros((T, 8), dtype=np.int64)
+        if self.world > 1:
+            parts = self._gather_shards(stats, [T] * self.world)
+            if self.rank != 0:
+                return None
+            stats = combine_recycles(parts)
+        return stats, np.array(st["times"], dtype=np.float64)
+
+    def recycle_generations(self):
+        """How often every packet of the ensemble was re-injected, int32 in
+        the original order.  Sharded: a collective; rank 0 gets the whole
+        ensemble's, the others None."""
+        if getattr(self, "_recycle", None) is None:
+            raise SwrtError("recycle_generations: call begin_recycle first")
+        gen = self.ctx.recycle_state()[0] if self.n > 0 else np.zeros(0, dtype=np.int32)
+        if self.world > 1:
+            parts = self._gather_shards(gen, [hi - lo for lo, hi in self.bounds])
+            return np.concatenate(parts) if self.rank == 0 else None
+        return gen
+
+    def write_recycle(self, directory=None):
+        """The run's recycling as raw native-endian files: recycle_stats.bin
+        (8 int64 per event: n, absorbed, rejected, sum q(omega_out),
+        sum q(omega_home), sum age, max age, serial), recycle_time.bin (one
+        double per event), recycle_geom.bin (doubles omega_cut, L, seed,
+        frac_bits, f, Cg, every) and recycle_gen.bin (int32 per packet of the
+        ensemble in the original order: its re-injections).  Sharded: a
+        collective; rank 0 writes.  Returns the events."""
+        st = getattr(self, "_recycle", None)
+        if st is None:
+            raise SwrtError("write_recycle: call begin_recycle first")
+        directory = st["directory"] if directory is None else directory
+        if directory is None:
+            raise ValueError("write_recycle: no directory given here or to begin_recycle")
+        series = self.recycle_series()
+        gen = self.recycle_generations()
+        if self.rank == 0:
+            stats, times = series
+            for name, a in (("recycle_stats", stats), ("recycle_time", times), ("recycle_gen", gen),
+                            ("recycle_geom", np.array([st["omega_cut"], self.L, st["seed"], st["frac_bits"], self.f,
+                                                       self.Cg, st["every"]], dtype=np.float64))):
+                with open(os.path.join(directory, name + ".bin"), "wb") as fh:
+                    fh.write(np.ascontiguousarray(a).tobytes())
+        return len(st["times"])
 
     def begin_tracks(self, ids, directory=None):
         """Track the packets with the **global** ids ``ids`` (distinct, in

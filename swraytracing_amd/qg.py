@@ -341,7 +341,7 @@ def _fresh_outputs(out_dir, fresh):
                  "map_n", "map_omega", "map_k", "map_l", "map_stats", "track_x", "track_k", "track_diag", "track_time",
                  "track_ids", "kmap_n", "kmap_stats", "kmap_geom", "flow_spec", "flow_stats", "flow_geom", "cond_hist",
                  "cond_sums", "cond_stats", "cond_geom", "trans_hist", "trans_sums", "trans_stats", "trans_time",
-                 "trans_geom"):
+                 "trans_geom", "recycle_stats", "recycle_time", "recycle_geom", "recycle_gen"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
@@ -458,6 +458,36 @@ def _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_
                          "cells a frame")
     return (1 if trans_by == "ring" else 0), edges, (None if trans_lag is None else int(trans_lag)), \
         int(trans_frac_bits)
+
+
+def _recycle_args(recycle_omega, recycle_seed, recycle_every, recycle_frac_bits, ring_factors, f, trans_src_edges,
+                  Npackets):
+    """The drivers' ``recycle_omega`` / ``recycle_seed`` / ``recycle_every`` /
+    ``recycle_frac_bits`` checked before anything runs: (omega_cut, seed,
+    every, frac_bits), or None without recycling."""
+    if recycle_omega is None:
+        return None
+    if isinstance(recycle_omega, (bool, np.bool_)) or not isinstance(recycle_omega, numbers.Real) \
+            or not math.isfinite(recycle_omega):
+        raise ValueError("recycle_omega must be None or a finite number")
+    omega0 = max(ring_factors) * abs(f)
+    if not recycle_omega > omega0:
+        raise ValueError(f"recycle_omega must be above the largest ring's omega0 ({omega0:g}): a packet re-injected at "
+                         "home would be absorbed again at every event")
+    if trans_src_edges is not None:
+        raise ValueError('recycle_omega with trans_src_edges: the omega mark of a re-injected packet would be stale '
+                         '(trans_by="ring" is allowed: home keeps the ring)')
+    if Npackets <= 0:
+        raise ValueError("recycle_omega needs packets")
+    for name, v, lo in (("recycle_seed", recycle_seed, 0), ("recycle_every", recycle_every, 1),
+                        ("recycle_frac_bits", recycle_frac_bits, 0)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Integral) or v < lo:
+            raise ValueError(f"{name} must be an integer >= {lo}")
+    if recycle_frac_bits > 32:
+        raise ValueError("recycle_frac_bits must be an integer 0..32")
+    if recycle_seed >= 2 ** 64:
+        raise ValueError("recycle_seed must be below 2^64")
+    return float(recycle_omega), int(recycle_seed), int(recycle_every), int(recycle_frac_bits)
 
 
 def _begin_trans(ens, trans_args, spectrum_edges, out_dir, t, Npackets, nrings):
@@ -785,7 +815,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                   map_cells=None, map_frac_bits=20, track_ids=None, track_every=None,
                   kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False,
                   cond_by=None, cond_edges=None, cond_frac_bits=20,
-                  trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20):
+                  trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20,
+                  recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -871,9 +902,27 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     ns, nw, frac_bits, by (0 omega / 1 ring), the source edges, the omega
     edges); frame i belongs to packet frame i + 1; no other output changes and
     ``packet_files=False`` is allowed with it.
+    ``recycle_omega`` (above the largest ring's omega0; not together with
+    ``trans_src_edges``, whose omega mark a re-injected packet would make
+    stale, while ``trans_by="ring"`` is allowed: home keeps the ring; needs
+    packets): packet recycling (swrt_recycle_*), a sink at that omega and a
+    source at omega0 with N fixed.  At every packet frame after the first whose
+    index ``recycle_every`` divides, after the packets reached the frame's time
+    and before the frame is saved, every packet with omega >= ``recycle_omega``
+    is absorbed and re-injected in place with its initial wavevector and a
+    fresh uniform position from a hash of (``recycle_seed``, its global index,
+    its generation): a saved frame holds no packet at or above the cut, and the
+    files do not depend on the sharding.  Both integrators are allowed.
+    Written as recycle_stats.bin (8 int64 per event: n, absorbed, rejected,
+    sum q(omega_out), sum q(omega_home), sum age, max age, serial; sums in
+    quanta of 2^-``recycle_frac_bits``, ages in events), recycle_time.bin (one
+    double per event), recycle_geom.bin (doubles omega_cut, L, seed, frac_bits,
+    f, Cg, every) and recycle_gen.bin (int32 per packet in the original order:
+    its re-injections, written at the end); the other outputs are those of the
+    recycled packets.
     Returns a dict of run facts (dt, Nsteps, steps run, frames written,
     final t, spectrum_frames, map_frames, track_frames, kmap_frames,
-    flow_frames, cond_frames, trans_frames)."""
+    flow_frames, cond_frames, trans_frames, recycle_events)."""
     _flow_args(flow_spectrum, Npackets)
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files, kmap_cells)
     map_args = _map_args(map_cells, map_frac_bits)
@@ -885,6 +934,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
     if trans_args is not None and Npackets <= 0:
         raise ValueError("the transition series needs packets")
+    recycle_args = _recycle_args(recycle_omega, recycle_seed, recycle_every, recycle_frac_bits, ring_factors, f,
+                                 trans_src_edges, Npackets)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
@@ -952,6 +1003,11 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
         _begin_trans(ens, trans_args, spectrum_edges, out_dir, dt * (packet_step_start - 1), Npackets,
                      len(ring_factors))
         trans = trans_args[2] or 0
+    recycle = 0  # (packet frames per recycle event; 0: no recycling)
+    if ens is not None and recycle_args is not None:  # (events from the second packet frame on)
+        ens.begin_recycle(recycle_args[0], seed=recycle_args[1], frac_bits=recycle_args[3], directory=out_dir,
+                          every=recycle_args[2])
+        recycle = recycle_args[2]
     tracks = ens is not None and track_args is not None
     if tracks:
         ens.begin_tracks(track_args[0], directory=out_dir)
@@ -989,6 +1045,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                 ens.record_tracks(t, 1)
             if (step - packet_step_start + 1) % packet_steps_per_save == 0:
                 group.flush()
+                if recycle and frames % recycle == 0:
+                    ens.recycle(t)  # (before the frame: it holds no packet at or above the cut)
                 _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames)
                 if flows:
                     model.record_flow_spectrum()
@@ -1009,6 +1067,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     kmap_frames = ens.write_kmaps(out_dir) if kmaps else 0
     cond_frames = ens.write_conds(out_dir) if conds else 0
     trans_frames = ens.write_trans(out_dir) if trans is not None else 0
+    recycle_events = ens.write_recycle(out_dir) if recycle else 0
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -1019,7 +1078,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
                 track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames,
-                trans_frames=trans_frames)
+                trans_frames=trans_frames, recycle_events=recycle_events)
 
 
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
@@ -1029,7 +1088,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                         packet_files=True, map_cells=None, map_frac_bits=20, track_ids=None, track_every=None,
                         kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False,
                         cond_by=None, cond_edges=None, cond_frac_bits=20,
-                        trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20):
+                        trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20,
+                        recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
@@ -1039,7 +1099,9 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     ``kmap_kmax``, ``kmap_frac_bits``, ``track_ids``,
     ``track_every`` (default: this driver's packet cadence, 25),
     ``flow_spectrum``, ``cond_by``, ``cond_edges``, ``cond_frac_bits``,
-    ``trans_src_edges``, ``trans_by``, ``trans_lag``, ``trans_frac_bits`` and a
+    ``trans_src_edges``, ``trans_by``, ``trans_lag``, ``trans_frac_bits``,
+    ``recycle_omega``, ``recycle_seed``, ``recycle_every``,
+    ``recycle_frac_bits`` and a
     sequence of factors as ``near_inertial_factor``: as in
     :func:`qgsw_raytrace`.
 
@@ -1062,6 +1124,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
     if trans_args is not None and Npackets <= 0:
         raise ValueError("the transition series needs packets")
+    recycle_args = _recycle_args(recycle_omega, recycle_seed, recycle_every, recycle_frac_bits, ring_factors, f,
+                                 trans_src_edges, Npackets)
     _flow_args(flow_spectrum, Npackets)
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
@@ -1121,6 +1185,11 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
         _begin_trans(ens, trans_args, spectrum_edges, out_dir, dt * (packet_step_start - 1), Npackets,
                      len(ring_factors))
         trans = trans_args[2] or 0
+    recycle = 0  # (packet frames per recycle event; 0: no recycling)
+    if ens is not None and recycle_args is not None:  # (events from the second packet frame on)
+        ens.begin_recycle(recycle_args[0], seed=recycle_args[1], frac_bits=recycle_args[3], directory=out_dir,
+                          every=recycle_args[2])
+        recycle = recycle_args[2]
     tracks = ens is not None and track_args is not None
     if tracks:
         ens.begin_tracks(track_args[0], directory=out_dir)
@@ -1156,6 +1225,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
             ens.record_tracks(loop.t, 1)
         if active and (loop.steps - packet_step_start + 1) % packet_steps_per_save == 0:
             loop.flush()
+            if recycle and frames % recycle == 0:
+                ens.recycle(loop.t)  # (before the frame: it holds no packet at or above the cut)
             _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames)
             if flows:
                 model.record_flow_spectrum()  # (the committed qk at loop.t; the next step is only speculative)
@@ -1171,6 +1242,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     kmap_frames = ens.write_kmaps(out_dir) if kmaps else 0
     cond_frames = ens.write_conds(out_dir) if conds else 0
     trans_frames = ens.write_trans(out_dir) if trans is not None else 0
+    recycle_events = ens.write_recycle(out_dir) if recycle else 0
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -1183,4 +1255,4 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     return dict(dt=dt, dts=dts, Nsteps=Nsteps, steps=step, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
                 track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames,
-                trans_frames=trans_frames)
+                trans_frames=trans_frames, recycle_events=recycle_events)
