@@ -850,6 +850,108 @@ int swrt_recycle_reset(swrt_ctx* ctx);
 int swrt_recycle_end(swrt_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * The refraction series: how fast the flow's gradients carry each packet along
+ * the omega axis right now, and how its wavevector lies in the local strain,
+ * reduced per class and kept on the device as integers.  The rate is the
+ * kick's, kdot = -(grad U)^T k (RaytracingScheme.m:9-16); summed per omega
+ * class, omega-dot is the instantaneous flux density of the cascade that
+ * analysis/load_data.m:33-52 plots, the lag-0 counterpart of the transition
+ * series' drift.
+ *
+ * Per packet.  The state is (x, y, k1, k2); the flow record is
+ * I[0..5] = (u, v, u_x, u_y, v_x, v_y), the bits swrt_eval and
+ * swrt_raydiag_sample give for the same (nslots, alpha, bump).  Every
+ * operation below is rounded on its own (no fused multiply-add):
+ *   kk  = k1*k1 + k2*k2
+ *   w   = sqrt(f2 + Cg2*kk)                  the spectrum series' omega (load_data.m:33)
+ *   kd  = -(I[2]*k1 + I[4]*k2)               RaytracingScheme.m:14, the kick's sum
+ *   ld  = -(I[3]*k1 + I[5]*k2)               RaytracingScheme.m:15
+ *   g   = k1*kd + k2*ld
+ *   wd  = (Cg2*g)/w                          omega-dot
+ *   gam = g/kk                               d ln|k| / dt
+ *   s1  = I[2]-I[5];  s2 = I[4]+I[3];  sig = sqrt(s1*s1 + s2*s2)   the strain (RaytracingScheme.m:25)
+ *   c   = (gam+gam)/sig                      alignment
+ * with f2 = f*f and Cg2 = Cg*Cg.  For a non-divergent flow c = -cos 2 theta,
+ * theta the angle between k and the extension axis of the local strain: c = +1
+ * has k on the compression axis, |k| growing at the largest rate the flow
+ * allows (wave capture); c = -1 has k on the extension axis.  With
+ * S = 2^frac_bits: qd = rint(wd*S), qd2 = rint((wd*wd)*S), qg = rint(gam*S),
+ * round half even.
+ *
+ * Classes.  wc is the spectrum series' rule over omega_edges (a row [below,
+ * bin 0 .. bin nw-1, above], the last bin closed) and ac the same rule for c
+ * over a_edges with na bins.  In a flow that is not exactly non-divergent, or
+ * by rounding, |c| may exceed 1: such packets land in below or above of
+ * whatever edges the caller gave, which is no error.
+ *
+ * Rejected, adding to stats[1] and to nothing else, is a packet with any of
+ *   !(fabs(w*S) < 2^38);
+ *   c NaN (a NaN anywhere in the gradients or in k, kk = 0, sig = 0 with
+ *   gam = 0);
+ *   !(fabs(wd*S) < 2^38);  !((wd*wd)*S < 2^38);  !(fabs(gam*S) < 2^38).
+ *
+ * A frame holds
+ *   counts  (na + 2) x (nw + 2) int64, alignment class major:
+ *           counts[ac * (nw + 2) + wc];
+ *   sums    3 (nw + 2) + (na + 2) int64, signed sums in two's complement:
+ *           sums[0 * (nw + 2) + wc] += qd,  sums[1 * (nw + 2) + wc] += qd2,
+ *           sums[2 * (nw + 2) + wc] += qg,  sums[3 * (nw + 2) + ac] += qd
+ *           (the omega flux each alignment class carries, which the joint
+ *           counts cannot give because omega-dot also depends on sig);
+ *   stats   2 int64 [n, rejected].
+ * The counts of a frame sum to n - rejected, and their marginal over the
+ * alignment classes is the spectrum series' row of the accepted packets.  With
+ * n <= 2^24 every sum stays below 2^62.  Integer addition is exact and
+ * order-free: a frame depends on the packet set alone (two contexts, a
+ * re-binning between two records, either advance call and either
+ * packet-stream setting give the same bits), and the frames of shards combine
+ * by adding.  Positions must be finite, as for every gather of the library.
+ * ------------------------------------------------------------------------- */
+
+/* Open a series: 1 <= nw, na <= 4096 with (na + 2) * (nw + 2) <= 65536 cells
+ * (512 KB a frame), both edge arrays finite and increasing,
+ * 0 <= frac_bits <= 32 (SWRT_ERR_ARG with a message otherwise).  Empties the
+ * series. */
+int swrt_refr_series_begin(swrt_ctx* ctx, double f, double Cg, const double* omega_edges, int64_t nw,
+                           const double* a_edges, int64_t na, int frac_bits);
+
+/* Append the frame of the current packets in the flow of slot 0 (nslots 1) or
+ * of slots 0 and 1 blended at alpha (nslots 2): queued on the packet stream
+ * after whatever last wrote the packets and after the snapshot writes of the
+ * slots it reads, no host wait (growing the series past its capacity, which
+ * doubles, may wait for the stream).  While the count plane has at most 16384
+ * cells and fits a workgroup's LDS share beside the sums, every workgroup
+ * counts into a private plane in LDS and adds its non-zero cells to the frame;
+ * beyond, every packet adds through global memory: the same integers.
+ * SWRT_ERR_STATE before swrt_refr_series_begin; SWRT_ERR_ARG as for
+ * swrt_raydiag_record (nslots, an unset slot, two grids, no packets) and with
+ * more than 2^24 packets. */
+int swrt_refr_series_record(swrt_ctx* ctx, int nslots, double alpha, double bump);
+
+/* One frame per history frame in [first, first + count), frame i in the flow
+ * at alphas[i] (alphas may be NULL with one snapshot, as for
+ * swrt_raydiag_record_history): the same bits as swrt_refr_series_record on
+ * packets set to that frame.  With two snapshots the call waits for the
+ * stream once, before its launches, while alphas goes to the device.  A
+ * range out of bounds: SWRT_ERR_ARG. */
+int swrt_refr_series_record_history(swrt_ctx* ctx, int64_t first, int64_t count, int nslots, const double* alphas,
+                                    double bump);
+
+/* Frames recorded since begin or the last reset; nw and na of the open
+ * series, 0 if none (either pointer may be NULL). */
+int64_t swrt_refr_series_frames(const swrt_ctx* ctx);
+int swrt_refr_series_bins(const swrt_ctx* ctx, int64_t* nw_out, int64_t* na_out);
+
+/* Frames [first, first + count): counts_out count x (na + 2) x (nw + 2),
+ * sums_out count x (3 (nw + 2) + (na + 2)) and stats2_out count x 2,
+ * frame-major.  Each may be NULL.  Waits for the frames. */
+int swrt_refr_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                         int64_t* stats2_out);
+
+/* Empty the series; the edges and frac_bits stay. */
+int swrt_refr_series_reset(swrt_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
  * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)
  * ------------------------------------------------------------------------ */
@@ -1289,7 +1391,10 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
  *   (tools/cond_series_rate.py).  Both values give the same integers.
  * SWRT_DEBUG_TRANS_GLOBAL 0 / 1 (default 0): 1 makes the transition series'
  *   records take the global kernel for every shape
- *   (tools/trans_series_rate.py).  Both values give the same integers. */
+ *   (tools/trans_series_rate.py).  Both values give the same integers.
+ * SWRT_DEBUG_REFR_GLOBAL 0 / 1 (default 0): 1 makes the refraction series'
+ *   records take the global kernel for every shape
+ *   (tools/refr_series_rate.py).  Both values give the same integers. */
 #define SWRT_DEBUG_HAZARD_CHECK 1
 #define SWRT_DEBUG_SPIN_US 2
 #define SWRT_DEBUG_LEGACY_PARK 3
@@ -1310,6 +1415,7 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
 #define SWRT_DEBUG_KMAP_GLOBAL 19
 #define SWRT_DEBUG_COND_GLOBAL 20
 #define SWRT_DEBUG_TRANS_GLOBAL 21
+#define SWRT_DEBUG_REFR_GLOBAL 22
 int swrt_debug_set(swrt_ctx* ctx, int key, int64_t value);
 int swrt_debug_get(swrt_ctx* ctx, int key, int64_t* value_out);
 

@@ -168,6 +168,43 @@ classdef SwrtContext < handle
             swrt_mex('trans_series_reset', obj.id());
         end
 
+        % The refraction series on the device: per frame the int64 counts of
+        % the packets over omega classes (load_data.m:33-52; rows
+        % [below, bins, above] over omega_edges) by the classes over a_edges
+        % of the alignment c = 2 gamma / sigma of each wavevector in the
+        % local strain (gamma = d ln|k|/dt from the kick's rate,
+        % RaytracingScheme.m:9-16; c = 1: k on the compression axis), per
+        % omega class the sums of round(omega_dot * 2^frac_bits),
+        % round(omega_dot^2 * ...) and round(gamma * ...), per alignment
+        % class the sum of round(omega_dot * ...), and [n; rejected].
+        function refr_series_begin(obj, f, Cg, omega_edges, a_edges, frac_bits)
+            if nargin < 6, frac_bits = 20; end
+            swrt_mex('refr_series_begin', obj.id(), f, Cg, omega_edges, a_edges, frac_bits);
+        end
+
+        function refr_series_record(obj, nslots, alpha, bump)
+            swrt_mex('refr_series_record', obj.id(), nslots, alpha, bump);
+        end
+
+        function refr_series_record_history(obj, first, count, nslots, alphas, bump)
+            % history frames first .. first+count-1, 0-based; alphas [] with one snapshot
+            swrt_mex('refr_series_record_history', obj.id(), first, count, nslots, alphas, bump);
+        end
+
+        function n = refr_series_frames(obj)
+            n = swrt_mex('refr_series_frames', obj.id());
+        end
+
+        function [counts, sums, stats] = refr_series_get(obj)
+            % counts: int64 (nw+2) x (na+2) x frames (first index the omega class);
+            % sums: int64 (3(nw+2)+(na+2)) x frames; stats: int64 2 x frames
+            [counts, sums, stats] = swrt_mex('refr_series_get', obj.id());
+        end
+
+        function refr_series_reset(obj)
+            swrt_mex('refr_series_reset', obj.id());
+        end
+
         % Packet recycling on the device: at every recycle_apply a packet
         % whose omega has reached omega_cut is absorbed and re-injected in
         % place with its home wavevector (home_k, n x 2 in the order of

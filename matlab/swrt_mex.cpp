@@ -76,6 +76,12 @@
 //   [gen, born] = swrt_mex('recycle_state', h)                % int64 n x 1 each, original order
 //   swrt_mex('recycle_reset', h)
 //   swrt_mex('recycle_end', h)
+//   swrt_mex('refr_series_begin', h, f, Cg, omega_edges, a_edges[, frac_bits])   % omega classes by strain-alignment classes; omega-dot, omega-dot^2, gamma sums
+//   swrt_mex('refr_series_record', h, nslots, alpha, bump)
+//   swrt_mex('refr_series_record_history', h, first, count, nslots, alphas, bump)   % alphas [] when nslots < 2
+//   n = swrt_mex('refr_series_frames', h)
+//   [counts, sums, stats] = swrt_mex('refr_series_get', h)    % int64 (nw+2) x (na+2) x frames, (3(nw+2)+(na+2)) x frames, 2 x frames
+//   swrt_mex('refr_series_reset', h)
 //   swrt_mex('track_begin', h, ids)                         % trajectories of chosen packets; ids 0-based doubles
 //   swrt_mex('track_record', h, f, gH, nslots, alpha, bump)   % nslots 0: no flow, Omega..D are NaN
 //   swrt_mex('track_record_history', h, first, count, f, gH, nslots, alphas, bump)   % alphas [] when nslots < 2
@@ -678,6 +684,54 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   if (!strcmp(cmd, "trans_series_reset")) {
     check(c, swrt_trans_series_reset(c), "swrt_trans_series_reset");
+    return;
+  }
+  if (!strcmp(cmd, "refr_series_begin")) {  // (f, Cg, omega_edges, a_edges[, frac_bits = 20])
+    need(na, 5, cmd);
+    const size_t ne = mxGetNumberOfElements(a[3]), nae = mxGetNumberOfElements(a[4]);
+    check(c, swrt_refr_series_begin(c, scalar(a[1]), scalar(a[2]), reals(a[3], "omega_edges"), (int64_t)ne - 1,
+                                    reals(a[4], "a_edges"), (int64_t)nae - 1, na > 5 ? (int)scalar(a[5]) : 20),
+          "swrt_refr_series_begin");
+    return;
+  }
+  if (!strcmp(cmd, "refr_series_record")) {  // (nslots, alpha, bump)
+    need(na, 4, cmd);
+    check(c, swrt_refr_series_record(c, (int)scalar(a[1]), scalar(a[2]), scalar(a[3])), "swrt_refr_series_record");
+    return;
+  }
+  if (!strcmp(cmd, "refr_series_record_history")) {  // (first, count, nslots, alphas, bump): [] alphas = none
+    need(na, 6, cmd);
+    const int64_t count = (int64_t)scalar(a[2]);
+    const size_t nal = mxGetNumberOfElements(a[4]);
+    if (nal != 0 && (int64_t)nal != count) mexErrMsgIdAndTxt("swrt:arg", "alphas must hold one value per frame");
+    check(c, swrt_refr_series_record_history(c, (int64_t)scalar(a[1]), count, (int)scalar(a[3]),
+                                             nal ? reals(a[4], "alphas") : nullptr, scalar(a[5])),
+          "swrt_refr_series_record_history");
+    return;
+  }
+  if (!strcmp(cmd, "refr_series_frames")) {
+    plhs[0] = mxCreateDoubleScalar((double)swrt_refr_series_frames(c));
+    return;
+  }
+  if (!strcmp(cmd, "refr_series_get")) {  // -> counts (nw+2) x (na+2) x frames, sums (3(nw+2)+(na+2)) x frames, stats 2 x frames
+    const int64_t nf = swrt_refr_series_frames(c);
+    int64_t nw = 0, nal = 0;
+    check(c, swrt_refr_series_bins(c, &nw, &nal), "swrt_refr_series_bins");
+    const mwSize dims[3] = {(mwSize)(nw + 2), (mwSize)(nal + 2), (mwSize)nf},
+                 udims[2] = {(mwSize)(3 * (nw + 2) + nal + 2), (mwSize)nf}, sdims[2] = {2, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(3, dims, mxINT64_CLASS, mxREAL);
+    mxArray* sums = mxCreateNumericArray(2, udims, mxINT64_CLASS, mxREAL);
+    mxArray* stats = mxCreateNumericArray(2, sdims, mxINT64_CLASS, mxREAL);
+    if (nf > 0)
+      check(c, swrt_refr_series_get(c, 0, nf, (int64_t*)mxGetInt64s(plhs[0]), (int64_t*)mxGetInt64s(sums),
+                                    (int64_t*)mxGetInt64s(stats)),
+            "swrt_refr_series_get");
+    if (nlhs > 1) plhs[1] = sums; else mxDestroyArray(sums);
+    if (nlhs > 2) plhs[2] = stats; else mxDestroyArray(stats);
+    return;
+  }
+  if (!strcmp(cmd, "refr_series_reset")) {
+    check(c, swrt_refr_series_reset(c), "swrt_refr_series_reset");
     return;
   }
   if (!strcmp(cmd, "recycle_begin")) {  // (f, Cg, omega_cut, L[, seed = 0, index_base = 0, frac_bits = 20, home_k = []])

@@ -8,6 +8,7 @@ MATLAB call surface mirrored in Python.
 from ._lib import Context, SwrtError, load
 from .integrate import (PacketEnsemble, combine_conds, combine_frames, combine_kmaps, combine_maps, combine_spectra, combine_tracks,
                         combine_transitions, trans_moments, combine_recycles, recycle_flux,
+                        combine_refrs, alignment_edges, refr_rates,
                         cond_spectra, energy_spectrum, kmap_moments, map_fields,
                         ode23_packets, ode23_trajectory,
                         ode_symplectic, raytrace_sw, raytrace_xka, rsw_background, step_packet_xka)
@@ -22,6 +23,7 @@ __all__ = [
     "Context", "SwrtError", "load", "PacketEnsemble", "combine_frames", "combine_maps", "combine_spectra",
     "combine_tracks", "combine_kmaps", "combine_conds", "cond_spectra",
     "combine_transitions", "trans_moments", "combine_recycles", "recycle_flux",
+    "combine_refrs", "alignment_edges", "refr_rates",
     "energy_spectrum", "kmap_moments", "map_fields", "ode23_packets", "ode23_trajectory",
     "ode_symplectic",
     "raytrace_sw", "raytrace_xka", "rsw_background", "step_packet_xka",

@@ -124,6 +124,14 @@ SIGNATURES = {
     "swrt_trans_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                      ctypes.POINTER(ctypes.c_int64)]),
     "swrt_trans_series_reset": (_INT, [_VP]),
+    "swrt_refr_series_begin": (_INT, [_VP, _D, _D, _P, _I, _P, _I, _INT]),
+    "swrt_refr_series_record": (_INT, [_VP, _INT, _D, _D]),
+    "swrt_refr_series_record_history": (_INT, [_VP, _I, _I, _INT, _P, _D]),
+    "swrt_refr_series_frames": (_I, [_VP]),
+    "swrt_refr_series_bins": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_refr_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                    ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_refr_series_reset": (_INT, [_VP]),
     "swrt_recycle_begin": (_INT, [_VP, _D, _D, _D, _D, ctypes.c_uint64, _I, _INT, _P]),
     "swrt_recycle_apply": (_INT, [_VP]),
     "swrt_recycle_frames": (_I, [_VP]),
@@ -221,6 +229,7 @@ DEBUG_MAP_STRAYS = 18
 DEBUG_KMAP_GLOBAL = 19
 DEBUG_COND_GLOBAL = 20
 DEBUG_TRANS_GLOBAL = 21
+DEBUG_REFR_GLOBAL = 22
 COND_WHICH = {"zeta": 0, "sigma": 1, "D": 2}  # swrt_cond_series_begin's ``which``
 
 _lib = None
@@ -815,6 +824,65 @@ class Context:
 
     def trans_series_reset(self):
         self._chk(self._L.swrt_trans_series_reset(self._h), "swrt_trans_series_reset")
+
+    # ---- the refraction series (swrt_refr_series_*: omega-dot and strain alignment per class) ----
+    def refr_series_begin(self, f, Cg, omega_edges, a_edges, frac_bits=20):
+        """Open a series of (na + 2) x (nw + 2) count planes: omega classes
+        over ``omega_edges`` (nw + 1 increasing values) by the classes of the
+        alignment c = 2 gamma / sigma over ``a_edges`` (na + 1 increasing
+        values); the per-class sums of omega-dot, omega-dot^2 and gamma
+        quantised to 2^-frac_bits.  Empties the series."""
+        wedges = _f64(np.asarray(omega_edges, dtype=np.float64).ravel())
+        aedges = _f64(np.asarray(a_edges, dtype=np.float64).ravel())
+        self._chk(self._L.swrt_refr_series_begin(self._h, float(f), float(Cg), _p(wedges), wedges.size - 1,
+                                                 _p(aedges), aedges.size - 1, int(frac_bits)),
+                  "swrt_refr_series_begin")
+
+    def refr_series_record(self, nslots=1, alpha=0.0, bump=1e-13):
+        """Append the current packets' frame in the flow of slot 0 (nslots 1)
+        or slots 0 and 1 blended at ``alpha`` (queued; no host wait)."""
+        self._chk(self._L.swrt_refr_series_record(self._h, int(nslots), float(alpha), float(bump)),
+                  "swrt_refr_series_record")
+
+    def refr_series_record_history(self, first, count, nslots=1, alphas=None, bump=1e-13):
+        """One frame per history frame [first, first + count), frame i with
+        the snapshot blend ``alphas[i]`` (None with one snapshot: 0)."""
+        if alphas is not None:
+            alphas = np.ascontiguousarray(alphas, dtype=np.float64)
+            if alphas.shape != (int(count),):
+                raise ValueError("alphas must hold one value per frame")
+        self._chk(self._L.swrt_refr_series_record_history(self._h, int(first), int(count), int(nslots), _p(alphas),
+                                                          float(bump)), "swrt_refr_series_record_history")
+
+    def refr_series_frames(self):
+        return int(self._L.swrt_refr_series_frames(self._h))
+
+    def refr_series_bins(self):
+        """(nw, na) of the open series, (0, 0) if none."""
+        nw, na = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self._L.swrt_refr_series_bins(self._h, ctypes.byref(nw), ctypes.byref(na)), "swrt_refr_series_bins")
+        return int(nw.value), int(na.value)
+
+    def refr_series_get(self, first=0, count=None):
+        """Recorded frames [first, first + count) -> (counts (count, na + 2,
+        nw + 2) int64, counts[t, ac, wc]; sums (count, 3 (nw + 2) + (na + 2))
+        int64: per omega class the sums of rint(omega-dot * 2^frac_bits),
+        rint(omega-dot^2 * ...) and rint(gamma * ...), then per alignment
+        class the sum of rint(omega-dot * ...); stats (count, 2) int64
+        [n, rejected])."""
+        count = self.refr_series_frames() - first if count is None else count
+        nw, na = self.refr_series_bins()
+        counts = np.zeros((max(count, 0), na + 2, nw + 2), dtype=np.int64)
+        sums = np.zeros((max(count, 0), 3 * (nw + 2) + na + 2), dtype=np.int64)
+        stats = np.zeros((max(count, 0), 2), dtype=np.int64)
+        i64 = ctypes.POINTER(ctypes.c_int64)
+        self._chk(self._L.swrt_refr_series_get(self._h, int(first), int(count), counts.ctypes.data_as(i64),
+                                               sums.ctypes.data_as(i64), stats.ctypes.data_as(i64)),
+                  "swrt_refr_series_get")
+        return counts, sums, stats
+
+    def refr_series_reset(self):
+        self._chk(self._L.swrt_refr_series_reset(self._h), "swrt_refr_series_reset")
 
     # ---- packet recycling (swrt_recycle_*: absorb at an omega cut, re-inject at home) ----
     def recycle_begin(self, f, Cg, omega_cut, L, seed=0, index_base=0, frac_bits=20, home_k=None):

@@ -1903,6 +1903,101 @@ int swrt_recycle_end(swrt_ctx* c) {
   GUARD_END(c)
 }
 
+// ---- the refraction series (swrt_refr.hpp, swrt_host_diag.hpp) ----
+int swrt_refr_series_begin(swrt_ctx* c, double f, double Cg, const double* omega_edges, int64_t nw,
+                           const double* a_edges, int64_t na, int frac_bits) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(omega_edges_check(c, omega_edges, nw));
+  HIPCHK_RC(omega_edges_check(c, a_edges, na));
+  if ((na + 2) * (nw + 2) > kRefrMaxCells) return fail(c, SWRT_ERR_ARG, "(na + 2) * (nw + 2) must be at most 65536");
+  if (frac_bits < 0 || frac_bits > kRefrMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
+  HIPCHK(c, hipSetDevice(c->device));
+  RefrSeriesState& rs = c->refr;
+  HIPCHK_RC(series_release(c, rs.series));  // (waits: queued records read the old edges too)
+  rs.open = false;
+  HIPCHK(c, rs.edges.alloc(nw + na + 2));
+  HIPCHK(c, hipMemcpyAsync(rs.edges.get(), omega_edges, sizeof(double) * (nw + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(rs.edges.get() + nw + 1, a_edges, sizeof(double) * (na + 1), hipMemcpyHostToDevice,
+                           c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  rs.nw = (int)nw;
+  rs.na = (int)na;
+  rs.frac_bits = frac_bits;
+  rs.f2 = f * f;
+  rs.Cg2 = Cg * Cg;
+  rs.open = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_refr_series_record(swrt_ctx* c, int nslots, double alpha, double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c, false, track_slot_mask(nslots));
+  HIPCHK_RC(refr_series_check(c, nslots));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(refr_reserve_zeroed(c, 1));
+  return refr_launch(c, nslots, alpha, nullptr, bump, c->pk.cur.x.get(), c->pk.cur.k.get(), 0, 1);
+  GUARD_END(c)
+}
+
+int swrt_refr_series_record_history(swrt_ctx* c, int64_t first, int64_t count, int nslots, const double* alphas,
+                                    double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c, false, track_slot_mask(nslots));
+  HIPCHK_RC(refr_series_check(c, nslots));
+  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
+  if (nslots == 2 && !alphas && count > 0) return fail(c, SWRT_ERR_ARG, "NULL buffer (alphas, two snapshots)");
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  RefrSeriesState& rs = c->refr;
+  const double* dalphas = nullptr;
+  if (nslots == 2) {  // the frames' alphas to the device; the caller's buffer is free on return
+    if (count > rs.acap) {  // (releasing the old buffer waits for queued readers)
+      rs.acap = 0;
+      HIPCHK(c, rs.alphas.alloc(count));
+      rs.acap = count;
+    }
+    HIPCHK(c, hipMemcpyAsync(rs.alphas.get(), alphas, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    dalphas = rs.alphas.get();
+  }
+  HIPCHK_RC(refr_reserve_zeroed(c, count));
+  for (int64_t i = 0; i < count; i += kRefrHistoryChunk) {
+    const int64_t nf = std::min<int64_t>(kRefrHistoryChunk, count - i), off = (first + i) * 2 * c->n;
+    HIPCHK_RC(refr_launch(c, nslots, 0.0, dalphas ? dalphas + i : nullptr, bump, c->hist.a.get() + off,
+                          c->hist.b.get() + off, 2 * c->n, nf));
+  }
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int64_t swrt_refr_series_frames(const swrt_ctx* c) { return c ? c->refr.series.ext.frames() : -1; }
+
+int swrt_refr_series_bins(const swrt_ctx* c, int64_t* nw_out, int64_t* na_out) {
+  if (!c) return SWRT_ERR_ARG;
+  if (nw_out) *nw_out = c->refr.open ? c->refr.nw : 0;
+  if (na_out) *na_out = c->refr.open ? c->refr.na : 0;
+  return SWRT_OK;
+}
+
+int swrt_refr_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                         int64_t* stats2_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  return refr_series_get(c, first, count, counts_out, sums_out, stats2_out);
+  GUARD_END(c)
+}
+
+int swrt_refr_series_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
+  c->refr.series.ext.cleared();
+  return SWRT_OK;
+}
+
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
@@ -1982,6 +2077,10 @@ int swrt_debug_set(swrt_ctx* c, int key, int64_t value) {
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "transition series path must be 0 or 1");
       c->dbg.trans_global = value != 0;
       return SWRT_OK;
+    case SWRT_DEBUG_REFR_GLOBAL:
+      if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "refraction series path must be 0 or 1");
+      c->dbg.refr_global = value != 0;
+      return SWRT_OK;
     case SWRT_DEBUG_QG_UPDATE_COLS:
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "QG update/column-pass fusion must be 0 or 1");
       if (c->qg.spec) return fail(c, SWRT_ERR_STATE, "a speculative QG step is pending (swrt_qg_resolve first)");
@@ -2022,6 +2121,7 @@ int swrt_debug_get(swrt_ctx* c, int key, int64_t* value_out) {
     case SWRT_DEBUG_KMAP_GLOBAL: *value_out = c->dbg.kmap_path; return SWRT_OK;
     case SWRT_DEBUG_COND_GLOBAL: *value_out = c->dbg.cond_global ? 1 : 0; return SWRT_OK;
     case SWRT_DEBUG_TRANS_GLOBAL: *value_out = c->dbg.trans_global ? 1 : 0; return SWRT_OK;
+    case SWRT_DEBUG_REFR_GLOBAL: *value_out = c->dbg.refr_global ? 1 : 0; return SWRT_OK;
     case SWRT_DEBUG_MAP_STRAYS: {  // the device's counter: waits for the queued records
       unsigned long long v = 0;
       if (c->map.strays) {

@@ -442,6 +442,25 @@ struct TransSeriesState {
   void drop() { marked = false; }  // another packet set: the mark describes the old one
 };
 
+// the refraction series (swrt_refr_series_*, swrt_refr.hpp).  Buffers of its
+// own, as the other recorders'; a frame is self-contained (its n is in its
+// stats), so swrt_packets_set with another N keeps the series.
+struct RefrSeriesState {
+  bool open = false;        // swrt_refr_series_begin was called
+  int nw = 0, na = 0;       // omega and alignment bins of the open series
+  int frac_bits = 0;
+  double f2 = 0.0, Cg2 = 0.0;
+  DevBuf<double> edges;     // nw + 1 omega edges, then na + 1 alignment edges
+  DevBuf<double> alphas;    // record_history's alphas, one per frame of the call
+  int64_t acap = 0;         // frames alphas is sized for
+  bool lds_attr = false;    // the kernels' dynamic LDS limit was raised
+  // recorded frames: (na + 2) x (nw + 2) counts each, and their 3 (nw + 2) + (na + 2) sums followed by [n, rejected]
+  Series<unsigned long long> series;
+  size_t frame() const { return (size_t)(na + 2) * (nw + 2); }
+  size_t nsums() const { return (size_t)3 * (nw + 2) + (na + 2); }
+  size_t tail() const { return nsums() + 2; }
+};
+
 // packet recycling (swrt_recycle_*, swrt_recycle.hpp).  The per-packet state
 // (home, gen, born, by original index) belongs to the packet set:
 // swrt_packets_set drops it (live), the recorded frames stay readable until
@@ -476,6 +495,7 @@ struct DebugKnobs {
   int kmap_path = 0;        // SWRT_DEBUG_KMAP_GLOBAL: 0 by m; 1 global; 2 / 3 global with / without the wave merge
   bool cond_global = false; // SWRT_DEBUG_COND_GLOBAL: the conditional spectrum series' global kernel for every shape
   bool trans_global = false; // SWRT_DEBUG_TRANS_GLOBAL: the transition series' global kernel for every shape
+  bool refr_global = false; // SWRT_DEBUG_REFR_GLOBAL: the refraction series' global kernel for every shape
 };
 }  // namespace
 
@@ -547,6 +567,7 @@ struct swrt_ctx {
   FlowSpecState flow;
   CondSeriesState cond;
   TransSeriesState trans;
+  RefrSeriesState refr;
   RecycleState recycle;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an

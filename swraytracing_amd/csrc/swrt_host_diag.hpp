@@ -1,15 +1,16 @@
-// swrt_host_diag.hpp — host side of the eight device-side recorders and of
-// the packet recycling (swrt_recycle.hpp, last below): the ray
+// swrt_host_diag.hpp — host side of the nine device-side recorders and of
+// the packet recycling (swrt_recycle.hpp): the ray
 // diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp), the
 // map series (swrt_map.hpp), the wave-vector plane series (swrt_kmap.hpp),
 // the track series (swrt_track.hpp), the flow spectrum series
-// (swrt_flowspec.hpp), the conditional spectrum series (swrt_cond.hpp) and
-// the transition series (swrt_trans.hpp).
+// (swrt_flowspec.hpp), the conditional spectrum series (swrt_cond.hpp), the
+// transition series (swrt_trans.hpp) and the refraction series
+// (swrt_refr.hpp, last below).
 // Each appends frames to a Series of its
 // state (swrt_ctx.hpp) without a host wait: a reserve, the launches that write
 // at the series' end, a commit.  The order below (ray, spectrum, map, k-plane,
-// track, flow, conditional, transition) is the order their template kernels are first
-// named in, hence emitted in.
+// track, flow, conditional, transition, recycling, refraction) is the order their
+// template kernels are first named in, hence emitted in.
 #pragma once
 #include <cmath>
 
@@ -25,6 +26,7 @@
 #include "swrt_cond.hpp"
 #include "swrt_trans.hpp"
 #include "swrt_recycle.hpp"
+#include "swrt_refr.hpp"
 
 namespace {
 
@@ -636,6 +638,99 @@ int recycle_launch(swrt_ctx* c) {
   rs.series.ext.committed(1);
   c->bin.invalidate();  // re-injected packets jump across tiles: the next packet call re-bins
   return SWRT_OK;
+}
+
+// ---- the refraction series ----
+// The records' common checks: an open series, then swrt_raydiag_record's.
+int refr_series_check(swrt_ctx* c, int nslots) {
+  if (!c->refr.open) return fail(c, SWRT_ERR_STATE, "call swrt_refr_series_begin first");
+  HIPCHK_RC(raydiag_check(c, nslots));
+  if (c->n > kRefrMaxPackets) return fail(c, SWRT_ERR_ARG, "a refraction frame takes at most 2^24 packets");
+  return SWRT_OK;
+}
+
+// Room for `count` more frames, zeroed on the stream (counts, sums and
+// stats): the launches that fill them only add.
+int refr_reserve_zeroed(swrt_ctx* c, int64_t count) {
+  RefrSeriesState& rs = c->refr;
+  const size_t fr = rs.frame(), tl = rs.tail();
+  HIPCHK_RC(series_reserve(c, rs.series, fr, tl, count, map_series_min(fr * sizeof(unsigned long long))));
+  HIPCHK(c, hipMemsetAsync(rs.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
+  HIPCHK(c, hipMemsetAsync(rs.series.end_b(tl), 0, sizeof(unsigned long long) * tl * count, c->stream));
+  return SWRT_OK;
+}
+
+// `count` frames from the series' end on: frame i from the packets at
+// x + i*stride, k + i*stride (any order) and the flow at alphas[i] (device;
+// NULL: `alpha` for every frame).  The LDS kernel for refr_lds_form's shapes,
+// the global one beyond (or when SWRT_DEBUG_REFR_GLOBAL says so).
+int refr_launch(swrt_ctx* c, int nslots, double alpha, const double* alphas, double bump, const double* x,
+                const double* k, int64_t stride, int64_t count) {
+  RefrSeriesState& rs = c->refr;
+  RefrArgs a;
+  a.f0 = view_of(c->slot[0]);
+  a.f1 = nslots == 2 ? view_of(c->slot[1]) : a.f0;
+  a.nslots = nslots;
+  a.alpha = alpha;
+  a.bump = bump;
+  a.alphas = alphas;
+  a.x = x;
+  a.k = k;
+  a.stride = stride;
+  a.n = c->n;
+  a.f2 = rs.f2;
+  a.Cg2 = rs.Cg2;
+  a.wedges = rs.edges.get();
+  a.aedges = rs.edges.get() + rs.nw + 1;
+  a.nw = rs.nw;
+  a.na = rs.na;
+  a.scale = std::ldexp(1.0, rs.frac_bits);
+  a.counts = rs.series.end_a(rs.frame());
+  a.tail = rs.series.end_b(rs.tail());
+  const bool lds = !c->dbg.refr_global && refr_lds_form(rs.nw, rs.na);
+  const size_t bytes = refr_lds_bytes(rs.nw, rs.na, lds);
+  if (bytes > ((size_t)64 << 10) && !rs.lds_attr) {  // (above 64 KB of dynamic LDS a kernel has to ask once)
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&refr_kernel<true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kRefrMaxLdsBytes));
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&refr_kernel<false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kRefrMaxLdsBytes));
+    rs.lds_attr = true;
+  }
+  const int most = bytes > kRefrLdsFormBytes ? kRefrHugeTailBlocks
+                   : bytes > kRefrBigPlaneBytes ? kRefrBigPlaneBlocks : kRefrBlocks;
+  const int nblk = (int)std::min<int64_t>(most, nblocks(c->n, kRefrThreads));
+  hipLaunchKernelGGL(lds ? refr_kernel<true> : refr_kernel<false>, dim3(nblk, (unsigned)count), dim3(kRefrThreads),
+                     bytes, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  rs.series.ext.committed(count);
+  return SWRT_OK;
+}
+
+// Frames [first, first + count) to the host, synchronously; every output may
+// be NULL.  The sums and the stats share the series' second column.
+int refr_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                    int64_t* stats_out) {
+  const RefrSeriesState& rs = c->refr;
+  HIPCHK_RC(frame_range_check(c, rs.series.ext, first, count, "frame range out of bounds"));
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t fr = rs.frame(), tl = rs.tail(), nsum = rs.nsums();
+  std::vector<int64_t> tails;
+  if (counts_out)
+    HIPCHK(c, hipMemcpyAsync(counts_out, rs.series.a.get() + fr * first, sizeof(int64_t) * fr * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  if (sums_out || stats_out) {
+    tails.resize(tl * count);
+    HIPCHK(c, hipMemcpyAsync(tails.data(), rs.series.b.get() + tl * first, sizeof(int64_t) * tl * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int64_t t = 0; t < count && !tails.empty(); ++t) {
+    const int64_t* row = tails.data() + tl * t;
+    if (sums_out) std::copy(row, row + nsum, sums_out + nsum * t);
+    if (stats_out) std::copy(row + nsum, row + tl, stats_out + (size_t)kRefrStats * t);
+  }
+  return dev_err_check(c);
 }
 
 }  // namespace

@@ -204,6 +204,77 @@ def cond_spectra(counts, sums, frac_bits):
     return dict(n=n, spectrum=spectrum, omega_mean=omega_mean)
 
 
+def combine_refrs(parts):
+    """The refraction series of an ensemble from its shards' series
+    (swrt_refr_series_*).  ``parts``: a sequence of (counts, sums, stats)
+    triples, one per shard, counts (T, na + 2, nw + 2) int64, sums
+    (T, 3 (nw + 2) + (na + 2)) int64 and stats (T, 2) int64 [n, rejected]: the
+    element-wise sum (integer, exact and order-free).  A shard without packets
+    stands as zeros."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no series to combine")
+    shapes = {tuple(np.shape(a) for a in p) for p in parts}
+    if len(shapes) != 1:
+        raise ValueError("every shard must give counts, sums and stats of the same shapes")
+    counts = np.stack([np.asarray(p[0], dtype=np.int64) for p in parts])
+    sums = np.stack([np.asarray(p[1], dtype=np.int64) for p in parts])
+    stats = np.stack([np.asarray(p[2], dtype=np.int64) for p in parts])
+    if counts.ndim != 4 or sums.shape != counts.shape[:2] + (3 * counts.shape[3] + counts.shape[2],) \
+            or stats.shape != counts.shape[:2] + (2,):
+        raise ValueError("every shard must give counts (T, na + 2, nw + 2), sums (T, 3 (nw + 2) + (na + 2)) "
+                         "and stats (T, 2)")
+    return counts.sum(axis=0), sums.sum(axis=0), stats.sum(axis=0)
+
+
+def alignment_edges(na):
+    """``na`` equal alignment classes over [-1, 1], the range of
+    c = -cos 2 theta in a non-divergent flow: na + 1 edges."""
+    if isinstance(na, (bool, np.bool_)) or int(na) != na or not 1 <= int(na) <= 4096:
+        raise ValueError("na must be an integer 1..4096")
+    return np.linspace(-1.0, 1.0, int(na) + 1)
+
+
+def refr_rates(counts, sums, frac_bits):
+    """Rates of refraction frames counts (..., na + 2, nw + 2) and sums
+    (..., 3 (nw + 2) + (na + 2)) int64, as fp64.  Per omega class: ``n``
+    (..., nw + 2) its packets, ``omega_dot_mean``, ``omega_dot_sq_mean`` and
+    ``gamma_mean`` (..., nw + 2) the means of omega-dot, omega-dot^2 and
+    gamma = d ln|k|/dt (each exact to the quantum 2^-frac_bits), ``alignment``
+    (..., nw + 2, na + 2) the class's alignment row divided by its n.  Per
+    alignment class: ``n_align`` (..., na + 2), ``omega_dot_mean_align``
+    (..., na + 2) and ``flux_share`` (..., na + 2), the class's part of the
+    frame's sum of omega-dot (NaN where that sum is 0).  The means and the
+    density are NaN where the class is empty."""
+    counts = np.asarray(counts)
+    sums = np.asarray(sums)
+    if counts.ndim < 2:
+        raise ValueError("counts must be (..., na + 2, nw + 2)")
+    nas, nws = counts.shape[-2:]
+    if sums.shape != counts.shape[:-2] + (3 * nws + nas,):
+        raise ValueError("counts must be (..., na + 2, nw + 2) and sums (..., 3 (nw + 2) + (na + 2))")
+    if not 0 <= int(frac_bits) <= 32:
+        raise ValueError("frac_bits must be 0..32")
+    unit = 2.0 ** -int(frac_bits)
+    n = counts.sum(axis=-2).astype(np.float64)
+    empty = n == 0
+    count = np.where(empty, 1.0, n)
+    wd, wd2, gam = (sums[..., j * nws:(j + 1) * nws].astype(np.float64) * unit / count for j in range(3))
+    alignment = np.swapaxes(counts, -1, -2).astype(np.float64) / count[..., None]
+    for a in (wd, wd2, gam, alignment):
+        a[empty] = np.nan
+    n_a = counts.sum(axis=-1).astype(np.float64)
+    empty_a = n_a == 0
+    flux_a = sums[..., 3 * nws:].astype(np.float64) * unit
+    wd_a = flux_a / np.where(empty_a, 1.0, n_a)
+    wd_a[empty_a] = np.nan
+    total = flux_a.sum(axis=-1, keepdims=True)
+    share = flux_a / np.where(total == 0, 1.0, total)
+    share[np.broadcast_to(total == 0, share.shape)] = np.nan
+    return dict(n=n, omega_dot_mean=wd, omega_dot_sq_mean=wd2, gamma_mean=gam, alignment=alignment,
+                n_align=n_a, omega_dot_mean_align=wd_a, flux_share=share)
+
+
 def combine_transitions(parts):
     """The transition series of an ensemble from its shards' series
     (swrt_trans_series_*).  ``parts``: a sequence of (counts, sums, stats)
@@ -1158,6 +1229,136 @@ class PacketEnsemble:
                 head = np.array([st["which"], st["qedges"].size - 1, st["wedges"].size - 1, st["frac_bits"]],
                                 dtype=np.float64)
                 fh.write(np.concatenate([head, st["qedges"], st["wedges"]]).tobytes())
+        return st["frames"]
+
+    def begin_refr(self, omega_edges, a_edges, frac_bits=20, directory=None):
+        """Open the refraction series of this run (swrt_refr_series_begin with
+        the ensemble's f, Cg): omega classes over ``omega_edges`` by the
+        classes of the alignment c = 2 gamma / sigma over ``a_edges``.
+        ``directory``: where record_refr drains the device series when it
+        grows large (default: the drained frames wait in host memory for
+        write_refrs)."""
+        wedges = np.array(omega_edges, dtype=np.float64).ravel()
+        aedges = np.array(a_edges, dtype=np.float64).ravel()
+        for name, e in (("omega", wedges), ("alignment", aedges)):
+            if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+                raise ValueError(f"the {name} edges must be at least two finite increasing values")
+        frac_bits = int(frac_bits)
+        if not 0 <= frac_bits <= 32:
+            raise ValueError("refraction series frac_bits must be 0..32")
+        if (aedges.size + 1) * (wedges.size + 1) > 65536:
+            raise ValueError("a refraction frame holds at most 65536 cells, (na + 2) * (nw + 2)")
+        self._refr = dict(wedges=wedges, aedges=aedges, frac_bits=frac_bits, directory=directory, frames=0,
+                          pending=0, kept=[])
+        if self.n > 0:
+            self.ctx.refr_series_begin(self.f, self.Cg, wedges, aedges, frac_bits)
+
+    def record_refr(self, alpha=None):
+        """Append this shard's refraction frame at the current state to the
+        device-side series (queued, no host wait), in the flow of slot 0
+        (``alpha`` None) or of slots 0 and 1 blended at ``alpha``.  An empty
+        shard records nothing.  When the device series holds more than 256 MB
+        it is drained (get, combine, append, reset): a collective when
+        sharded, at the same frame on every rank."""
+        st = getattr(self, "_refr", None)
+        if st is None:
+            raise SwrtError("record_refr: call begin_refr first")
+        st["frames"] += 1
+        st["pending"] += 1
+        if self.n > 0:
+            if alpha is None:
+                self.ctx.refr_series_record(nslots=1, bump=self.bump)
+            else:
+                self.ctx.refr_series_record(nslots=2, alpha=alpha, bump=self.bump)
+        nas, nws = st["aedges"].size + 1, st["wedges"].size + 1
+        if st["pending"] * 8 * (nas * nws + 3 * nws + nas + 2) > MAP_DRAIN_BYTES:
+            self._drain_refrs()
+
+    def _drain_refrs(self):
+        """The frames on the device, summed over the shards, to the files or
+        the host list of rank 0; the device series emptied."""
+        st = self._refr
+        T, nas, nws = st["pending"], st["aedges"].size + 1, st["wedges"].size + 1
+        if T == 0:
+            return
+        if self.n > 0:
+            part = self.ctx.refr_series_get(0, T)
+            self.ctx.refr_series_reset()
+        else:
+            part = (np.zeros((T, nas, nws), dtype=np.int64), np.zeros((T, 3 * nws + nas), dtype=np.int64),
+                    np.zeros((T, 2), dtype=np.int64))
+        st["pending"] = 0
+        if self.world > 1:
+            import torch
+            import torch.distributed as dist
+
+            from .dist import _device_for
+            dev = _device_for(dist.get_backend())
+            gathered = []
+            for a in part:
+                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                out = [torch.empty_like(buf) for _ in range(self.world)]
+                dist.all_gather(out, buf)
+                gathered.append([o.cpu().numpy() for o in out])
+            if self.rank != 0:
+                return
+            part = combine_refrs(zip(*gathered))
+        if st["directory"] is None:
+            st["kept"].append(part)
+        else:
+            self._append_refrs(st["directory"], *part)
+
+    @staticmethod
+    def _append_refrs(directory, counts, sums, stats):
+        with open(os.path.join(directory, "refr_hist.bin"), "ab") as fc, \
+                open(os.path.join(directory, "refr_sums.bin"), "ab") as fs, \
+                open(os.path.join(directory, "refr_stats.bin"), "ab") as ft:
+            for fr, s, t in zip(counts, sums, stats):
+                fc.write(np.ascontiguousarray(fr, dtype=np.int64).tobytes())  # (cell (ac, wc) at ac*(nw + 2) + wc)
+                fs.write(np.ascontiguousarray(s, dtype=np.int64).tobytes())
+                ft.write(np.ascontiguousarray(t, dtype=np.int64).tobytes())
+
+    def refr_series(self):
+        """(counts (T, na + 2, nw + 2), sums (T, 3 (nw + 2) + (na + 2)), stats
+        (T, 2)), all int64, of the ensemble's frames still held (not yet
+        drained into files).  Sharded: a collective; rank 0 gets
+        combine_refrs() of the shards' frames, the others None."""
+        st = getattr(self, "_refr", None)
+        if st is None:
+            raise SwrtError("refr_series: call begin_refr first")
+        if st["directory"] is not None:
+            raise ValueError("refr_series: begin_refr drains into a directory (read its files)")
+        self._drain_refrs()
+        if self.rank != 0:
+            return None
+        nas, nws = st["aedges"].size + 1, st["wedges"].size + 1
+        if not st["kept"]:
+            return (np.zeros((0, nas, nws), dtype=np.int64), np.zeros((0, 3 * nws + nas), dtype=np.int64),
+                    np.zeros((0, 2), dtype=np.int64))
+        return tuple(np.concatenate([p[i] for p in st["kept"]]) for i in range(3))
+
+    def write_refrs(self, directory):
+        """The run's refraction series as raw native-endian files:
+        refr_hist.bin (int64, one (na + 2) x (nw + 2) plane per frame, cell
+        (ac, wc) at ac*(nw + 2) + wc), refr_sums.bin (3 (nw + 2) + (na + 2)
+        int64 per frame), refr_stats.bin (2 int64 per frame: n, rejected) and
+        refr_geom.bin (doubles [na, nw, frac_bits], the na + 1 alignment
+        edges, the nw + 1 omega edges).  Sharded: a collective; rank 0 writes.
+        Returns the frames recorded."""
+        st = getattr(self, "_refr", None)
+        if st is None:
+            raise SwrtError("write_refrs: call begin_refr first")
+        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
+            raise ValueError("write_refrs: begin_refr drained into another directory")
+        self._drain_refrs()
+        if self.rank == 0:
+            if st["directory"] is None:
+                for part in st["kept"]:
+                    self._append_refrs(directory, *part)
+                st["kept"] = []
+            with open(os.path.join(directory, "refr_geom.bin"), "wb") as fh:
+                head = np.array([st["aedges"].size - 1, st["wedges"].size - 1, st["frac_bits"]], dtype=np.float64)
+                fh.write(np.concatenate([head, st["aedges"], st["wedges"]]).tobytes())
         return st["frames"]
 
     def begin_trans(self, omega_edges, src_edges, frac_bits=20, by=0, directory=None):

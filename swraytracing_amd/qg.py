@@ -341,7 +341,8 @@ def _fresh_outputs(out_dir, fresh):
                  "map_n", "map_omega", "map_k", "map_l", "map_stats", "track_x", "track_k", "track_diag", "track_time",
                  "track_ids", "kmap_n", "kmap_stats", "kmap_geom", "flow_spec", "flow_stats", "flow_geom", "cond_hist",
                  "cond_sums", "cond_stats", "cond_geom", "trans_hist", "trans_sums", "trans_stats", "trans_time",
-                 "trans_geom", "recycle_stats", "recycle_time", "recycle_geom", "recycle_gen"):
+                 "trans_geom", "recycle_stats", "recycle_time", "recycle_geom", "recycle_gen", "refr_hist", "refr_sums",
+                 "refr_stats", "refr_geom"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
@@ -419,6 +420,26 @@ def _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges):
     if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
         raise ValueError("cond_edges: at most 4096 classes and (nq + 2) * (nbins + 2) <= 65536 cells a frame")
     return cond_by, edges, int(cond_frac_bits)
+
+
+def _refr_args(refr_edges, refr_frac_bits, spectrum_edges):
+    """The drivers' ``refr_edges`` / ``refr_frac_bits`` checked before anything
+    runs: (alignment edges, frac_bits), or None without ``refr_edges``.  The
+    omega classes are the run's ``spectrum_edges``."""
+    if refr_edges is None:
+        return None
+    if spectrum_edges is None:
+        raise ValueError("refr_edges needs spectrum_edges: they are the refraction series' omega classes")
+    edges = np.array(refr_edges, dtype=np.float64).ravel()
+    if edges.size < 2 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
+        raise ValueError("refr_edges must be at least two finite increasing values")
+    if isinstance(refr_frac_bits, (bool, np.bool_)) or not isinstance(refr_frac_bits, numbers.Real) \
+            or int(refr_frac_bits) != refr_frac_bits or not 0 <= int(refr_frac_bits) <= 32:
+        raise ValueError("refr_frac_bits must be an integer 0..32")
+    nw = np.asarray(spectrum_edges).size - 1
+    if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
+        raise ValueError("refr_edges: at most 4096 classes and (na + 2) * (nbins + 2) <= 65536 cells a frame")
+    return edges, int(refr_frac_bits)
 
 
 def _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, nrings):
@@ -543,9 +564,11 @@ def _track_args(track_ids, track_every, Npackets, default_every):
     return ids, int(track_every)
 
 
-def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False, conds=False, trans=None, index=0):
+def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False, conds=False, trans=None, index=0,
+                refrs=False):
     """One packet frame: its spectrum, its map, its k-plane, its conditional
-    spectrum (in the flow of slot 0, the snapshot at the packets' time) and its
+    spectrum and its refraction frame (both in the flow of slot 0, the snapshot
+    at the packets' time) and its
     transition frame recorded on the device (queued, no host wait) whether or
     not the frame itself is written.  ``trans``: the run's lag (0: never
     re-marked); packet frame ``index`` records against the mark, and re-marks
@@ -558,6 +581,8 @@ def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False
         ens.record_kmap()
     if conds:
         ens.record_cond()
+    if refrs:
+        ens.record_refr()
     if trans is not None:
         ens.record_trans(t)
         if trans and index % trans == 0:
@@ -816,7 +841,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                   kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False,
                   cond_by=None, cond_edges=None, cond_frac_bits=20,
                   trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20,
-                  recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20):
+                  recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20,
+                  refr_edges=None, refr_frac_bits=20):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -920,9 +946,24 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     f, Cg, every) and recycle_gen.bin (int32 per packet in the original order:
     its re-injections, written at the end); the other outputs are those of the
     recycled packets.
+    ``refr_edges`` (the na + 1 increasing class edges of the alignment
+    c = 2 gamma / sigma, e.g. alignment_edges(na); needs ``spectrum_edges``):
+    the refraction series (swrt_refr_series_*).  Beside every packet frame but
+    the first (written before any snapshot exists), after a recycle event that
+    falls on the frame, the counts of the packets over (alignment class, omega
+    class) and the per-class sums of omega-dot, omega-dot^2 and
+    gamma = d ln|k|/dt in quanta of 2^-``refr_frac_bits`` are recorded on the
+    device in the snapshot at the packets' time and written as refr_hist.bin
+    (int64, (na + 2) x (nw + 2) per frame, cell (ac, wc) at ac*(nw + 2) + wc),
+    refr_sums.bin (3 (nw + 2) + (na + 2) int64 per frame: omega-dot,
+    omega-dot^2 and gamma per omega class, then omega-dot per alignment
+    class), refr_stats.bin (n, rejected per frame) and refr_geom.bin (doubles:
+    na, nw, frac_bits, the alignment edges, the omega edges); frame i belongs
+    to packet frame i + 1; no other output changes and ``packet_files=False``
+    is allowed with it.
     Returns a dict of run facts (dt, Nsteps, steps run, frames written,
     final t, spectrum_frames, map_frames, track_frames, kmap_frames,
-    flow_frames, cond_frames, trans_frames, recycle_events)."""
+    flow_frames, cond_frames, trans_frames, recycle_events, refr_frames)."""
     _flow_args(flow_spectrum, Npackets)
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files, kmap_cells)
     map_args = _map_args(map_cells, map_frac_bits)
@@ -931,6 +972,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                            _ring_radius(max(ring_factors), f, Cg) if kmap_cells is not None else None)
     track_args = _track_args(track_ids, track_every, Npackets, 5)  # (5: packet_steps_per_save below)
     cond_args = _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges)
+    refr_args = _refr_args(refr_edges, refr_frac_bits, spectrum_edges)
     trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
     if trans_args is not None and Npackets <= 0:
         raise ValueError("the transition series needs packets")
@@ -998,6 +1040,9 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     conds = ens is not None and cond_args is not None
     if conds:  # (no frame beside the first packet frame: no snapshot exists yet)
         ens.begin_cond(spectrum_edges, cond_args[0], cond_args[1], cond_args[2], directory=out_dir)
+    refrs = ens is not None and refr_args is not None
+    if refrs:  # (no frame beside the first packet frame: no snapshot exists yet)
+        ens.begin_refr(spectrum_edges, refr_args[0], refr_args[1], directory=out_dir)
     trans = None  # (the lag, 0: never re-marked; None: no transition series)
     if ens is not None and trans_args is not None:  # (the mark beside the first packet frame; frames from the second on)
         _begin_trans(ens, trans_args, spectrum_edges, out_dir, dt * (packet_step_start - 1), Npackets,
@@ -1047,7 +1092,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                 group.flush()
                 if recycle and frames % recycle == 0:
                     ens.recycle(t)  # (before the frame: it holds no packet at or above the cut)
-                _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames)
+                _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames, refrs)
                 if flows:
                     model.record_flow_spectrum()
                 frames += 1
@@ -1068,6 +1113,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     cond_frames = ens.write_conds(out_dir) if conds else 0
     trans_frames = ens.write_trans(out_dir) if trans is not None else 0
     recycle_events = ens.write_recycle(out_dir) if recycle else 0
+    refr_frames = ens.write_refrs(out_dir) if refrs else 0
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -1078,7 +1124,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
                 track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames,
-                trans_frames=trans_frames, recycle_events=recycle_events)
+                trans_frames=trans_frames, recycle_events=recycle_events, refr_frames=refr_frames)
 
 
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
@@ -1089,7 +1135,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                         kmap_cells=None, kmap_kmax=None, kmap_frac_bits=16, flow_spectrum=False,
                         cond_by=None, cond_edges=None, cond_frac_bits=20,
                         trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20,
-                        recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20):
+                        recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20,
+                        refr_edges=None, refr_frac_bits=20):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
@@ -1101,7 +1148,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     ``flow_spectrum``, ``cond_by``, ``cond_edges``, ``cond_frac_bits``,
     ``trans_src_edges``, ``trans_by``, ``trans_lag``, ``trans_frac_bits``,
     ``recycle_omega``, ``recycle_seed``, ``recycle_every``,
-    ``recycle_frac_bits`` and a
+    ``recycle_frac_bits``, ``refr_edges``, ``refr_frac_bits`` and a
     sequence of factors as ``near_inertial_factor``: as in
     :func:`qgsw_raytrace`.
 
@@ -1121,6 +1168,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                            _ring_radius(max(ring_factors), f, Cg) if kmap_cells is not None else None)
     track_args = _track_args(track_ids, track_every, Npackets, 25)  # (25: packet_steps_per_save below)
     cond_args = _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges)
+    refr_args = _refr_args(refr_edges, refr_frac_bits, spectrum_edges)
     trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
     if trans_args is not None and Npackets <= 0:
         raise ValueError("the transition series needs packets")
@@ -1180,6 +1228,9 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     conds = ens is not None and cond_args is not None
     if conds:  # (no frame beside the first packet frame: no snapshot exists yet)
         ens.begin_cond(spectrum_edges, cond_args[0], cond_args[1], cond_args[2], directory=out_dir)
+    refrs = ens is not None and refr_args is not None
+    if refrs:  # (no frame beside the first packet frame: no snapshot exists yet)
+        ens.begin_refr(spectrum_edges, refr_args[0], refr_args[1], directory=out_dir)
     trans = None  # (the lag, 0: never re-marked; None: no transition series)
     if ens is not None and trans_args is not None:  # (the mark beside the first packet frame; frames from the second on)
         _begin_trans(ens, trans_args, spectrum_edges, out_dir, dt * (packet_step_start - 1), Npackets,
@@ -1227,7 +1278,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
             loop.flush()
             if recycle and frames % recycle == 0:
                 ens.recycle(loop.t)  # (before the frame: it holds no packet at or above the cut)
-            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames)
+            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames, refrs)
             if flows:
                 model.record_flow_spectrum()  # (the committed qk at loop.t; the next step is only speculative)
             frames += 1
@@ -1243,6 +1294,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     cond_frames = ens.write_conds(out_dir) if conds else 0
     trans_frames = ens.write_trans(out_dir) if trans is not None else 0
     recycle_events = ens.write_recycle(out_dir) if recycle else 0
+    refr_frames = ens.write_refrs(out_dir) if refrs else 0
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -1255,4 +1307,4 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     return dict(dt=dt, dts=dts, Nsteps=Nsteps, steps=step, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
                 track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames,
-                trans_frames=trans_frames, recycle_events=recycle_events)
+                trans_frames=trans_frames, recycle_events=recycle_events, refr_frames=refr_frames)
