@@ -254,17 +254,28 @@ int rebin(swrt_ctx* c, bool indirect, int tile = 0, int lanes = kTileThreads) {
 // The LDS-tiled leapfrog kernel and its workgroup width: two blended snapshots
 // or one, divergence-free (v5: the five-sum gather), its sums as fused
 // multiply-adds (v5 only), the sparse launch shape (two v5 snapshots only).
+// Each in two forms: plain (X = false: no history frames, one interval) and
+// everything on (X = true), for calls that write history frames or run
+// several intervals.
 struct TileKernel { void (*fn)(TileArgs); int threads; };
+template <bool X>
 TileKernel tile_kernel_of(bool two, bool v5, bool fma, bool sparse) {
   constexpr int T = kTile, M = kMargin, NT = kTileThreads, ST = kSparseThreads, PF = kSparsePrefetch;
-  constexpr int MW = kSparseMinWaves;
+  constexpr int MW = kSparseMinWaves, W4 = SWRT_TILE_MIN_WAVES;
   if (two && v5 && sparse)
-    return {fma ? tile_leapfrog_kernel<true, T, M, ST, true, true, PF, MW>
-                : tile_leapfrog_kernel<true, T, M, ST, true, false, PF, MW>, ST};
-  if (two && v5) return {fma ? tile_leapfrog_kernel<true, T, M, NT, true, true> : tile_leapfrog_kernel<true, T, M, NT, true>, NT};
-  if (two) return {tile_leapfrog_kernel<true, T, M, NT>, NT};
-  if (v5) return {fma ? tile_leapfrog_kernel<false, T, M, NT, true, true> : tile_leapfrog_kernel<false, T, M, NT, true>, NT};
-  return {tile_leapfrog_kernel<false, T, M, NT>, NT};
+    return {fma ? tile_leapfrog_kernel<true, T, M, ST, true, true, PF, MW, X, X>
+                : tile_leapfrog_kernel<true, T, M, ST, true, false, PF, MW, X, X>, ST};
+  if (two && v5)
+    return {fma ? tile_leapfrog_kernel<true, T, M, NT, true, true, 1, W4, X, X>
+                : tile_leapfrog_kernel<true, T, M, NT, true, false, 1, W4, X, X>, NT};
+  if (two) return {tile_leapfrog_kernel<true, T, M, NT, false, false, 1, W4, X, X>, NT};
+  if (v5)
+    return {fma ? tile_leapfrog_kernel<false, T, M, NT, true, true, 1, W4, X, X>
+                : tile_leapfrog_kernel<false, T, M, NT, true, false, 1, W4, X, X>, NT};
+  return {tile_leapfrog_kernel<false, T, M, NT, false, false, 1, W4, X, X>, NT};
+}
+TileKernel tile_kernel_of(bool two, bool v5, bool fma, bool sparse, bool hist, bool multi) {
+  return hist || multi ? tile_kernel_of<true>(two, v5, fma, sparse) : tile_kernel_of<false>(two, v5, fma, sparse);
 }
 
 int tile_launch(swrt_ctx* c, const StepArgs& a, bool count_next, const IvLaunch* iv = nullptr) {
@@ -303,7 +314,8 @@ int tile_launch(swrt_ctx* c, const StepArgs& a, bool count_next, const IvLaunch*
   const bool two = a.nslots == 2;
   const bool v5 = two ? (iv ? iv->div_free : two_v5(c, 2, 0)) : c->slot[0].div_free;
   const TileKernel tk = tile_kernel_of(two, v5, c->gather_mode == 1,
-                                       two && v5 && tile_threads(c, true, ntiles) == kSparseThreads);
+                                       two && v5 && tile_threads(c, true, ntiles) == kSparseThreads,
+                                       a.hist_x != nullptr, iv != nullptr);
   HIPCHK_RC(launch_tiles(c, tk.fn, tk.threads, t, zero));
   HIPCHK(c, hipGetLastError());
   // (a.f0: the view this launch bins by; a multi-interval launch: slot i0's)

@@ -58,6 +58,20 @@ struct TileArgs {
   double ivdt[kMaxIntervals];
 };
 
+// The kernel's argument block read again from the kernarg segment (scalar
+// loads that hit the constant cache).  The step loop holds about a hundred
+// scalars; an argument kept in a register across it is spilled to a VGPR lane
+// and read back.  What only a round's prologue or epilogue needs (the packet
+// buffers, n, the next-binning arrays) is loaded there instead: the empty asm
+// makes every call's pointer a value of its own, so these loads are not merged
+// with the ones at the kernel's entry.  (TileArgs is the kernel's only
+// argument: it starts the segment.)
+__device__ __forceinline__ auto tile_args_again() {
+  auto* p = (const __attribute__((address_space(4))) TileArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
 // Interval views by constant-index selects: a runtime index into the
 // by-value kernel argument would copy the whole argument to scratch.
 __device__ __forceinline__ const double* iv_nodes(const TileArgs& ta, int i) {
@@ -280,37 +294,82 @@ __device__ __forceinline__ void gather5_lds(const double2* lds, int node0, const
 // V5 (fields with v_y == -u_x exactly): 5 chunks for two snapshots —
 // {u,v}0 {ux,uy}0 {vx0,vx1} {u,v}1 {ux,uy}1 — or 3 for one, whose third
 // holds {vx, vy} of which only vx is read.
+//
+// One record (16-B pieces s0[0..2], s1[0..2]) into window slot d.
+template <bool TWO, int WN, bool V5>
+__device__ __forceinline__ void stage_record(const double2* s0, const double2* s1, int d, double2* win) {
+  if constexpr (V5 && TWO) {
+    const double2 a0 = s0[0], a1 = s0[1], a2 = s0[2], b0 = s1[0], b1 = s1[1], b2 = s1[2];
+    win[0 * WN + d] = a0;
+    win[1 * WN + d] = a1;
+    win[2 * WN + d] = make_double2(a2.x, b2.x);
+    win[3 * WN + d] = b0;
+    win[4 * WN + d] = b1;
+  } else if constexpr (TWO) {
+    const double2 a0 = s0[0], a1 = s0[1], a2 = s0[2], b0 = s1[0], b1 = s1[1], b2 = s1[2];
+    win[0 * WN + d] = a0;
+    win[1 * WN + d] = a1;
+    win[2 * WN + d] = a2;
+    win[3 * WN + d] = b0;
+    win[4 * WN + d] = b1;
+    win[5 * WN + d] = b2;
+  } else {
+    const double2 a0 = s0[0], a1 = s0[1], a2 = s0[2];
+    win[0 * WN + d] = a0;
+    win[1 * WN + d] = a1;
+    win[2 * WN + d] = a2;
+  }
+}
+// Lanes take whole window rows: CW (the power of two >= W) consecutive lanes
+// own one row, so a wave of 64 holds 64 / CW whole rows, a lane's column
+// wj = tid % CW is fixed for the launch and its row advances by NT / CW per
+// pass — shifts and masks, no division by W.
+//
+// Periodic wrap.  The tile origins lie in [0, nx - 1] (tiles_per_side rounds
+// up), so the window's node coordinates g = o - M - 2 + w, w in [0, W - 1],
+// lie in [-M - 2, nx - 1 + T + M + 2]: g + nx >= 0 needs nx >= M + 2 and
+// g - nx < nx needs nx >= T + M + 2.  Both hold for nx >= W = T + 5 + 2M,
+// where one conditional wrap each way reduces g to [0, nx); smaller grids
+// (the window laps the grid) take the remainder, under a launch-uniform
+// branch.  The fast path also forms the record's byte offset in 32 bits,
+// once for both node arrays (npad^2 records of 48 B below 2^32), as the
+// unsigned offset of a load from the scalar array base.
 template <bool TWO, int T, int M, int NT, int WS = T + 5 + 2 * M, bool V5 = false>
 __device__ __forceinline__ void stage_window_regs(const FieldView& f0, const FieldView& f1, int ox, int oy,
                                                   double2* win) {
   constexpr int W = T + 5 + 2 * M;
   constexpr int WN = W * WS;  // chunk size (rows of WS >= W nodes)
+  constexpr int CW = W <= 32 ? 32 : (W <= 64 ? 64 : 128);  // lanes per window row
+  constexpr int RP = NT / CW;                               // rows per pass
+  static_assert(W <= CW && NT % CW == 0, "window rows per workgroup pass");
   const int nx = f0.nx, npad = f0.npad;
-  for (int e = threadIdx.x; e < W * W; e += NT) {
-    const int wi = e / W, wj = e % W;
-    int gx = (ox - M - 2 + wi) % nx; gx += gx < 0 ? nx : 0;
+  const int wj = (int)threadIdx.x % CW;
+  int wi = (int)threadIdx.x / CW;
+  if (wj >= W) return;
+  const char* n0 = reinterpret_cast<const char*>(f0.nodes);
+  const char* n1 = reinterpret_cast<const char*>(f1.nodes);
+  constexpr unsigned kRecBytes = kRec * sizeof(double);
+  if (nx >= W && (uint64_t)npad * (uint64_t)npad * kRecBytes < (1ull << 32)) {
+    int gy = oy - M - 2 + wj;
+    gy += gy < 0 ? nx : 0;
+    gy -= gy >= nx ? nx : 0;
+    const unsigned col = (unsigned)(gy + kPadLo) * kRecBytes;
+    const unsigned rowb = (unsigned)npad * kRecBytes;
+    for (int d = wi * WS + wj; wi < W; wi += RP, d += RP * WS) {
+      int gx = ox - M - 2 + wi;
+      gx += gx < 0 ? nx : 0;
+      gx -= gx >= nx ? nx : 0;
+      const unsigned off = (unsigned)(gx + kPadLo) * rowb + col;
+      stage_record<TWO, WN, V5>(reinterpret_cast<const double2*>(n0 + off),
+                                reinterpret_cast<const double2*>(n1 + off), d, win);
+    }
+  } else {
     int gy = (oy - M - 2 + wj) % nx; gy += gy < 0 ? nx : 0;
-    const size_t src = ((size_t)(gx + kPadLo) * npad + (gy + kPadLo)) * kRec;
-    const int d = wi * WS + wj;
-    const double2* s0 = reinterpret_cast<const double2*>(f0.nodes + src);
-    if constexpr (V5 && TWO) {
-      const double2* s1 = reinterpret_cast<const double2*>(f1.nodes + src);
-      const double2 a0 = s0[0], a1 = s0[1], a2 = s0[2], b0 = s1[0], b1 = s1[1], b2 = s1[2];
-      win[0 * WN + d] = a0;
-      win[1 * WN + d] = a1;
-      win[2 * WN + d] = make_double2(a2.x, b2.x);
-      win[3 * WN + d] = b0;
-      win[4 * WN + d] = b1;
-    } else {
-      win[0 * WN + d] = s0[0];
-      win[1 * WN + d] = s0[1];
-      win[2 * WN + d] = s0[2];
-      if constexpr (TWO) {
-        const double2* s1 = reinterpret_cast<const double2*>(f1.nodes + src);
-        win[3 * WN + d] = s1[0];
-        win[4 * WN + d] = s1[1];
-        win[5 * WN + d] = s1[2];
-      }
+    for (; wi < W; wi += RP) {
+      int gx = (ox - M - 2 + wi) % nx; gx += gx < 0 ? nx : 0;
+      const size_t off = ((size_t)(gx + kPadLo) * npad + (gy + kPadLo)) * kRecBytes;
+      stage_record<TWO, WN, V5>(reinterpret_cast<const double2*>(n0 + off),
+                                reinterpret_cast<const double2*>(n1 + off), wi * WS + wj, win);
     }
   }
 }
@@ -329,6 +388,103 @@ __device__ unsigned long long swrt_phase_dbg[16384 * 8];
   } while (0)
 #endif
 
+// Step 2 of tile_leapfrog_kernel: the in-tile counting sort of one batch, nb
+// packets from binned slot b0, by the cell of the (led) position; order[r] =
+// the input slot of rank r.  Sort launches are the first of an interval, so
+// the input is the launch's own (s.x, s.k, src).  Called by every lane.
+// The sort takes its arguments from the kernarg segment, and the lane id as a
+// value of its own (the empty asm): lane-id compare masks and the reciprocal
+// of nx hoisted out of the caller's batch loop would be held, spilled, across
+// the step loop of launches that never sort.
+template <int T, int NT, int NB>
+__device__ __forceinline__ void sort_batch_by_cell(int b0, int nb, bool first_batch, int tile, int* hist,
+                                                   int* kr, int* order) {
+  const auto* g = tile_args_again();
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int nx = g->s.f0.nx;
+  const int tx = (int)((unsigned)tile / (unsigned)g->ntx), ty = tile - tx * g->ntx;
+  const int ox = tx * T, oy = ty * T;  // tile origin (cells)
+  const int64_t n = g->s.n;
+  const double* xin = g->s.x;
+  const double* kin = g->s.k;
+  const int* srcp = g->src;
+  const double sort_lead = g->sort_lead, gH = g->s.gH, f2 = g->s.f2, inv_dx = g->s.f0.inv_dx;
+  for (int h = tid; h < NB; h += NT) hist[h] = 0;
+  __syncthreads();  // (also publishes the window on the first batch)
+  if (first_batch) SWRT_STAMP(1);
+  for (int i = tid; i < nb; i += NT) {
+    const int64_t p = srcp ? srcp[b0 + i] : b0 + i;
+    // sort key position: the packet drifted by its group velocity to the
+    // middle of the steps this order serves (x0 + sort_lead*gH*k/omega).
+    // Packets of one cell separate at up to 2|cg| (k points every way), so
+    // keys of the launch-start cell go stale within a cycle; the lead
+    // keeps the lane groups compact over the whole cycle (LDS bank-conflict
+    // model, tools/conflict_model.py: 1.40 -> 1.22 LDS cycles per access).
+    // Order only: results do not depend on it.
+    double xs = xin[p], ys = xin[n + p];
+    if (sort_lead != 0.0) {
+      const double kx = kin[p], ky = kin[n + p];
+      const double s = sort_lead * gH / sqrt(f2 + gH * (kx * kx + ky * ky));
+      xs += s * kx;
+      ys += s * ky;
+    }
+    const int ic = fast_cell(xs, inv_dx, nx);
+    const int jc = fast_cell(ys, inv_dx, nx);
+    // cells predicted beyond the tile sort at its edge
+    const int dx_ = min(max(ring_diff(ic, ox, nx), 0), T - 1);
+    const int dy_ = min(max(ring_diff(jc, oy, nx), 0), T - 1);
+    // Z-order of the cell within the tile (T = 16): a run of 16 consecutive
+    // packets (one ds_read_b128 lane group) stays inside a 2x2 or 4x4 block
+    // of cells — with the 12 (mod 16) row stride a conflict-free read
+    // (measured: bank-conflict cycles -36 %, LDS busy -15 %)
+    int key;
+    if constexpr (T == 16) {
+      key = (dx_ >= 0 && dx_ < T && dy_ >= 0 && dy_ < T)
+                ? ((dy_ & 1) | ((dx_ & 1) << 1) | ((dy_ & 2) << 1) | ((dx_ & 2) << 2) |
+                   ((dy_ & 4) << 2) | ((dx_ & 4) << 3) | ((dy_ & 8) << 3) | ((dx_ & 8) << 4))
+                : T * T;
+    } else {  // the same interleave for any power-of-two T
+      key = 0;
+#pragma unroll
+      for (int b = 0; (1 << b) < T; ++b) key |= (((dy_ >> b) & 1) << (2 * b)) | (((dx_ >> b) & 1) << (2 * b + 1));
+    }
+    const int r = atomicAdd(&hist[key], 1);
+    kr[i] = (key << 16) | r;
+  }
+  __syncthreads();
+  if (tid < 64) {  // exclusive scan of NB bins by one wavefront
+    constexpr int PER = (NB + 63) / 64;
+    int loc[PER];
+    int sum = 0;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int h = tid * PER + q;
+      loc[q] = h < NB ? hist[h] : 0;
+      sum += loc[q];
+    }
+    int incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int v = __shfl_up(incl, off, 64);
+      if (tid >= off) incl += v;
+    }
+    int run = incl - sum;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int h = tid * PER + q;
+      if (h < NB) hist[h] = run;
+      run += loc[q];
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < nb; i += NT) {
+    const int v = kr[i];
+    order[hist[v >> 16] + (v & 0xffff)] = srcp ? srcp[b0 + i] : b0 + i;  // input slot
+  }
+  __syncthreads();
+}
+
 #ifndef SWRT_TILE_MIN_WAVES
 #define SWRT_TILE_MIN_WAVES 4
 #endif
@@ -338,8 +494,13 @@ __device__ unsigned long long swrt_phase_dbg[16384 * 8];
 // PF: the five-sum gather's prefetch depth (gather5_lds); MINW: the waves per
 // SIMD the register budget is sized for (4: 128 VGPRs; the sparse-tile
 // instantiation, 256 threads with PF 3, takes 2: 256 VGPRs).
+// HIST / MULTI: what the call may use.  The plain instantiation (neither) has
+// no history frames and one interval: no interval loop, no iv_nodes / iv_dt
+// selects, no save_every / frame0 arithmetic, and none of their arguments
+// live.  The other one (both) takes every call; the host picks
+// (tile_kernel_of).  Same arithmetic in both.
 template <bool TWO, int T, int M, int NT, bool V5 = false, bool FMA = false, int PF = 1,
-          int MINW = SWRT_TILE_MIN_WAVES>
+          int MINW = SWRT_TILE_MIN_WAVES, bool HIST = true, bool MULTI = true>
 __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
   static_assert(!FMA || V5, "the FMA gather exists for the five-sum window only");
   constexpr int W = T + 5 + 2 * M;  // window side in nodes
@@ -363,14 +524,34 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
 
   const StepArgs& a = ta.s;
   const int tid = threadIdx.x;
+  // The tile and its packet range are the same in every lane but come from
+  // vector loads (order[], starts[]): readfirstlane makes them, and all that
+  // derives from them (origins, loop bounds, base addresses), scalar.
   int pbeg, pend;
-  const int tile = wg_work(ta, pbeg, pend);
-  const int tx = tile / ta.ntx, ty = tile % ta.ntx;
+  // (the tile clamped to the grid's: the window's one-wrap addressing relies
+  // on an origin inside [0, nx), whatever a corrupted binning says)
+  const int tile = min(max(__builtin_amdgcn_readfirstlane(wg_work(ta, pbeg, pend)), 0), ta.ntx * ta.ntx - 1);
+  pbeg = __builtin_amdgcn_readfirstlane(pbeg);
+  pend = __builtin_amdgcn_readfirstlane(pend);
   const int nx = a.f0.nx, npad = a.f0.npad;
-  const int ox = tx * T, oy = ty * T;  // tile origin (cells)
-  // the window's first cell (origin - M) on the ring [0, nx)
-  const int oxm = ((ox - M) % nx + nx) % nx, oym = ((oy - M) % nx + nx) % nx;
-  if (tid < 9) nbr[tid] = 0;
+  int ox, oy;  // tile origin (cells)
+  {
+    const int tx = (int)((unsigned)tile / (unsigned)ta.ntx), ty = tile - tx * ta.ntx;
+    ox = tx * T;
+    oy = ty * T;
+  }
+  // the window's first cell (origin - M) on the ring [0, nx): the origin lies
+  // in [0, nx), so one wrap does unless the grid is smaller than the margin
+  int oxm = ox - M, oym = oy - M;
+  if (nx >= M) {
+    oxm += oxm < 0 ? nx : 0;
+    oym += oym < 0 ? nx : 0;
+  } else {
+    oxm = (oxm % nx + nx) % nx;
+    oym = (oym % nx + nx) % nx;
+  }
+  // (the tile's own count starts at its packets: the movers subtract themselves)
+  if (tid < 9) nbr[tid] = tid == 4 ? pend - pbeg : 0;
 #ifdef SWRT_PHASE_TIMING
   if (tid == 0) nfall = 0;
   if (tid == 0) simds = 0;
@@ -394,26 +575,24 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
   if (tid == 0) swrt_phase_dbg[blockIdx.x * 8 + 6] |= (unsigned long long)simds << 32;
 #endif
 
-  const int lane_rank = b128_lane_rank(tid & 63);
-  const int nint = ta.ivmode ? ta.nint : 1;
+  const unsigned lane_rank = (unsigned)b128_lane_rank(tid & 63);
+  const int wave0 = __builtin_amdgcn_readfirstlane(tid & ~63);  // the wave's first rank of a round
+  const bool ivmode = MULTI && ta.ivmode;
+  const int nint = ivmode ? ta.nint : 1;
   for (int ivl = 0; ivl < nint; ++ivl) {
   // interval ivl of a multi-interval launch (TileArgs::ivmode): its snapshot
   // pair and step size; the later intervals take the previous one's output
   // in place, already in cell order
   FieldView fa = a.f0, fb = a.f1;
-  if (ta.ivmode) {
+  if (ivmode) {
     fa.nodes = iv_nodes(ta, ivl);
     fb.nodes = iv_nodes(ta, ivl + 1);
   }
-  const double dt = ta.ivmode ? iv_dt(ta, ivl) : a.dt;
-  const double half = ta.ivmode ? 0.5 * dt : a.half;
-  const bool first = ivl == 0;
-  const double* xin = first ? a.x : ta.x_out;
-  const double* kin = first ? a.k : ta.k_out;
-  const int* pin = first ? a.perm : ta.perm_out;
+  const double dt = ivmode ? iv_dt(ta, ivl) : a.dt;
+  const double half = ivmode ? 0.5 * dt : a.half;
+  const bool first = !MULTI || ivl == 0;
   const int sortc = first ? ta.sort_cells : 0;
-  const int* srcp = first ? ta.src : nullptr;
-  int* nkeys = ivl == nint - 1 ? ta.next_keys : nullptr;
+  const bool last = !MULTI || ivl == nint - 1;
   const int64_t sbase = a.s0 + (int64_t)ivl * a.nsteps;
   if (!first) __syncthreads();  // every wave is done with the previous window
 
@@ -423,96 +602,48 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
     __syncthreads();  // publish the window
     SWRT_STAMP(1);
   }
-  for (int b0 = pbeg; b0 < pend; b0 += MAXB) {
-    const int nb = min(MAXB, pend - b0);
-    if (sortc) {
+  // A sort launch takes the tile's packets in batches of MAXB (what the LDS
+  // sort arrays hold).  Without a sort nothing uses those arrays: one pass
+  // over [pbeg, pend), no batch loop and no barrier after the rounds.  A
+  // packet's output slot po = b0 + r is the same either way (MAXB is a whole
+  // number of 64-rank rounds), so the output order, perm and the next
+  // launch's input are those of the batched pass.
+  const int bstep = sortc ? MAXB : max(pend - pbeg, 1);
+  for (int b0 = pbeg; b0 < pend; b0 += bstep) {
+    const int nb = min(bstep, pend - b0);
     // 2. in-tile counting sort by the cell of the current position
-    for (int h = tid; h < NB; h += NT) hist[h] = 0;
-    __syncthreads();  // (also publishes the window on the first batch)
-    if (b0 == pbeg) SWRT_STAMP(1);
-    for (int i = tid; i < nb; i += NT) {
-      const int64_t p = srcp ? srcp[b0 + i] : b0 + i;
-      // sort key position: the packet drifted by its group velocity to the
-      // middle of the steps this order serves (x0 + sort_lead*gH*k/omega).
-      // Packets of one cell separate at up to 2|cg| (k points every way), so
-      // keys of the launch-start cell go stale within a cycle; the lead
-      // keeps the lane groups compact over the whole cycle (LDS bank-conflict
-      // model, tools/conflict_model.py: 1.40 -> 1.22 LDS cycles per access).
-      // Order only: results do not depend on it.
-      double xs = xin[p], ys = xin[a.n + p];
-      if (ta.sort_lead != 0.0) {
-        const double kx = kin[p], ky = kin[a.n + p];
-        const double s = ta.sort_lead * a.gH / sqrt(a.f2 + a.gH * (kx * kx + ky * ky));
-        xs += s * kx;
-        ys += s * ky;
-      }
-      const int ic = fast_cell(xs, a.f0.inv_dx, nx);
-      const int jc = fast_cell(ys, a.f0.inv_dx, nx);
-      // cells predicted beyond the tile sort at its edge
-      const int dx_ = min(max(ring_diff(ic, ox, nx), 0), T - 1);
-      const int dy_ = min(max(ring_diff(jc, oy, nx), 0), T - 1);
-      // Z-order of the cell within the tile (T = 16): a run of 16 consecutive
-      // packets (one ds_read_b128 lane group) stays inside a 2x2 or 4x4 block
-      // of cells — with the 12 (mod 16) row stride a conflict-free read
-      // (measured: bank-conflict cycles -36 %, LDS busy -15 %)
-      int key;
-      if constexpr (T == 16) {
-        key = (dx_ >= 0 && dx_ < T && dy_ >= 0 && dy_ < T)
-                  ? ((dy_ & 1) | ((dx_ & 1) << 1) | ((dy_ & 2) << 1) | ((dx_ & 2) << 2) |
-                     ((dy_ & 4) << 2) | ((dx_ & 4) << 3) | ((dy_ & 8) << 3) | ((dx_ & 8) << 4))
-                  : T * T;
-      } else {  // the same interleave for any power-of-two T
-        key = 0;
-#pragma unroll
-        for (int b = 0; (1 << b) < T; ++b) key |= (((dy_ >> b) & 1) << (2 * b)) | (((dx_ >> b) & 1) << (2 * b + 1));
-      }
-      const int r = atomicAdd(&hist[key], 1);
-      kr[i] = (key << 16) | r;
-    }
-    __syncthreads();
-    if (tid < 64) {  // exclusive scan of NB bins by one wavefront
-      constexpr int PER = (NB + 63) / 64;
-      int loc[PER];
-      int sum = 0;
-#pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        const int h = tid * PER + q;
-        loc[q] = h < NB ? hist[h] : 0;
-        sum += loc[q];
-      }
-      int incl = sum;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (tid >= off) incl += v;
-      }
-      int run = incl - sum;
-#pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        const int h = tid * PER + q;
-        if (h < NB) hist[h] = run;
-        run += loc[q];
-      }
-    }
-    __syncthreads();
-    for (int i = tid; i < nb; i += NT) {
-      const int v = kr[i];
-      order[hist[v >> 16] + (v & 0xffff)] = srcp ? srcp[b0 + i] : b0 + i;  // input slot
-    }
-    __syncthreads();
-    }  // sort_cells
+    if (sortc) sort_batch_by_cell<T, NT, NB>(b0, nb, b0 == pbeg, tile, hist, kr, order);
     if (b0 == pbeg) SWRT_STAMP(2);
 
     // 3. advance the packets in sorted order (lane -> rank remapped for the
     //    ds_read_b128 lane groups; every rank of the batch is still taken once)
-    for (int r0 = tid & ~63; r0 < nb; r0 += NT) {
-      const int r = r0 + lane_rank;
+    //    A round's first slot b0 + r0 is wave-uniform: the state, perm and
+    //    output addresses are scalar bases plus the lane's constant rank.
+    for (int r0 = wave0; r0 < nb; r0 += NT) {
+      const int r = r0 + (int)lane_rank;
       if (r >= nb) continue;
-      const int64_t pi = sortc ? order[r] : b0 + r;
-      const int64_t po = b0 + r;
-      double x0 = xin[pi], y0 = xin[a.n + pi];
-      double k0 = kin[pi], l0 = kin[a.n + pi];
-      const int orig = pin[pi];
+      const int64_t slot0 = (int64_t)b0 + r0;
+      double x0, y0, k0, l0;
+      int orig;
+      {
+        const auto* g = tile_args_again();
+        const int64_t n = g->s.n;
+        const double* xi = first ? g->s.x : g->x_out;
+        const double* ki = first ? g->s.k : g->k_out;
+        const int* pi_ = first ? g->s.perm : g->perm_out;
+        if (sortc) {
+          const int64_t pi = order[r];
+          x0 = xi[pi]; y0 = xi[n + pi];
+          k0 = ki[pi]; l0 = ki[n + pi];
+          orig = pi_[pi];
+        } else {
+          const double* xr = xi + slot0;
+          const double* kr_ = ki + slot0;
+          x0 = xr[lane_rank]; y0 = (xr + n)[lane_rank];
+          k0 = kr_[lane_rank]; l0 = (kr_ + n)[lane_rank];
+          orig = (pi_ + slot0)[lane_rank];
+        }
+      }
       // half-step drift of the current k, half * gH*k/omega(k)
       // (ode_symplectic.m:10-16): the second drift of a step and the first
       // drift of the next one use the same k (k0 = k2), hence the same
@@ -521,9 +652,8 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
       drift_inc(k0, l0, a.f2, a.gH, half, a.fastdisp, hcx, hcy);
       // the blend's step index as a double, counted up by exact additions
       // (integers < 2^53): (double)sg without an int64 conversion per step
-      double sgd = (double)(ta.ivmode ? (int64_t)0 : sbase);
+      double sgd = (double)(ivmode ? (int64_t)0 : sbase);
       for (int st = 0; st < a.nsteps; ++st) {
-        const int64_t sg = sbase + st;
         const double alpha = a.alpha0 + sgd * a.dalpha;
         sgd = sgd + 1.0;
         const double x1 = x0 + hcx;
@@ -547,7 +677,13 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
           else
             gather6_lds<TWO, WS, WNP>(win, (int)(ux * WS + uy), sc, I, J);
         } else {
-          gather6_lean<TWO, FMA>(fa.nodes, fb.nodes, npad, sc, I, J);
+          // (rare: the plain form loads the node arrays here, not across the loop)
+          if constexpr (MULTI) {
+            gather6_lean<TWO, FMA>(fa.nodes, fb.nodes, npad, sc, I, J);
+          } else {
+            const auto* g = tile_args_again();
+            gather6_lean<TWO, FMA>(g->s.f0.nodes, g->s.f1.nodes, g->s.f0.npad, sc, I, J);
+          }
         }
         if constexpr (TWO) {
           const double oma = 1 - alpha;
@@ -567,21 +703,32 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
         y0 = y2 + hcy;
         k0 = k2;
         l0 = l2;
-        if (a.hist_x != nullptr && ((sg + 1) % a.save_every) == 0) {
-          const int64_t fr = a.frame0 + (sg + 1) / a.save_every - 1;
-          double* hx = a.hist_x + fr * 2 * a.n;
-          double* hk = a.hist_k + fr * 2 * a.n;
-          hx[orig] = x0; hx[a.n + orig] = y0;
-          hk[orig] = k0; hk[a.n + orig] = l0;
+        if constexpr (HIST) {
+          const int64_t sg = sbase + st;
+          if (a.hist_x != nullptr && ((sg + 1) % a.save_every) == 0) {
+            const int64_t fr = a.frame0 + (sg + 1) / a.save_every - 1;
+            double* hx = a.hist_x + fr * 2 * a.n;
+            double* hk = a.hist_k + fr * 2 * a.n;
+            hx[orig] = x0; hx[a.n + orig] = y0;
+            hk[orig] = k0; hk[a.n + orig] = l0;
+          }
         }
       }
-      ta.x_out[po] = x0; ta.x_out[a.n + po] = y0;
-      ta.k_out[po] = k0; ta.k_out[a.n + po] = l0;
-      ta.perm_out[po] = orig;
-      if (nkeys != nullptr) {  // fused histogram for the next re-binning
-        const int ic = fast_cell(x0, a.f0.inv_dx, nx);
-        const int jc = fast_cell(y0, a.f0.inv_dx, nx);
-        const int ntx_ = ta.ntx;
+      const auto* g = tile_args_again();
+      const int64_t n = g->s.n;
+      double* xw = g->x_out + slot0;
+      double* kw = g->k_out + slot0;
+      xw[lane_rank] = x0; (xw + n)[lane_rank] = y0;
+      kw[lane_rank] = k0; (kw + n)[lane_rank] = l0;
+      (g->perm_out + slot0)[lane_rank] = orig;
+      int* nkeys = g->next_keys;
+      if (last && nkeys != nullptr) {  // fused histogram for the next re-binning
+        const int64_t po = slot0 + lane_rank;
+        const int nxk = g->s.f0.nx;  // (its reciprocal is formed here, not held across the step loop)
+        const int ic = fast_cell(x0, a.f0.inv_dx, nxk);
+        const int jc = fast_cell(y0, a.f0.inv_dx, nxk);
+        const int ntx_ = g->ntx;
+        const int tx = (int)((unsigned)tile / (unsigned)ntx_), ty = tile - tx * ntx_;
         const int ntx2 = ic / T, nty2 = jc / T;
         nkeys[po] = ntx2 * ntx_ + nty2;
         const int ddx = ring_diff(ntx2, tx, ntx_), ddy = ring_diff(nty2, ty, ntx_);
@@ -594,21 +741,29 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
           if (ddx >= -1 && ddx <= 1 && ddy >= -1 && ddy <= 1)
             atomicAdd(&nbr[(ddx + 1) * 3 + (ddy + 1)], 1);
           else
-            atomicAdd(&ta.next_counts[ntx2 * ntx_ + nty2], 1);
+            atomicAdd(&g->next_counts[ntx2 * ntx_ + nty2], 1);
         }
       }
     }
-    __syncthreads();  // LDS sort arrays are reused by the next batch
+#ifdef SWRT_PHASE_TIMING
+    __syncthreads();  // (diagnostic build: stamp 3 is "every wave's rounds are done")
+#else
+    if (sortc) __syncthreads();  // LDS sort arrays are reused by the next batch
+#endif
     if (b0 == pbeg) SWRT_STAMP(3);
   }
   }  // intervals
-  if (ta.next_keys != nullptr) {
+  const auto* g = tile_args_again();
+  if (g->next_keys != nullptr) {
     __syncthreads();
-    const int v = tid < 9 ? nbr[tid] + (tid == 4 ? pend - pbeg : 0) : 0;
+    int t9 = tid;  // (a value of its own: the entry's mask of tid < 9 is not held across the rounds)
+    asm volatile("" : "+v"(t9));
+    const int v = t9 < 9 ? nbr[t9] : 0;
     if (v != 0) {
-      const int n_ = ta.ntx;
-      const int gx = ((tx + tid / 3 - 1) % n_ + n_) % n_, gy = ((ty + tid % 3 - 1) % n_ + n_) % n_;
-      atomicAdd(&ta.next_counts[gx * n_ + gy], v);
+      const int n_ = g->ntx;
+      const int tx = (int)((unsigned)tile / (unsigned)n_), ty = tile - tx * n_;
+      const int gx = ((tx + t9 / 3 - 1) % n_ + n_) % n_, gy = ((ty + t9 % 3 - 1) % n_ + n_) % n_;
+      atomicAdd(&g->next_counts[gx * n_ + gy], v);
     }
   }
   SWRT_STAMP(4);
