@@ -952,6 +952,115 @@ int swrt_refr_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* c
 int swrt_refr_series_reset(swrt_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * The absolute-frequency series: the distribution of the ray Hamiltonian
+ * Omega = omega(k) + U(x,t).k over the packets beside that of omega, and its
+ * rate along the rays, dOmega/dt = k . dU/dt, reduced per class and kept on
+ * the device as integers.  In a steady flow Omega is conserved per packet and
+ * omega only wanders inside the Doppler band |U.k| around it; only the
+ * unsteadiness of the flow diffuses Omega, which is what lets the
+ * energy-vs-omega spectrum of analysis/load_data.m:33-52 keep spreading.  The
+ * reference watches Omega (symplectic_full_fourier.m:41,54-57,
+ * SW_zero_background_raytracing.m:57,85-87); swrt_raydiag_* gives moments of
+ * its relative change, this series its distribution and its rate.
+ *
+ * The flow is linear in time between two snapshots (interpolate_U.m:19-23),
+ * so for the ODE the packets solve dU/dt = (U2 - U1)/tau exactly, tau the time
+ * between the snapshots.  The records name their two slots: slot_a holds the
+ * flow at alpha = 0, slot_b the flow at alpha = 1.
+ *
+ * Per packet.  The state is (x, y, k1, k2); A[0..1] and B[0..1] are (u, v) of
+ * slot_a and slot_b at (x, y), the bits swrt_eval(nslots = 1) gives with that
+ * slot in place 0 and the same bump.  Every operation below is rounded on its
+ * own (no fused multiply-add):
+ *   two snapshots:  oma = 1 - alpha
+ *                   u   = oma*A[0] + alpha*B[0]    swrt_eval's blend (nslots = 2)
+ *                   v   = oma*A[1] + alpha*B[1]
+ *                   ut  = (B[0] - A[0]) / tau
+ *                   vt  = (B[1] - A[1]) / tau
+ *   one snapshot:   u = A[0];  v = A[1];  Od below is the literal 0.0
+ *   kk  = k1*k1 + k2*k2
+ *   w   = sqrt(f2 + Cg2*kk)                the spectrum series' omega (load_data.m:33)
+ *   D   = u*k1 + v*k2                      the Doppler shift, swrt_raydiag's dot(U, k)
+ *   Om  = w + D                            swrt_raydiag_sample's Omega when gH == Cg*Cg
+ *   Od  = ut*k1 + vt*k2                    dOmega/dt along the ray
+ * with f2 = f*f and Cg2 = Cg*Cg.  With S = 2^frac_bits: qO = rint(Od*S),
+ * qO2 = rint((Od*Od)*S), qD = rint(D*S), round half even.
+ *
+ * Classes.  wc is the spectrum series' rule over omega_edges (a row [below,
+ * bin 0 .. bin nw-1, above], the last bin closed) and oc the same rule for Om
+ * over abs_edges with no bins.
+ *
+ * Rejected, adding to stats[1] and to nothing else, is a packet with any of
+ *   Om or Od NaN;
+ *   !(fabs(w*S) < 2^38);  !(fabs(Om*S) < 2^38);  !(fabs(D*S) < 2^38);
+ *   !(fabs(Od*S) < 2^38);  !((Od*Od)*S < 2^38).
+ * A packet with k = 0 is accepted: w = f, D = 0.
+ *
+ * A frame holds
+ *   counts  (no + 2) x (nw + 2) int64, Omega class major:
+ *           counts[oc * (nw + 2) + wc];
+ *   sums    3 (nw + 2) + 2 (no + 2) int64, signed sums in two's complement:
+ *           sums[0 * (nw + 2) + wc] += qO,  sums[1 * (nw + 2) + wc] += qO2,
+ *           sums[2 * (nw + 2) + wc] += qD,
+ *           sums[3 * (nw + 2) + oc] += qO,  sums[3 * (nw + 2) + (no + 2) + oc] += qO2;
+ *   stats   2 int64 [n, rejected].
+ * The counts of a frame sum to n - rejected, and their marginal over the
+ * Omega classes is the spectrum series' row of the accepted packets.  With
+ * n <= 2^24 every sum stays below 2^62.  Integer addition is exact and
+ * order-free: a frame depends on the packet set and the two snapshots alone
+ * (two contexts, a re-binning between two records, either advance call and
+ * either packet-stream setting give the same bits), and the frames of shards
+ * combine by adding.  Positions must be finite, as for every gather of the
+ * library.  swrt_packets_set with another N empties the series.
+ * ------------------------------------------------------------------------- */
+
+/* Open a series: 1 <= nw, no <= 4096 with (no + 2) * (nw + 2) <= 65536 cells
+ * (512 KB a frame), both edge arrays finite and increasing,
+ * 0 <= frac_bits <= 32 (SWRT_ERR_ARG with a message otherwise).  Empties the
+ * series. */
+int swrt_absfreq_series_begin(swrt_ctx* ctx, double f, double Cg, const double* omega_edges, int64_t nw,
+                              const double* abs_edges, int64_t no, int frac_bits);
+
+/* Append the frame of the current packets in the flow of slot_a (alpha = 0)
+ * and slot_b (alpha = 1), both in 0..SWRT_MAX_SLOTS-1, blended at alpha, the
+ * snapshots tau apart; slot_b = -1: one snapshot, alpha and tau are ignored
+ * and the rates are zero.  Queued on the packet stream after whatever last
+ * wrote the packets and after the snapshot writes of both slots, no host wait
+ * (growing the series past its capacity, which doubles, may wait for the
+ * stream); a later snapshot into either slot waits for the record.  While the
+ * count plane has at most 16384 cells and fits a workgroup's LDS share beside
+ * the sums, every workgroup counts into a private plane in LDS and adds its
+ * non-zero cells to the frame; beyond, every packet adds through global
+ * memory: the same integers.  SWRT_ERR_STATE before
+ * swrt_absfreq_series_begin; SWRT_ERR_ARG with a slot out of range,
+ * slot_a == slot_b, an unset slot, two grids, with two snapshots a tau that
+ * is zero or not finite (a negative tau is allowed), no packets, and with
+ * more than 2^24 packets. */
+int swrt_absfreq_series_record(swrt_ctx* ctx, int slot_a, int slot_b, double alpha, double tau, double bump);
+
+/* One frame per history frame in [first, first + count), frame i in the flow
+ * at alphas[i] (alphas may be NULL with one snapshot): the same bits as
+ * swrt_absfreq_series_record on packets set to that frame.  With two
+ * snapshots the call waits for the stream once, before its launches, while
+ * alphas goes to the device.  A range out of bounds: SWRT_ERR_ARG. */
+int swrt_absfreq_series_record_history(swrt_ctx* ctx, int64_t first, int64_t count, int slot_a, int slot_b,
+                                       const double* alphas, double tau, double bump);
+
+/* Frames recorded since begin or the last reset; nw and no of the open
+ * series, 0 if none (either pointer may be NULL). */
+int64_t swrt_absfreq_series_frames(const swrt_ctx* ctx);
+int swrt_absfreq_series_bins(const swrt_ctx* ctx, int64_t* nw_out, int64_t* no_out);
+
+/* Frames [first, first + count): counts_out count x (no + 2) x (nw + 2),
+ * sums_out count x (3 (nw + 2) + 2 (no + 2)) and stats2_out count x 2,
+ * frame-major.  Each may be NULL.  Waits for the frames. */
+int swrt_absfreq_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                            int64_t* stats2_out);
+
+/* Empty the series; the edges and frac_bits stay. */
+int swrt_absfreq_series_reset(swrt_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
  * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)
  * ------------------------------------------------------------------------ */
@@ -1394,7 +1503,10 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
  *   (tools/trans_series_rate.py).  Both values give the same integers.
  * SWRT_DEBUG_REFR_GLOBAL 0 / 1 (default 0): 1 makes the refraction series'
  *   records take the global kernel for every shape
- *   (tools/refr_series_rate.py).  Both values give the same integers. */
+ *   (tools/refr_series_rate.py).  Both values give the same integers.
+ * SWRT_DEBUG_ABSFREQ_GLOBAL 0 / 1 (default 0): 1 makes the absolute-frequency
+ *   series' records take the global kernel for every shape
+ *   (tools/absfreq_series_rate.py).  Both values give the same integers. */
 #define SWRT_DEBUG_HAZARD_CHECK 1
 #define SWRT_DEBUG_SPIN_US 2
 #define SWRT_DEBUG_LEGACY_PARK 3
@@ -1416,6 +1528,7 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
 #define SWRT_DEBUG_COND_GLOBAL 20
 #define SWRT_DEBUG_TRANS_GLOBAL 21
 #define SWRT_DEBUG_REFR_GLOBAL 22
+#define SWRT_DEBUG_ABSFREQ_GLOBAL 23
 int swrt_debug_set(swrt_ctx* ctx, int key, int64_t value);
 int swrt_debug_get(swrt_ctx* ctx, int key, int64_t* value_out);
 

@@ -205,6 +205,44 @@ classdef SwrtContext < handle
             swrt_mex('refr_series_reset', obj.id());
         end
 
+        % The absolute-frequency series on the device: per frame the int64
+        % counts of the packets over omega classes (load_data.m:33-52; rows
+        % [below, bins, above] over omega_edges) by the classes over abs_edges
+        % of the absolute frequency Omega = omega + U.k
+        % (symplectic_full_fourier.m:41), per omega class the sums of
+        % round(Omega_dot * 2^frac_bits), round(Omega_dot^2 * ...) and
+        % round(U.k * ...), per Omega class the sums of round(Omega_dot * ...)
+        % and round(Omega_dot^2 * ...), and [n; rejected].  Omega_dot =
+        % k.(U_b - U_a)/tau from the snapshots in slot_a (alpha = 0) and
+        % slot_b (alpha = 1), 0-based; slot_b = -1: one snapshot, zero rates.
+        function absfreq_series_begin(obj, f, Cg, omega_edges, abs_edges, frac_bits)
+            if nargin < 6, frac_bits = 20; end
+            swrt_mex('absfreq_series_begin', obj.id(), f, Cg, omega_edges, abs_edges, frac_bits);
+        end
+
+        function absfreq_series_record(obj, slot_a, slot_b, alpha, tau, bump)
+            swrt_mex('absfreq_series_record', obj.id(), slot_a, slot_b, alpha, tau, bump);
+        end
+
+        function absfreq_series_record_history(obj, first, count, slot_a, slot_b, alphas, tau, bump)
+            % history frames first .. first+count-1, 0-based; alphas [] with one snapshot
+            swrt_mex('absfreq_series_record_history', obj.id(), first, count, slot_a, slot_b, alphas, tau, bump);
+        end
+
+        function n = absfreq_series_frames(obj)
+            n = swrt_mex('absfreq_series_frames', obj.id());
+        end
+
+        function [counts, sums, stats] = absfreq_series_get(obj)
+            % counts: int64 (nw+2) x (no+2) x frames (first index the omega class);
+            % sums: int64 (3(nw+2)+2(no+2)) x frames; stats: int64 2 x frames
+            [counts, sums, stats] = swrt_mex('absfreq_series_get', obj.id());
+        end
+
+        function absfreq_series_reset(obj)
+            swrt_mex('absfreq_series_reset', obj.id());
+        end
+
         % Packet recycling on the device: at every recycle_apply a packet
         % whose omega has reached omega_cut is absorbed and re-injected in
         % place with its home wavevector (home_k, n x 2 in the order of

@@ -82,6 +82,12 @@
 //   n = swrt_mex('refr_series_frames', h)
 //   [counts, sums, stats] = swrt_mex('refr_series_get', h)    % int64 (nw+2) x (na+2) x frames, (3(nw+2)+(na+2)) x frames, 2 x frames
 //   swrt_mex('refr_series_reset', h)
+//   swrt_mex('absfreq_series_begin', h, f, Cg, omega_edges, abs_edges[, frac_bits])   % omega classes by classes of Omega = omega + U.k; Omega-dot, Omega-dot^2, U.k sums
+//   swrt_mex('absfreq_series_record', h, slot_a, slot_b, alpha, tau, bump)   % slots 0-based; slot_b -1: one snapshot
+//   swrt_mex('absfreq_series_record_history', h, first, count, slot_a, slot_b, alphas, tau, bump)   % alphas [] when slot_b < 0
+//   n = swrt_mex('absfreq_series_frames', h)
+//   [counts, sums, stats] = swrt_mex('absfreq_series_get', h)    % int64 (nw+2) x (no+2) x frames, (3(nw+2)+2(no+2)) x frames, 2 x frames
+//   swrt_mex('absfreq_series_reset', h)
 //   swrt_mex('track_begin', h, ids)                         % trajectories of chosen packets; ids 0-based doubles
 //   swrt_mex('track_record', h, f, gH, nslots, alpha, bump)   % nslots 0: no flow, Omega..D are NaN
 //   swrt_mex('track_record_history', h, first, count, f, gH, nslots, alphas, bump)   % alphas [] when nslots < 2
@@ -732,6 +738,56 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   if (!strcmp(cmd, "refr_series_reset")) {
     check(c, swrt_refr_series_reset(c), "swrt_refr_series_reset");
+    return;
+  }
+  if (!strcmp(cmd, "absfreq_series_begin")) {  // (f, Cg, omega_edges, abs_edges[, frac_bits = 20])
+    need(na, 5, cmd);
+    const size_t ne = mxGetNumberOfElements(a[3]), noe = mxGetNumberOfElements(a[4]);
+    check(c, swrt_absfreq_series_begin(c, scalar(a[1]), scalar(a[2]), reals(a[3], "omega_edges"), (int64_t)ne - 1,
+                                       reals(a[4], "abs_edges"), (int64_t)noe - 1, na > 5 ? (int)scalar(a[5]) : 20),
+          "swrt_absfreq_series_begin");
+    return;
+  }
+  if (!strcmp(cmd, "absfreq_series_record")) {  // (slot_a, slot_b, alpha, tau, bump)
+    need(na, 6, cmd);
+    check(c, swrt_absfreq_series_record(c, (int)scalar(a[1]), (int)scalar(a[2]), scalar(a[3]), scalar(a[4]),
+                                        scalar(a[5])),
+          "swrt_absfreq_series_record");
+    return;
+  }
+  if (!strcmp(cmd, "absfreq_series_record_history")) {  // (first, count, slot_a, slot_b, alphas, tau, bump): [] alphas = none
+    need(na, 8, cmd);
+    const int64_t count = (int64_t)scalar(a[2]);
+    const size_t nal = mxGetNumberOfElements(a[5]);
+    if (nal != 0 && (int64_t)nal != count) mexErrMsgIdAndTxt("swrt:arg", "alphas must hold one value per frame");
+    check(c, swrt_absfreq_series_record_history(c, (int64_t)scalar(a[1]), count, (int)scalar(a[3]), (int)scalar(a[4]),
+                                                nal ? reals(a[5], "alphas") : nullptr, scalar(a[6]), scalar(a[7])),
+          "swrt_absfreq_series_record_history");
+    return;
+  }
+  if (!strcmp(cmd, "absfreq_series_frames")) {
+    plhs[0] = mxCreateDoubleScalar((double)swrt_absfreq_series_frames(c));
+    return;
+  }
+  if (!strcmp(cmd, "absfreq_series_get")) {  // -> counts (nw+2) x (no+2) x frames, sums (3(nw+2)+2(no+2)) x frames, stats 2 x frames
+    const int64_t nf = swrt_absfreq_series_frames(c);
+    int64_t nw = 0, nol = 0;
+    check(c, swrt_absfreq_series_bins(c, &nw, &nol), "swrt_absfreq_series_bins");
+    const mwSize dims[3] = {(mwSize)(nw + 2), (mwSize)(nol + 2), (mwSize)nf},
+                 udims[2] = {(mwSize)(3 * (nw + 2) + 2 * (nol + 2)), (mwSize)nf}, sdims[2] = {2, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(3, dims, mxINT64_CLASS, mxREAL);
+    mxArray* sums = mxCreateNumericArray(2, udims, mxINT64_CLASS, mxREAL);
+    mxArray* stats = mxCreateNumericArray(2, sdims, mxINT64_CLASS, mxREAL);
+    if (nf > 0)
+      check(c, swrt_absfreq_series_get(c, 0, nf, (int64_t*)mxGetInt64s(plhs[0]), (int64_t*)mxGetInt64s(sums),
+                                       (int64_t*)mxGetInt64s(stats)),
+            "swrt_absfreq_series_get");
+    if (nlhs > 1) plhs[1] = sums; else mxDestroyArray(sums);
+    if (nlhs > 2) plhs[2] = stats; else mxDestroyArray(stats);
+    return;
+  }
+  if (!strcmp(cmd, "absfreq_series_reset")) {
+    check(c, swrt_absfreq_series_reset(c), "swrt_absfreq_series_reset");
     return;
   }
   if (!strcmp(cmd, "recycle_begin")) {  // (f, Cg, omega_cut, L[, seed = 0, index_base = 0, frac_bits = 20, home_k = []])

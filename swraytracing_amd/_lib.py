@@ -132,6 +132,14 @@ SIGNATURES = {
     "swrt_refr_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                     ctypes.POINTER(ctypes.c_int64)]),
     "swrt_refr_series_reset": (_INT, [_VP]),
+    "swrt_absfreq_series_begin": (_INT, [_VP, _D, _D, _P, _I, _P, _I, _INT]),
+    "swrt_absfreq_series_record": (_INT, [_VP, _INT, _INT, _D, _D, _D]),
+    "swrt_absfreq_series_record_history": (_INT, [_VP, _I, _I, _INT, _INT, _P, _D, _D]),
+    "swrt_absfreq_series_frames": (_I, [_VP]),
+    "swrt_absfreq_series_bins": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_absfreq_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                       ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_absfreq_series_reset": (_INT, [_VP]),
     "swrt_recycle_begin": (_INT, [_VP, _D, _D, _D, _D, ctypes.c_uint64, _I, _INT, _P]),
     "swrt_recycle_apply": (_INT, [_VP]),
     "swrt_recycle_frames": (_I, [_VP]),
@@ -230,6 +238,7 @@ DEBUG_KMAP_GLOBAL = 19
 DEBUG_COND_GLOBAL = 20
 DEBUG_TRANS_GLOBAL = 21
 DEBUG_REFR_GLOBAL = 22
+DEBUG_ABSFREQ_GLOBAL = 23
 COND_WHICH = {"zeta": 0, "sigma": 1, "D": 2}  # swrt_cond_series_begin's ``which``
 
 _lib = None
@@ -883,6 +892,70 @@ class Context:
 
     def refr_series_reset(self):
         self._chk(self._L.swrt_refr_series_reset(self._h), "swrt_refr_series_reset")
+
+    # ---- the absolute-frequency series (swrt_absfreq_series_*: Omega = omega + U.k and k.dU/dt per class) ----
+    def absfreq_series_begin(self, f, Cg, omega_edges, abs_edges, frac_bits=20):
+        """Open a series of (no + 2) x (nw + 2) count planes: omega classes
+        over ``omega_edges`` (nw + 1 increasing values) by the classes of the
+        absolute frequency Omega = omega + U.k over ``abs_edges`` (no + 1
+        increasing values); the per-class sums of dOmega/dt, its square and
+        the Doppler shift U.k quantised to 2^-frac_bits.  Empties the
+        series."""
+        wedges = _f64(np.asarray(omega_edges, dtype=np.float64).ravel())
+        oedges = _f64(np.asarray(abs_edges, dtype=np.float64).ravel())
+        self._chk(self._L.swrt_absfreq_series_begin(self._h, float(f), float(Cg), _p(wedges), wedges.size - 1,
+                                                    _p(oedges), oedges.size - 1, int(frac_bits)),
+                  "swrt_absfreq_series_begin")
+
+    def absfreq_series_record(self, slot_a=0, slot_b=-1, alpha=0.0, tau=1.0, bump=1e-13):
+        """Append the current packets' frame in the flow of ``slot_a``
+        (alpha = 0) and ``slot_b`` (alpha = 1) blended at ``alpha``, the two
+        snapshots ``tau`` apart; ``slot_b`` -1: one snapshot, zero rates
+        (queued; no host wait)."""
+        self._chk(self._L.swrt_absfreq_series_record(self._h, int(slot_a), int(slot_b), float(alpha), float(tau),
+                                                     float(bump)), "swrt_absfreq_series_record")
+
+    def absfreq_series_record_history(self, first, count, slot_a=0, slot_b=-1, alphas=None, tau=1.0, bump=1e-13):
+        """One frame per history frame [first, first + count), frame i with
+        the snapshot blend ``alphas[i]`` (None with one snapshot)."""
+        if alphas is not None:
+            alphas = np.ascontiguousarray(alphas, dtype=np.float64)
+            if alphas.shape != (int(count),):
+                raise ValueError("alphas must hold one value per frame")
+        self._chk(self._L.swrt_absfreq_series_record_history(self._h, int(first), int(count), int(slot_a), int(slot_b),
+                                                             _p(alphas), float(tau), float(bump)),
+                  "swrt_absfreq_series_record_history")
+
+    def absfreq_series_frames(self):
+        return int(self._L.swrt_absfreq_series_frames(self._h))
+
+    def absfreq_series_bins(self):
+        """(nw, no) of the open series, (0, 0) if none."""
+        nw, no = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self._L.swrt_absfreq_series_bins(self._h, ctypes.byref(nw), ctypes.byref(no)),
+                  "swrt_absfreq_series_bins")
+        return int(nw.value), int(no.value)
+
+    def absfreq_series_get(self, first=0, count=None):
+        """Recorded frames [first, first + count) -> (counts (count, no + 2,
+        nw + 2) int64, counts[t, oc, wc]; sums (count, 3 (nw + 2) + 2 (no + 2))
+        int64: per omega class the sums of rint(Omega-dot * 2^frac_bits),
+        rint(Omega-dot^2 * ...) and rint(U.k * ...), then per Omega class the
+        sums of rint(Omega-dot * ...) and rint(Omega-dot^2 * ...); stats
+        (count, 2) int64 [n, rejected])."""
+        count = self.absfreq_series_frames() - first if count is None else count
+        nw, no = self.absfreq_series_bins()
+        counts = np.zeros((max(count, 0), no + 2, nw + 2), dtype=np.int64)
+        sums = np.zeros((max(count, 0), 3 * (nw + 2) + 2 * (no + 2)), dtype=np.int64)
+        stats = np.zeros((max(count, 0), 2), dtype=np.int64)
+        i64 = ctypes.POINTER(ctypes.c_int64)
+        self._chk(self._L.swrt_absfreq_series_get(self._h, int(first), int(count), counts.ctypes.data_as(i64),
+                                                  sums.ctypes.data_as(i64), stats.ctypes.data_as(i64)),
+                  "swrt_absfreq_series_get")
+        return counts, sums, stats
+
+    def absfreq_series_reset(self):
+        self._chk(self._L.swrt_absfreq_series_reset(self._h), "swrt_absfreq_series_reset")
 
     # ---- packet recycling (swrt_recycle_*: absorb at an omega cut, re-inject at home) ----
     def recycle_begin(self, f, Cg, omega_cut, L, seed=0, index_base=0, frac_bits=20, home_k=None):

@@ -438,6 +438,7 @@ int swrt_packets_set(swrt_ctx* c, const double* x, const double* k, int64_t n) {
   if (!c->bins.buf) HIPCHK(c, c->bins.alloc());
   if (n != c->n) c->rd.drop();  // Omega_0 and the frame series belong to an ensemble of the old size
   if (n != c->n) c->trk.drop();  // (the tracked ids too)
+  if (n != c->n) c->absfreq.drop();  // (the absolute-frequency frames too)
   c->trans.drop();  // the transition series' mark belongs to the packet set it was taken on
   c->recycle.drop();  // (home, gen and born too)
   c->n = n;
@@ -1998,6 +1999,101 @@ int swrt_refr_series_reset(swrt_ctx* c) {
   return SWRT_OK;
 }
 
+// ---- the absolute-frequency series (swrt_absfreq.hpp, swrt_host_diag.hpp) ----
+int swrt_absfreq_series_begin(swrt_ctx* c, double f, double Cg, const double* omega_edges, int64_t nw,
+                              const double* abs_edges, int64_t no, int frac_bits) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(omega_edges_check(c, omega_edges, nw));
+  HIPCHK_RC(omega_edges_check(c, abs_edges, no));
+  if ((no + 2) * (nw + 2) > kAbsfreqMaxCells) return fail(c, SWRT_ERR_ARG, "(no + 2) * (nw + 2) must be at most 65536");
+  if (frac_bits < 0 || frac_bits > kAbsfreqMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
+  HIPCHK(c, hipSetDevice(c->device));
+  AbsfreqSeriesState& as = c->absfreq;
+  HIPCHK_RC(series_release(c, as.series));  // (waits: queued records read the old edges too)
+  as.open = false;
+  HIPCHK(c, as.edges.alloc(nw + no + 2));
+  HIPCHK(c, hipMemcpyAsync(as.edges.get(), omega_edges, sizeof(double) * (nw + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(as.edges.get() + nw + 1, abs_edges, sizeof(double) * (no + 1), hipMemcpyHostToDevice,
+                           c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  as.nw = (int)nw;
+  as.no = (int)no;
+  as.frac_bits = frac_bits;
+  as.f2 = f * f;
+  as.Cg2 = Cg * Cg;
+  as.open = true;
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_absfreq_series_record(swrt_ctx* c, int slot_a, int slot_b, double alpha, double tau, double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c, false, absfreq_slot_mask(slot_a, slot_b));
+  HIPCHK_RC(absfreq_series_check(c, slot_a, slot_b, tau));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(absfreq_reserve_zeroed(c, 1));
+  return absfreq_launch(c, slot_a, slot_b, alpha, nullptr, tau, bump, c->pk.cur.x.get(), c->pk.cur.k.get(), 0, 1);
+  GUARD_END(c)
+}
+
+int swrt_absfreq_series_record_history(swrt_ctx* c, int64_t first, int64_t count, int slot_a, int slot_b,
+                                       const double* alphas, double tau, double bump) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  SlotUse slot_use(c, false, absfreq_slot_mask(slot_a, slot_b));
+  HIPCHK_RC(absfreq_series_check(c, slot_a, slot_b, tau));
+  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
+  if (slot_b >= 0 && !alphas && count > 0) return fail(c, SWRT_ERR_ARG, "NULL buffer (alphas, two snapshots)");
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  AbsfreqSeriesState& as = c->absfreq;
+  const double* dalphas = nullptr;
+  if (slot_b >= 0) {  // the frames' alphas to the device; the caller's buffer is free on return
+    if (count > as.acap) {  // (releasing the old buffer waits for queued readers)
+      as.acap = 0;
+      HIPCHK(c, as.alphas.alloc(count));
+      as.acap = count;
+    }
+    HIPCHK(c, hipMemcpyAsync(as.alphas.get(), alphas, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    dalphas = as.alphas.get();
+  }
+  HIPCHK_RC(absfreq_reserve_zeroed(c, count));
+  for (int64_t i = 0; i < count; i += kAbsfreqHistoryChunk) {
+    const int64_t nf = std::min<int64_t>(kAbsfreqHistoryChunk, count - i), off = (first + i) * 2 * c->n;
+    HIPCHK_RC(absfreq_launch(c, slot_a, slot_b, 0.0, dalphas ? dalphas + i : nullptr, tau, bump,
+                             c->hist.a.get() + off, c->hist.b.get() + off, 2 * c->n, nf));
+  }
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int64_t swrt_absfreq_series_frames(const swrt_ctx* c) { return c ? c->absfreq.series.ext.frames() : -1; }
+
+int swrt_absfreq_series_bins(const swrt_ctx* c, int64_t* nw_out, int64_t* no_out) {
+  if (!c) return SWRT_ERR_ARG;
+  if (nw_out) *nw_out = c->absfreq.open ? c->absfreq.nw : 0;
+  if (no_out) *no_out = c->absfreq.open ? c->absfreq.no : 0;
+  return SWRT_OK;
+}
+
+int swrt_absfreq_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                            int64_t* stats2_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  return absfreq_series_get(c, first, count, counts_out, sums_out, stats2_out);
+  GUARD_END(c)
+}
+
+int swrt_absfreq_series_reset(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
+  c->absfreq.series.ext.cleared();
+  return SWRT_OK;
+}
+
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
@@ -2081,6 +2177,10 @@ int swrt_debug_set(swrt_ctx* c, int key, int64_t value) {
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "refraction series path must be 0 or 1");
       c->dbg.refr_global = value != 0;
       return SWRT_OK;
+    case SWRT_DEBUG_ABSFREQ_GLOBAL:
+      if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "absolute-frequency series path must be 0 or 1");
+      c->dbg.absfreq_global = value != 0;
+      return SWRT_OK;
     case SWRT_DEBUG_QG_UPDATE_COLS:
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "QG update/column-pass fusion must be 0 or 1");
       if (c->qg.spec) return fail(c, SWRT_ERR_STATE, "a speculative QG step is pending (swrt_qg_resolve first)");
@@ -2122,6 +2222,7 @@ int swrt_debug_get(swrt_ctx* c, int key, int64_t* value_out) {
     case SWRT_DEBUG_COND_GLOBAL: *value_out = c->dbg.cond_global ? 1 : 0; return SWRT_OK;
     case SWRT_DEBUG_TRANS_GLOBAL: *value_out = c->dbg.trans_global ? 1 : 0; return SWRT_OK;
     case SWRT_DEBUG_REFR_GLOBAL: *value_out = c->dbg.refr_global ? 1 : 0; return SWRT_OK;
+    case SWRT_DEBUG_ABSFREQ_GLOBAL: *value_out = c->dbg.absfreq_global ? 1 : 0; return SWRT_OK;
     case SWRT_DEBUG_MAP_STRAYS: {  // the device's counter: waits for the queued records
       unsigned long long v = 0;
       if (c->map.strays) {

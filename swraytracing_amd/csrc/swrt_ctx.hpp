@@ -461,6 +461,26 @@ struct RefrSeriesState {
   size_t tail() const { return nsums() + 2; }
 };
 
+// the absolute-frequency series (swrt_absfreq_series_*, swrt_absfreq.hpp).
+// Buffers of its own, laid out as the refraction series'; swrt_packets_set
+// with another N drops the frames (drop()), the edges stay.
+struct AbsfreqSeriesState {
+  bool open = false;        // swrt_absfreq_series_begin was called
+  int nw = 0, no = 0;       // omega and Omega bins of the open series
+  int frac_bits = 0;
+  double f2 = 0.0, Cg2 = 0.0;
+  DevBuf<double> edges;     // nw + 1 omega edges, then no + 1 Omega edges
+  DevBuf<double> alphas;    // record_history's alphas, one per frame of the call
+  int64_t acap = 0;         // frames alphas is sized for
+  bool lds_attr = false;    // the kernels' dynamic LDS limit was raised
+  // recorded frames: (no + 2) x (nw + 2) counts each, and their 3 (nw + 2) + 2 (no + 2) sums followed by [n, rejected]
+  Series<unsigned long long> series;
+  size_t frame() const { return (size_t)(no + 2) * (nw + 2); }
+  size_t nsums() const { return (size_t)3 * (nw + 2) + (size_t)2 * (no + 2); }
+  size_t tail() const { return nsums() + 2; }
+  void drop() { series.ext.cleared(); }  // the ensemble changed size: the frames describe another one
+};
+
 // packet recycling (swrt_recycle_*, swrt_recycle.hpp).  The per-packet state
 // (home, gen, born, by original index) belongs to the packet set:
 // swrt_packets_set drops it (live), the recorded frames stay readable until
@@ -496,6 +516,7 @@ struct DebugKnobs {
   bool cond_global = false; // SWRT_DEBUG_COND_GLOBAL: the conditional spectrum series' global kernel for every shape
   bool trans_global = false; // SWRT_DEBUG_TRANS_GLOBAL: the transition series' global kernel for every shape
   bool refr_global = false; // SWRT_DEBUG_REFR_GLOBAL: the refraction series' global kernel for every shape
+  bool absfreq_global = false; // SWRT_DEBUG_ABSFREQ_GLOBAL: the absolute-frequency series' global kernel for every shape
 };
 }  // namespace
 
@@ -568,6 +589,7 @@ struct swrt_ctx {
   CondSeriesState cond;
   TransSeriesState trans;
   RefrSeriesState refr;
+  AbsfreqSeriesState absfreq;
   RecycleState recycle;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an

@@ -1,16 +1,17 @@
-// swrt_host_diag.hpp — host side of the nine device-side recorders and of
+// swrt_host_diag.hpp — host side of the ten device-side recorders and of
 // the packet recycling (swrt_recycle.hpp): the ray
 // diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp), the
 // map series (swrt_map.hpp), the wave-vector plane series (swrt_kmap.hpp),
 // the track series (swrt_track.hpp), the flow spectrum series
 // (swrt_flowspec.hpp), the conditional spectrum series (swrt_cond.hpp), the
-// transition series (swrt_trans.hpp) and the refraction series
-// (swrt_refr.hpp, last below).
+// transition series (swrt_trans.hpp), the refraction series (swrt_refr.hpp)
+// and the absolute-frequency series (swrt_absfreq.hpp, last below).
 // Each appends frames to a Series of its
 // state (swrt_ctx.hpp) without a host wait: a reserve, the launches that write
 // at the series' end, a commit.  The order below (ray, spectrum, map, k-plane,
-// track, flow, conditional, transition, recycling, refraction) is the order their
-// template kernels are first named in, hence emitted in.
+// track, flow, conditional, transition, recycling, refraction, absolute
+// frequency) is the order their template kernels are first named in, hence
+// emitted in.
 #pragma once
 #include <cmath>
 
@@ -27,6 +28,7 @@
 #include "swrt_trans.hpp"
 #include "swrt_recycle.hpp"
 #include "swrt_refr.hpp"
+#include "swrt_absfreq.hpp"
 
 namespace {
 
@@ -729,6 +731,123 @@ int refr_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_o
     const int64_t* row = tails.data() + tl * t;
     if (sums_out) std::copy(row, row + nsum, sums_out + nsum * t);
     if (stats_out) std::copy(row + nsum, row + tl, stats_out + (size_t)kRefrStats * t);
+  }
+  return dev_err_check(c);
+}
+
+// ---- the absolute-frequency series ----
+// The records' common checks: an open series, then swrt_raydiag_record's on
+// the two slots the call names (slot_b < 0: one snapshot, alpha and tau unused).
+int absfreq_series_check(swrt_ctx* c, int slot_a, int slot_b, double tau) {
+  if (!c->absfreq.open) return fail(c, SWRT_ERR_STATE, "call swrt_absfreq_series_begin first");
+  HIPCHK_RC(lost_check(c));
+  if (slot_a < 0 || slot_a >= SWRT_MAX_SLOTS || slot_b < -1 || slot_b >= SWRT_MAX_SLOTS)
+    return fail(c, SWRT_ERR_ARG, "slot out of range");
+  if (slot_a == slot_b) return fail(c, SWRT_ERR_ARG, "slot_a and slot_b must differ");
+  if (!c->slot[slot_a].set || (slot_b >= 0 && !c->slot[slot_b].set)) return fail(c, SWRT_ERR_ARG, "field slot not set");
+  if (slot_b >= 0) {
+    const Slot &sa = c->slot[slot_a], &sb = c->slot[slot_b];
+    if (sb.nx != sa.nx || sb.L != sa.L || sb.ny_period != sa.ny_period)
+      return fail(c, SWRT_ERR_ARG, "slots a and b have different grids");
+    if (!std::isfinite(tau) || tau == 0.0) return fail(c, SWRT_ERR_ARG, "tau must be finite and non-zero");
+  }
+  HIPCHK_RC(packets_check(c));
+  if (c->n > kAbsfreqMaxPackets)
+    return fail(c, SWRT_ERR_ARG, "an absolute-frequency frame takes at most 2^24 packets");
+  return SWRT_OK;
+}
+
+// The slots a record reads, for SlotUse (out-of-range arguments: none; the
+// check refuses them before anything is queued).
+inline unsigned absfreq_slot_mask(int slot_a, int slot_b) {
+  unsigned m = 0u;
+  if (slot_a >= 0 && slot_a < SWRT_MAX_SLOTS) m |= 1u << slot_a;
+  if (slot_b >= 0 && slot_b < SWRT_MAX_SLOTS) m |= 1u << slot_b;
+  return m;
+}
+
+// Room for `count` more frames, zeroed on the stream (counts, sums and
+// stats): the launches that fill them only add.
+int absfreq_reserve_zeroed(swrt_ctx* c, int64_t count) {
+  AbsfreqSeriesState& as = c->absfreq;
+  const size_t fr = as.frame(), tl = as.tail();
+  HIPCHK_RC(series_reserve(c, as.series, fr, tl, count, map_series_min(fr * sizeof(unsigned long long))));
+  HIPCHK(c, hipMemsetAsync(as.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
+  HIPCHK(c, hipMemsetAsync(as.series.end_b(tl), 0, sizeof(unsigned long long) * tl * count, c->stream));
+  return SWRT_OK;
+}
+
+// `count` frames from the series' end on: frame i from the packets at
+// x + i*stride, k + i*stride (any order) and the flow of slots a and b at
+// alphas[i] (device; NULL: `alpha` for every frame).  The LDS kernel for
+// absfreq_lds_form's shapes, the global one beyond (or when
+// SWRT_DEBUG_ABSFREQ_GLOBAL says so).
+int absfreq_launch(swrt_ctx* c, int slot_a, int slot_b, double alpha, const double* alphas, double tau, double bump,
+                   const double* x, const double* k, int64_t stride, int64_t count) {
+  AbsfreqSeriesState& as = c->absfreq;
+  AbsfreqArgs a;
+  a.fa = view_of(c->slot[slot_a]);
+  a.fb = slot_b >= 0 ? view_of(c->slot[slot_b]) : a.fa;
+  a.two = slot_b >= 0 ? 1 : 0;
+  a.alpha = alpha;
+  a.tau = slot_b >= 0 ? tau : 1.0;
+  a.bump = bump;
+  a.alphas = alphas;
+  a.x = x;
+  a.k = k;
+  a.stride = stride;
+  a.n = c->n;
+  a.f2 = as.f2;
+  a.Cg2 = as.Cg2;
+  a.wedges = as.edges.get();
+  a.oedges = as.edges.get() + as.nw + 1;
+  a.nw = as.nw;
+  a.no = as.no;
+  a.scale = std::ldexp(1.0, as.frac_bits);
+  a.counts = as.series.end_a(as.frame());
+  a.tail = as.series.end_b(as.tail());
+  const bool lds = !c->dbg.absfreq_global && absfreq_lds_form(as.nw, as.no);
+  const size_t bytes = absfreq_lds_bytes(as.nw, as.no, lds);
+  if (bytes > ((size_t)64 << 10) && !as.lds_attr) {  // (above 64 KB of dynamic LDS a kernel has to ask once)
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&absfreq_kernel<true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kAbsfreqMaxLdsBytes));
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&absfreq_kernel<false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kAbsfreqMaxLdsBytes));
+    as.lds_attr = true;
+  }
+  const int most = bytes > kAbsfreqLdsFormBytes ? kAbsfreqHugeTailBlocks
+                   : bytes > kAbsfreqBigPlaneBytes ? kAbsfreqBigPlaneBlocks : kAbsfreqBlocks;
+  const int nblk = (int)std::min<int64_t>(most, nblocks(c->n, kAbsfreqThreads));
+  hipLaunchKernelGGL(lds ? absfreq_kernel<true> : absfreq_kernel<false>, dim3(nblk, (unsigned)count),
+                     dim3(kAbsfreqThreads), bytes, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  as.series.ext.committed(count);
+  return SWRT_OK;
+}
+
+// Frames [first, first + count) to the host, synchronously; every output may
+// be NULL.  The sums and the stats share the series' second column.
+int absfreq_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                       int64_t* stats_out) {
+  const AbsfreqSeriesState& as = c->absfreq;
+  HIPCHK_RC(frame_range_check(c, as.series.ext, first, count, "frame range out of bounds"));
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t fr = as.frame(), tl = as.tail(), nsum = as.nsums();
+  std::vector<int64_t> tails;
+  if (counts_out)
+    HIPCHK(c, hipMemcpyAsync(counts_out, as.series.a.get() + fr * first, sizeof(int64_t) * fr * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  if (sums_out || stats_out) {
+    tails.resize(tl * count);
+    HIPCHK(c, hipMemcpyAsync(tails.data(), as.series.b.get() + tl * first, sizeof(int64_t) * tl * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int64_t t = 0; t < count && !tails.empty(); ++t) {
+    const int64_t* row = tails.data() + tl * t;
+    if (sums_out) std::copy(row, row + nsum, sums_out + nsum * t);
+    if (stats_out) std::copy(row + nsum, row + tl, stats_out + (size_t)kAbsfreqStats * t);
   }
   return dev_err_check(c);
 }

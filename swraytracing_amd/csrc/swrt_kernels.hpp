@@ -498,6 +498,18 @@ __device__ __forceinline__ void eval_flow_t(const FieldView& f0, const FieldView
   }
 }
 
+// Both snapshots' records at (x, y), unblended: A from fa and, with TWO, B
+// from fb on fa's stencil (one grid, checked on the host) — the sums
+// eval_flow_t blends, for callers that also want their difference
+// (swrt_absfreq.hpp).  Without TWO, B is -0.0.
+template <bool TWO>
+__device__ __forceinline__ void flow_pair(const FieldView& fa, const FieldView& fb, double x, double y,
+                                          double bump, double A[kRec], double B[kRec]) {
+  Stencil s;
+  stencil_at(fa, x, y, bump, s);
+  gather6<TWO>(fa.nodes, fb.nodes, fa.npad, s, A, B);
+}
+
 __device__ __forceinline__ void eval_flow(const FieldView& f0, const FieldView& f1, int nslots,
                                           double alpha, double x, double y, double bump,
                                           double I[kRec]) {

@@ -275,6 +275,69 @@ def refr_rates(counts, sums, frac_bits):
                 n_align=n_a, omega_dot_mean_align=wd_a, flux_share=share)
 
 
+def combine_absfreqs(parts):
+    """The absolute-frequency series of an ensemble from its shards' series
+    (swrt_absfreq_series_*).  ``parts``: a sequence of (counts, sums, stats)
+    triples, one per shard, counts (T, no + 2, nw + 2) int64, sums
+    (T, 3 (nw + 2) + 2 (no + 2)) int64 and stats (T, 2) int64 [n, rejected]:
+    the element-wise sum (integer, exact and order-free).  A shard without
+    packets stands as zeros."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("no series to combine")
+    shapes = {tuple(np.shape(a) for a in p) for p in parts}
+    if len(shapes) != 1:
+        raise ValueError("every shard must give counts, sums and stats of the same shapes")
+    counts = np.stack([np.asarray(p[0], dtype=np.int64) for p in parts])
+    sums = np.stack([np.asarray(p[1], dtype=np.int64) for p in parts])
+    stats = np.stack([np.asarray(p[2], dtype=np.int64) for p in parts])
+    if counts.ndim != 4 or sums.shape != counts.shape[:2] + (3 * counts.shape[3] + 2 * counts.shape[2],) \
+            or stats.shape != counts.shape[:2] + (2,):
+        raise ValueError("every shard must give counts (T, no + 2, nw + 2), sums (T, 3 (nw + 2) + 2 (no + 2)) "
+                         "and stats (T, 2)")
+    return counts.sum(axis=0), sums.sum(axis=0), stats.sum(axis=0)
+
+
+def absfreq_rates(counts, sums, stats, frac_bits):
+    """Rates of absolute-frequency frames counts (..., no + 2, nw + 2), sums
+    (..., 3 (nw + 2) + 2 (no + 2)) and stats (..., 2) int64, as fp64.  Per
+    omega class: ``n`` (..., nw + 2) its packets (the frame's omega spectrum),
+    ``abs_dot_mean``, ``abs_dot_sq_mean`` and ``doppler_mean`` (..., nw + 2) the
+    means of dOmega/dt = k.dU/dt, of its square and of the Doppler shift U.k
+    (each exact to the quantum 2^-frac_bits).  Per Omega class: ``n_abs``
+    (..., no + 2) its packets (the frame's Omega spectrum),
+    ``abs_dot_mean_abs`` and ``abs_dot_sq_mean_abs`` (..., no + 2).
+    ``accepted`` (...) is n - rejected of the frame, the sum of either
+    spectrum.  The means are NaN where the class is empty."""
+    counts = np.asarray(counts)
+    sums = np.asarray(sums)
+    stats = np.asarray(stats)
+    if counts.ndim < 2:
+        raise ValueError("counts must be (..., no + 2, nw + 2)")
+    nos, nws = counts.shape[-2:]
+    if sums.shape != counts.shape[:-2] + (3 * nws + 2 * nos,) or stats.shape != counts.shape[:-2] + (2,):
+        raise ValueError("counts must be (..., no + 2, nw + 2), sums (..., 3 (nw + 2) + 2 (no + 2)) and stats (..., 2)")
+    if not 0 <= int(frac_bits) <= 32:
+        raise ValueError("frac_bits must be 0..32")
+    unit = 2.0 ** -int(frac_bits)
+    n = counts.sum(axis=-2).astype(np.float64)
+    empty = n == 0
+    count = np.where(empty, 1.0, n)
+    od, od2, dop = (sums[..., j * nws:(j + 1) * nws].astype(np.float64) * unit / count for j in range(3))
+    for a in (od, od2, dop):
+        a[empty] = np.nan
+    n_o = counts.sum(axis=-1).astype(np.float64)
+    empty_o = n_o == 0
+    count_o = np.where(empty_o, 1.0, n_o)
+    od_o, od2_o = (sums[..., 3 * nws + j * nos:3 * nws + (j + 1) * nos].astype(np.float64) * unit / count_o
+                   for j in range(2))
+    for a in (od_o, od2_o):
+        a[empty_o] = np.nan
+    accepted = (stats[..., 0] - stats[..., 1]).astype(np.float64)
+    return dict(n=n, abs_dot_mean=od, abs_dot_sq_mean=od2, doppler_mean=dop, n_abs=n_o, abs_dot_mean_abs=od_o,
+                abs_dot_sq_mean_abs=od2_o, accepted=accepted)
+
+
 def combine_transitions(parts):
     """The transition series of an ensemble from its shards' series
     (swrt_trans_series_*).  ``parts``: a sequence of (counts, sums, stats)
@@ -1359,6 +1422,134 @@ class PacketEnsemble:
             with open(os.path.join(directory, "refr_geom.bin"), "wb") as fh:
                 head = np.array([st["aedges"].size - 1, st["wedges"].size - 1, st["frac_bits"]], dtype=np.float64)
                 fh.write(np.concatenate([head, st["aedges"], st["wedges"]]).tobytes())
+        return st["frames"]
+
+    def begin_absfreq(self, omega_edges, abs_edges, frac_bits=20, directory=None):
+        """Open the absolute-frequency series of this run
+        (swrt_absfreq_series_begin with the ensemble's f, Cg): omega classes
+        over ``omega_edges`` by the classes of Omega = omega + U.k over
+        ``abs_edges``.  ``directory``: where record_absfreq drains the device
+        series when it grows large (default: the drained frames wait in host
+        memory for write_absfreqs)."""
+        wedges = np.array(omega_edges, dtype=np.float64).ravel()
+        oedges = np.array(abs_edges, dtype=np.float64).ravel()
+        for name, e in (("omega", wedges), ("absolute-frequency", oedges)):
+            if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+                raise ValueError(f"the {name} edges must be at least two finite increasing values")
+        frac_bits = int(frac_bits)
+        if not 0 <= frac_bits <= 32:
+            raise ValueError("absolute-frequency series frac_bits must be 0..32")
+        if (oedges.size + 1) * (wedges.size + 1) > 65536:
+            raise ValueError("an absolute-frequency frame holds at most 65536 cells, (no + 2) * (nw + 2)")
+        self._absfreq = dict(wedges=wedges, oedges=oedges, frac_bits=frac_bits, directory=directory, frames=0,
+                             pending=0, kept=[])
+        if self.n > 0:
+            self.ctx.absfreq_series_begin(self.f, self.Cg, wedges, oedges, frac_bits)
+
+    def record_absfreq(self, slot_a=0, slot_b=-1, alpha=0.0, tau=1.0):
+        """Append this shard's absolute-frequency frame at the current state
+        to the device-side series (queued, no host wait): the flow of
+        ``slot_a`` (alpha = 0) and ``slot_b`` (alpha = 1) blended at ``alpha``,
+        its rate (slot_b - slot_a) / ``tau``; ``slot_b`` -1: slot_a alone, zero
+        rates.  An empty shard records nothing.  When the device series holds
+        more than 256 MB it is drained (get, combine, append, reset): a
+        collective when sharded, at the same frame on every rank."""
+        st = getattr(self, "_absfreq", None)
+        if st is None:
+            raise SwrtError("record_absfreq: call begin_absfreq first")
+        st["frames"] += 1
+        st["pending"] += 1
+        if self.n > 0:
+            self.ctx.absfreq_series_record(slot_a, slot_b, alpha, tau, bump=self.bump)
+        nos, nws = st["oedges"].size + 1, st["wedges"].size + 1
+        if st["pending"] * 8 * (nos * nws + 3 * nws + 2 * nos + 2) > MAP_DRAIN_BYTES:
+            self._drain_absfreqs()
+
+    def _drain_absfreqs(self):
+        """The frames on the device, summed over the shards, to the files or
+        the host list of rank 0; the device series emptied."""
+        st = self._absfreq
+        T, nos, nws = st["pending"], st["oedges"].size + 1, st["wedges"].size + 1
+        if T == 0:
+            return
+        if self.n > 0:
+            part = self.ctx.absfreq_series_get(0, T)
+            self.ctx.absfreq_series_reset()
+        else:
+            part = (np.zeros((T, nos, nws), dtype=np.int64), np.zeros((T, 3 * nws + 2 * nos), dtype=np.int64),
+                    np.zeros((T, 2), dtype=np.int64))
+        st["pending"] = 0
+        if self.world > 1:
+            import torch
+            import torch.distributed as dist
+
+            from .dist import _device_for
+            dev = _device_for(dist.get_backend())
+            gathered = []
+            for a in part:
+                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                out = [torch.empty_like(buf) for _ in range(self.world)]
+                dist.all_gather(out, buf)
+                gathered.append([o.cpu().numpy() for o in out])
+            if self.rank != 0:
+                return
+            part = combine_absfreqs(zip(*gathered))
+        if st["directory"] is None:
+            st["kept"].append(part)
+        else:
+            self._append_absfreqs(st["directory"], *part)
+
+    @staticmethod
+    def _append_absfreqs(directory, counts, sums, stats):
+        with open(os.path.join(directory, "absfreq_hist.bin"), "ab") as fc, \
+                open(os.path.join(directory, "absfreq_sums.bin"), "ab") as fs, \
+                open(os.path.join(directory, "absfreq_stats.bin"), "ab") as ft:
+            for fr, s, t in zip(counts, sums, stats):
+                fc.write(np.ascontiguousarray(fr, dtype=np.int64).tobytes())  # (cell (oc, wc) at oc*(nw + 2) + wc)
+                fs.write(np.ascontiguousarray(s, dtype=np.int64).tobytes())
+                ft.write(np.ascontiguousarray(t, dtype=np.int64).tobytes())
+
+    def absfreq_series(self):
+        """(counts (T, no + 2, nw + 2), sums (T, 3 (nw + 2) + 2 (no + 2)),
+        stats (T, 2)), all int64, of the ensemble's frames still held (not yet
+        drained into files).  Sharded: a collective; rank 0 gets
+        combine_absfreqs() of the shards' frames, the others None."""
+        st = getattr(self, "_absfreq", None)
+        if st is None:
+            raise SwrtError("absfreq_series: call begin_absfreq first")
+        if st["directory"] is not None:
+            raise ValueError("absfreq_series: begin_absfreq drains into a directory (read its files)")
+        self._drain_absfreqs()
+        if self.rank != 0:
+            return None
+        nos, nws = st["oedges"].size + 1, st["wedges"].size + 1
+        if not st["kept"]:
+            return (np.zeros((0, nos, nws), dtype=np.int64), np.zeros((0, 3 * nws + 2 * nos), dtype=np.int64),
+                    np.zeros((0, 2), dtype=np.int64))
+        return tuple(np.concatenate([p[i] for p in st["kept"]]) for i in range(3))
+
+    def write_absfreqs(self, directory):
+        """The run's absolute-frequency series as raw native-endian files:
+        absfreq_hist.bin (int64, one (no + 2) x (nw + 2) plane per frame, cell
+        (oc, wc) at oc*(nw + 2) + wc), absfreq_sums.bin (3 (nw + 2) +
+        2 (no + 2) int64 per frame), absfreq_stats.bin (2 int64 per frame: n,
+        rejected) and absfreq_geom.bin (doubles [no, nw, frac_bits], the
+        no + 1 Omega edges, the nw + 1 omega edges).  Sharded: a collective;
+        rank 0 writes.  Returns the frames recorded."""
+        st = getattr(self, "_absfreq", None)
+        if st is None:
+            raise SwrtError("write_absfreqs: call begin_absfreq first")
+        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
+            raise ValueError("write_absfreqs: begin_absfreq drained into another directory")
+        self._drain_absfreqs()
+        if self.rank == 0:
+            if st["directory"] is None:
+                for part in st["kept"]:
+                    self._append_absfreqs(directory, *part)
+                st["kept"] = []
+            with open(os.path.join(directory, "absfreq_geom.bin"), "wb") as fh:
+                head = np.array([st["oedges"].size - 1, st["wedges"].size - 1, st["frac_bits"]], dtype=np.float64)
+                fh.write(np.concatenate([head, st["oedges"], st["wedges"]]).tobytes())
         return st["frames"]
 
     def begin_trans(self, omega_edges, src_edges, frac_bits=20, by=0, directory=None):

@@ -289,6 +289,9 @@ class _IntervalGroup:
         # ode23 (the reference's own packet integrator) takes one interval per call
         self.k = 1 if integrator == "ode23" else max(1, min(int(k), 4))
         self.dts = []
+        # (slot_a, slot_b, dt) of the last completed interval after the last
+        # flush's swap: the slots that hold its start and its end snapshot
+        self.last = None
         # ode23 controller totals over the calls (steps, failed, attempts)
         self.ode23_stats = {"steps": 0, "failed": 0, "attempts": 0, "intervals": 0}
 
@@ -316,7 +319,12 @@ class _IntervalGroup:
                 self.ens.advance_intervals(self.dts, self.nsub)
                 if hook is not None:
                     hook()
-            self.ctx.swap_slots(0, len(self.dts))  # the last end snapshot starts the next group
+            g = len(self.dts)
+            self.ctx.swap_slots(0, g)  # the last end snapshot starts the next group
+            # the last interval ran from snapshot g - 1 to snapshot g: the swap
+            # put snapshot g into slot 0 and the group's start into slot g, so
+            # snapshot g - 1 sits in slot g - 1, or (g = 1: it is the start) in slot 1
+            self.last = (g - 1 if g >= 2 else g, 0, self.dts[-1])
             self.dts = []
 
 
@@ -342,7 +350,7 @@ def _fresh_outputs(out_dir, fresh):
                  "track_ids", "kmap_n", "kmap_stats", "kmap_geom", "flow_spec", "flow_stats", "flow_geom", "cond_hist",
                  "cond_sums", "cond_stats", "cond_geom", "trans_hist", "trans_sums", "trans_stats", "trans_time",
                  "trans_geom", "recycle_stats", "recycle_time", "recycle_geom", "recycle_gen", "refr_hist", "refr_sums",
-                 "refr_stats", "refr_geom"):
+                 "refr_stats", "refr_geom", "absfreq_hist", "absfreq_sums", "absfreq_stats", "absfreq_geom"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
@@ -440,6 +448,31 @@ def _refr_args(refr_edges, refr_frac_bits, spectrum_edges):
     if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
         raise ValueError("refr_edges: at most 4096 classes and (na + 2) * (nbins + 2) <= 65536 cells a frame")
     return edges, int(refr_frac_bits)
+
+
+def _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges):
+    """The drivers' ``absfreq_edges`` / ``absfreq_frac_bits`` checked before
+    anything runs: (Omega edges, frac_bits), or None without ``absfreq_edges``.
+    The omega classes are the run's ``spectrum_edges``."""
+    if absfreq_edges is None:
+        return None
+    if spectrum_edges is None:
+        raise ValueError("absfreq_edges needs spectrum_edges: they are the absolute-frequency series' omega classes")
+    edges = np.array(absfreq_edges, dtype=np.float64).ravel()
+    if edges.size < 2 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
+        raise ValueError("absfreq_edges must be at least two finite increasing values")
+    if isinstance(absfreq_frac_bits, (bool, np.bool_)) or not isinstance(absfreq_frac_bits, numbers.Real) \
+            or int(absfreq_frac_bits) != absfreq_frac_bits or not 0 <= int(absfreq_frac_bits) <= 32:
+        raise ValueError("absfreq_frac_bits must be an integer 0..32")
+    nw = np.asarray(spectrum_edges).size - 1
+    if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
+        raise ValueError("absfreq_edges: at most 4096 classes and (no + 2) * (nbins + 2) <= 65536 cells a frame")
+    return edges, int(absfreq_frac_bits)
+
+
+def _absfreq_line(edges, frac_bits):
+    """The one extra log line of a run with the absolute-frequency series."""
+    return f"Absolute frequency: {edges.size - 1} classes over [{edges[0]:g}, {edges[-1]:g}], quantum 2^-{frac_bits}"
 
 
 def _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, nrings):
@@ -565,10 +598,13 @@ def _track_args(track_ids, track_every, Npackets, default_every):
 
 
 def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False, conds=False, trans=None, index=0,
-                refrs=False):
+                refrs=False, absfreq=None):
     """One packet frame: its spectrum, its map, its k-plane, its conditional
     spectrum and its refraction frame (both in the flow of slot 0, the snapshot
-    at the packets' time) and its
+    at the packets' time), its absolute-frequency frame (``absfreq``: the
+    interval group's (slot_a, slot_b, dt) of the last completed interval, read
+    at alpha = 1: the flow at the packets' time and the rate of the interval
+    they just crossed) and its
     transition frame recorded on the device (queued, no host wait) whether or
     not the frame itself is written.  ``trans``: the run's lag (0: never
     re-marked); packet frame ``index`` records against the mark, and re-marks
@@ -583,6 +619,8 @@ def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False
         ens.record_cond()
     if refrs:
         ens.record_refr()
+    if absfreq is not None:
+        ens.record_absfreq(absfreq[0], absfreq[1], 1.0, absfreq[2])
     if trans is not None:
         ens.record_trans(t)
         if trans and index % trans == 0:
@@ -842,7 +880,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                   cond_by=None, cond_edges=None, cond_frac_bits=20,
                   trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20,
                   recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20,
-                  refr_edges=None, refr_frac_bits=20):
+                  refr_edges=None, refr_frac_bits=20, absfreq_edges=None, absfreq_frac_bits=20):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -961,9 +999,28 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     na, nw, frac_bits, the alignment edges, the omega edges); frame i belongs
     to packet frame i + 1; no other output changes and ``packet_files=False``
     is allowed with it.
+    ``absfreq_edges`` (the no + 1 increasing class edges of the absolute
+    frequency Omega = omega + U.k; needs ``spectrum_edges``): the
+    absolute-frequency series (swrt_absfreq_series_*).  Beside every packet
+    frame but the first, after a recycle event that falls on the frame, the
+    counts of the packets over (Omega class, omega class) and the per-class
+    sums of dOmega/dt = k.dU/dt, its square and the Doppler shift U.k in
+    quanta of 2^-``absfreq_frac_bits`` are recorded on the device from the two
+    snapshots that bracket the last completed PDE interval, at alpha = 1 with
+    tau that interval's dt (the flow at the packets' time, the rate of the
+    interval they just crossed), and written as absfreq_hist.bin (int64,
+    (no + 2) x (nw + 2) per frame, cell (oc, wc) at oc*(nw + 2) + wc),
+    absfreq_sums.bin (3 (nw + 2) + 2 (no + 2) int64 per frame: Omega-dot,
+    Omega-dot^2 and U.k per omega class, then Omega-dot and Omega-dot^2 per
+    Omega class), absfreq_stats.bin (n, rejected per frame) and
+    absfreq_geom.bin (doubles: no, nw, frac_bits, the Omega edges, the omega
+    edges); frame i belongs to packet frame i + 1; run.log gets one line after
+    its parameter block; no other output changes and ``packet_files=False`` is
+    allowed with it.
     Returns a dict of run facts (dt, Nsteps, steps run, frames written,
     final t, spectrum_frames, map_frames, track_frames, kmap_frames,
-    flow_frames, cond_frames, trans_frames, recycle_events, refr_frames)."""
+    flow_frames, cond_frames, trans_frames, recycle_events, refr_frames,
+    absfreq_frames)."""
     _flow_args(flow_spectrum, Npackets)
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files, kmap_cells)
     map_args = _map_args(map_cells, map_frac_bits)
@@ -973,6 +1030,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     track_args = _track_args(track_ids, track_every, Npackets, 5)  # (5: packet_steps_per_save below)
     cond_args = _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges)
     refr_args = _refr_args(refr_edges, refr_frac_bits, spectrum_edges)
+    absfreq_args = _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges)
     trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
     if trans_args is not None and Npackets <= 0:
         raise ValueError("the transition series needs packets")
@@ -1017,6 +1075,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                         packet_steps_per_save, f, Cg, U_g, U0, Fr, K_d2))
     if several_rings:
         log(_rings_line(ring_factors, f, Cg))
+    if absfreq_args is not None:
+        log(("\n" if several_rings else "") + _absfreq_line(*absfreq_args) + "\n")  # (a line of its own)
     ens = PacketEnsemble(x, k, L, f, Cg, nx, K_d2, shear=0.0, k_scale=1.0, nlayers=1, bump=BUMP_QG, ctx=ctx,
                          shard=(rank, world), bounds=bounds) \
         if Npackets > 0 else None
@@ -1043,6 +1103,9 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     refrs = ens is not None and refr_args is not None
     if refrs:  # (no frame beside the first packet frame: no snapshot exists yet)
         ens.begin_refr(spectrum_edges, refr_args[0], refr_args[1], directory=out_dir)
+    absfreqs = ens is not None and absfreq_args is not None
+    if absfreqs:  # (no frame beside the first packet frame: no interval is complete yet)
+        ens.begin_absfreq(spectrum_edges, absfreq_args[0], absfreq_args[1], directory=out_dir)
     trans = None  # (the lag, 0: never re-marked; None: no transition series)
     if ens is not None and trans_args is not None:  # (the mark beside the first packet frame; frames from the second on)
         _begin_trans(ens, trans_args, spectrum_edges, out_dir, dt * (packet_step_start - 1), Npackets,
@@ -1092,7 +1155,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                 group.flush()
                 if recycle and frames % recycle == 0:
                     ens.recycle(t)  # (before the frame: it holds no packet at or above the cut)
-                _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames, refrs)
+                _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames, refrs,
+                            group.last if absfreqs else None)
                 if flows:
                     model.record_flow_spectrum()
                 frames += 1
@@ -1114,6 +1178,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     trans_frames = ens.write_trans(out_dir) if trans is not None else 0
     recycle_events = ens.write_recycle(out_dir) if recycle else 0
     refr_frames = ens.write_refrs(out_dir) if refrs else 0
+    absfreq_frames = ens.write_absfreqs(out_dir) if absfreqs else 0
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -1124,7 +1189,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
                 track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames,
-                trans_frames=trans_frames, recycle_events=recycle_events, refr_frames=refr_frames)
+                trans_frames=trans_frames, recycle_events=recycle_events, refr_frames=refr_frames,
+                absfreq_frames=absfreq_frames)
 
 
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
@@ -1136,7 +1202,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                         cond_by=None, cond_edges=None, cond_frac_bits=20,
                         trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20,
                         recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20,
-                        refr_edges=None, refr_frac_bits=20):
+                        refr_edges=None, refr_frac_bits=20, absfreq_edges=None, absfreq_frac_bits=20):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
@@ -1148,7 +1214,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     ``flow_spectrum``, ``cond_by``, ``cond_edges``, ``cond_frac_bits``,
     ``trans_src_edges``, ``trans_by``, ``trans_lag``, ``trans_frac_bits``,
     ``recycle_omega``, ``recycle_seed``, ``recycle_every``,
-    ``recycle_frac_bits``, ``refr_edges``, ``refr_frac_bits`` and a
+    ``recycle_frac_bits``, ``refr_edges``, ``refr_frac_bits``,
+    ``absfreq_edges``, ``absfreq_frac_bits`` and a
     sequence of factors as ``near_inertial_factor``: as in
     :func:`qgsw_raytrace`.
 
@@ -1169,6 +1236,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     track_args = _track_args(track_ids, track_every, Npackets, 25)  # (25: packet_steps_per_save below)
     cond_args = _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges)
     refr_args = _refr_args(refr_edges, refr_frac_bits, spectrum_edges)
+    absfreq_args = _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges)
     trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
     if trans_args is not None and Npackets <= 0:
         raise ValueError("the transition series needs packets")
@@ -1212,6 +1280,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                         packet_steps_per_save, f, Cg, U_g, U0, Fr, K_d2, two_layer=True))
     if several_rings:
         log(_rings_line(ring_factors, f, Cg))
+    if absfreq_args is not None:
+        log(("\n" if several_rings else "") + _absfreq_line(*absfreq_args) + "\n")  # (a line of its own)
     ens = PacketEnsemble(x, k, L, f, Cg, nx, K_d2, shear=shear, k_scale=2 * math.pi / L, nlayers=2,
                          bump=BUMP_QG, ctx=ctx, shard=(rank, world), bounds=bounds) if Npackets > 0 else None
     t = 0.0
@@ -1231,6 +1301,9 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     refrs = ens is not None and refr_args is not None
     if refrs:  # (no frame beside the first packet frame: no snapshot exists yet)
         ens.begin_refr(spectrum_edges, refr_args[0], refr_args[1], directory=out_dir)
+    absfreqs = ens is not None and absfreq_args is not None
+    if absfreqs:  # (no frame beside the first packet frame: no interval is complete yet)
+        ens.begin_absfreq(spectrum_edges, absfreq_args[0], absfreq_args[1], directory=out_dir)
     trans = None  # (the lag, 0: never re-marked; None: no transition series)
     if ens is not None and trans_args is not None:  # (the mark beside the first packet frame; frames from the second on)
         _begin_trans(ens, trans_args, spectrum_edges, out_dir, dt * (packet_step_start - 1), Npackets,
@@ -1278,7 +1351,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
             loop.flush()
             if recycle and frames % recycle == 0:
                 ens.recycle(loop.t)  # (before the frame: it holds no packet at or above the cut)
-            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames, refrs)
+            _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames, refrs,
+                        loop.group.last if absfreqs else None)
             if flows:
                 model.record_flow_spectrum()  # (the committed qk at loop.t; the next step is only speculative)
             frames += 1
@@ -1295,6 +1369,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     trans_frames = ens.write_trans(out_dir) if trans is not None else 0
     recycle_events = ens.write_recycle(out_dir) if recycle else 0
     refr_frames = ens.write_refrs(out_dir) if refrs else 0
+    absfreq_frames = ens.write_absfreqs(out_dir) if absfreqs else 0
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -1307,4 +1382,5 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     return dict(dt=dt, dts=dts, Nsteps=Nsteps, steps=step, packet_frames=frames, t=t, U0=U0,
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
                 track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames,
-                trans_frames=trans_frames, recycle_events=recycle_events, refr_frames=refr_frames)
+                trans_frames=trans_frames, recycle_events=recycle_events, refr_frames=refr_frames,
+                absfreq_frames=absfreq_frames)
