@@ -187,6 +187,52 @@ int swrt_set_gather_mode(swrt_ctx* ctx, int mode);
  * order: bit-identical for any setting. */
 int swrt_set_sparse_tiles(swrt_ctx* ctx, int mode);
 
+/* The packet step of swrt_advance, swrt_advance_intervals and swrt_leapfrog.
+ *
+ * The reference's step (ode_symplectic.m:13-37) is drift dt/2, kick dt, drift
+ * dt/2, and its kick phi2 (ode_symplectic.m:18-21) moves x by dt*U(x1) and k
+ * by -dt*(grad U(x1))^T k1: one explicit Euler step of the sub-flow of
+ * H2 = U(x).k.  That sub-flow is not integrable, so the Euler step is neither
+ * its exact flow nor symmetric, and the splitting around it is FIRST order
+ * (the conserved frequency drifts as O(dt)), whatever the file names of the
+ * reference's error plots say.  Its yoshida (ode_symplectic.m:39-53) computes
+ * triple-jump weights and never applies them (and its w0 lacks the minus
+ * sign that makes 2*w1 + w0 = 1).
+ *
+ *   kick 0 (default)  the reference's Euler kick.                   Order 1.
+ *   kick 1            the implicit midpoint rule of the same sub-flow:
+ *                     xm = x1 + (h/2)*U(xm) by `iterations` (1..4) fixed-
+ *                     point passes from xm = x1 (each one gather of u and
+ *                     v), U and grad U once at xm, x2 = x1 + h*U, and
+ *                     (1 + (h/2)A) k2 = (1 - (h/2)A) k1, A = (grad U)^T,
+ *                     by Cramer's rule.  Symmetric.                 Order 2.
+ *   composition 0     one stage of size dt.
+ *   composition 1     Yoshida's triple jump, stage sizes w*dt with
+ *                     w = {w1, 1 - 2*w1, w1}, w1 = 1/(2 - 2^(1/3)).
+ *                     Over kick 1: order 4.  Over kick 0 (a base that is
+ *                     not symmetric): order 1, worse than the plain step.
+ *   composition 2     Suzuki's five stages, w = {s, s, 1 - 4*s, s, s},
+ *                     s = 1/(4 - 4^(1/3)).  Over kick 1: order 4.
+ *
+ * A stage is drift(h/2), kick(h), drift(h/2) with its own blend value
+ * a_j = (alpha0 + s*dalpha) + off_j*dalpha (the stage's midpoint within the
+ * step), so a composite step is, bit for bit, its stages as single-step
+ * swrt_advance(w_j*dt, 1, .., alpha0 = a_j, dalpha = 0, ..) calls under the
+ * same kick.  History frames, save_every and the re-binning cadence count
+ * composite steps.  iterations is ignored for kick 0.  The default is
+ * (0, 1, 0): the reference's arithmetic, bit for bit.  Setting it does not
+ * invalidate the binning.  A non-default integrator with
+ * swrt_set_gather_mode(1) makes the advance calls fail with SWRT_ERR_ARG: the
+ * FMA gather has the leapfrog step only.  ode23, xka and
+ * swrt_spectral_leapfrog are not affected. */
+int swrt_set_integrator(swrt_ctx* ctx, int kick, int iterations, int composition);
+int swrt_get_integrator(const swrt_ctx* ctx, int* kick, int* iterations, int* composition);
+
+/* The stage weights and blend offsets of a composition (0, 1 or 2), as the
+ * exact doubles the device uses: w5[0..nstages-1], off5[0..nstages-1] (the
+ * rest 0).  No context and no GPU call. */
+int swrt_integrator_weights(int composition, double* w5, double* off5, int* nstages);
+
 /* Packet streams of the LDS-tiled leapfrog: 2 (default) or 1.  With 2 every
  * launch runs as two part launches — the even and the odd band positions of
  * each XCD band's tiles (the mapping: swraytracing_amd/csrc/swrt_share.hpp)

@@ -32,6 +32,33 @@ classdef SwrtContext < handle
             obj.release();
         end
 
+        % The packet step of leapfrog / advance / advance_intervals
+        % (swrt_set_integrator): kick 0 (the reference's Euler kick, first
+        % order) or 1 (implicit midpoint, iterations 1..4, second order);
+        % composition 0, 1 (Yoshida) or 2 (Suzuki; fourth order over kick 1).
+        % method (optional, instead of the three numbers): 'leapfrog',
+        % 'midpoint', 'yoshida4' or 'suzuki4'.
+        function set_integrator(obj, kick, iterations, composition, method)
+            if nargin > 4
+                switch method
+                    case 'leapfrog', kick = 0; iterations = 1; composition = 0;
+                    case 'midpoint', kick = 1; iterations = 2; composition = 0;
+                    case 'yoshida4', kick = 1; iterations = 4; composition = 1;
+                    case 'suzuki4',  kick = 1; iterations = 4; composition = 2;
+                    otherwise, error('swrt:arg', 'method must be leapfrog, midpoint, yoshida4 or suzuki4');
+                end
+            end
+            swrt_mex('set_integrator', obj.id(), kick, iterations, composition);
+        end
+
+        function s = get_integrator(obj)
+            s = swrt_mex('get_integrator', obj.id());  % [kick iterations composition]
+        end
+
+        function [w, off] = integrator_weights(~, composition)
+            [w, off] = swrt_mex('integrator_weights', composition);
+        end
+
         % The energy-vs-omega series of the device-resident packets
         % (analysis/load_data.m:33-52,63) and the ideal distribution
         % (ideal_omega_distribution.m:3-11): thin calls into swrt_mex.

@@ -199,6 +199,20 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     plhs[0] = mxCreateDoubleScalar((double)live_contexts());
     return;
   }
+  if (!strcmp(cmd, "integrator_weights")) {  // (composition 0|1|2) -> [w 1 x S, off 1 x S]; no context
+    if (nrhs < 2) mexErrMsgIdAndTxt("swrt:arg", "integrator_weights: composition");
+    double w[5], off[5];
+    int S = 0;
+    if (swrt_integrator_weights((int)scalar(prhs[1]), w, off, &S) != SWRT_OK)
+      mexErrMsgIdAndTxt("swrt:arg", "integrator_weights: composition must be 0 (none), 1 (Yoshida) or 2 (Suzuki)");
+    plhs[0] = mxCreateDoubleMatrix(1, (mwSize)S, mxREAL);
+    memcpy(mxGetDoubles(plhs[0]), w, sizeof(double) * (size_t)S);
+    if (nlhs > 1) {
+      plhs[1] = mxCreateDoubleMatrix(1, (mwSize)S, mxREAL);
+      memcpy(mxGetDoubles(plhs[1]), off, sizeof(double) * (size_t)S);
+    }
+    return;
+  }
   swrt_ctx* c = handle(nrhs, prhs);
   const mxArray** a = prhs + 1;  // a[1] = first argument after the handle
   const int na = nrhs - 1;
@@ -353,6 +367,19 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (!strcmp(cmd, "set_locality")) {  // (rebin_every, tile)
     need(na, 3, cmd);
     check(c, swrt_set_locality(c, (int64_t)scalar(a[1]), (int64_t)scalar(a[2])), "swrt_set_locality");
+    return;
+  }
+  if (!strcmp(cmd, "set_integrator")) {  // (kick, iterations, composition): the packet step of leapfrog / advance*
+    need(na, 4, cmd);
+    check(c, swrt_set_integrator(c, (int)scalar(a[1]), (int)scalar(a[2]), (int)scalar(a[3])), "swrt_set_integrator");
+    return;
+  }
+  if (!strcmp(cmd, "get_integrator")) {  // () -> [kick iterations composition]
+    int kick = 0, it = 0, comp = 0;
+    check(c, swrt_get_integrator(c, &kick, &it, &comp), "swrt_get_integrator");
+    plhs[0] = mxCreateDoubleMatrix(1, 3, mxREAL);
+    double* d = mxGetDoubles(plhs[0]);
+    d[0] = kick; d[1] = it; d[2] = comp;
     return;
   }
   if (!strcmp(cmd, "ode23_f1")) {  // (t, tmax, f, Cg, nslots, thr, bump) -> rh_raw

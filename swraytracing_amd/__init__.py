@@ -5,7 +5,7 @@ over SpectralScheme / interpolate_U / grid_U / g2k / k2g) as hand-written
 CDNA4 kernels behind the C ABI in include/swrt.h, with the reference's
 MATLAB call surface mirrored in Python.
 """
-from ._lib import Context, SwrtError, load
+from ._lib import Context, SwrtError, integrator_weights, load
 from .integrate import (PacketEnsemble, combine_conds, combine_frames, combine_kmaps, combine_maps, combine_spectra, combine_tracks,
                         combine_transitions, trans_moments, combine_recycles, recycle_flux,
                         combine_refrs, alignment_edges, refr_rates,
@@ -21,7 +21,7 @@ from .scheme import (BUMP_QG, BUMP_SW, DifferenceScheme, FourierScheme, Raytraci
                      SpectralScheme, g2k, grid_U, interpolate, interpolate_U, k2g)
 
 __all__ = [
-    "Context", "SwrtError", "load", "PacketEnsemble", "combine_frames", "combine_maps", "combine_spectra",
+    "Context", "SwrtError", "integrator_weights", "load", "PacketEnsemble", "combine_frames", "combine_maps", "combine_spectra",
     "combine_tracks", "combine_kmaps", "combine_conds", "cond_spectra",
     "combine_transitions", "trans_moments", "combine_recycles", "recycle_flux",
     "combine_refrs", "alignment_edges", "refr_rates",

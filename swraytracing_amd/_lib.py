@@ -68,6 +68,9 @@ SIGNATURES = {
     "swrt_set_kernel": (_INT, [_VP, _INT]),
     "swrt_set_gather_mode": (_INT, [_VP, _INT]),
     "swrt_set_sparse_tiles": (_INT, [_VP, _INT]),
+    "swrt_set_integrator": (_INT, [_VP, _INT, _INT, _INT]),
+    "swrt_get_integrator": (_INT, [_VP, ctypes.POINTER(_INT), ctypes.POINTER(_INT), ctypes.POINTER(_INT)]),
+    "swrt_integrator_weights": (_INT, [_INT, _P, _P, ctypes.POINTER(_INT)]),
     "swrt_set_packet_streams": (_INT, [_VP, _INT]),
     "swrt_advance": (_INT, [_VP, _D, _I, _D, _D, _INT, _D, _D, _D, _I]),
     "swrt_advance_intervals": (_INT, [_VP, _INT, _VP, _I, _D, _D, _D, _D, _D, _I]),
@@ -297,6 +300,31 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(_P)
 
 
+KICKS = {"euler": 0, "midpoint": 1}
+COMPOSITIONS = {None: 0, "yoshida": 1, "suzuki": 2}
+
+
+def _code(table, v, what):
+    """A setting by name or by its integer code."""
+    if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+        if v not in table:
+            raise ValueError(f"{what} must be one of {list(table)}, got {v!r}")
+        return table[v]
+    return int(v)
+
+
+def integrator_weights(composition=None):
+    """swrt_integrator_weights: (w, off), the stage weights and blend offsets
+    of a composition (None, "yoshida", "suzuki" or 0, 1, 2) as the exact
+    doubles the device uses.  No context and no GPU call."""
+    w, off, n = np.zeros(5), np.zeros(5), _INT(0)
+    rc = load().swrt_integrator_weights(_code(COMPOSITIONS, composition, "composition"), _p(w), _p(off),
+                                        ctypes.byref(n))
+    if rc != SWRT_OK:
+        raise SwrtError(f"swrt_integrator_weights: {ERRORS.get(rc, rc)}: unknown composition {composition!r}")
+    return w[:n.value].copy(), off[:n.value].copy()
+
+
 def _f64(a, order="C"):
     return np.require(np.asarray(a, dtype=np.float64), requirements=[order[0] + "_CONTIGUOUS", "ALIGNED"])
 
@@ -475,6 +503,25 @@ class Context:
     def set_sparse_tiles(self, mode=0):
         """swrt_set_sparse_tiles: 0 auto (below SWRT_SPARSE_BELOW packets per tile), 1 never, 2 always; same bits."""
         self._chk(self._L.swrt_set_sparse_tiles(self._h, int(mode)), "swrt_set_sparse_tiles")
+
+    def set_integrator(self, kick="euler", iterations=2, composition=None):
+        """swrt_set_integrator: the packet step of advance / advance_intervals /
+        leapfrog.  kick "euler" (the reference's, first order; the default) or
+        "midpoint" (implicit midpoint with `iterations` in 1..4 fixed-point
+        passes, second order); composition None, "yoshida" or "suzuki" (fourth
+        order over the midpoint kick).  The integer codes are accepted too."""
+        self._chk(self._L.swrt_set_integrator(self._h, _code(KICKS, kick, "kick"), int(iterations),
+                                              _code(COMPOSITIONS, composition, "composition")),
+                  "swrt_set_integrator")
+
+    def get_integrator(self):
+        """(kick, iterations, composition) as integer codes (swrt_get_integrator)."""
+        k, i, c = _INT(0), _INT(0), _INT(0)
+        self._chk(self._L.swrt_get_integrator(self._h, ctypes.byref(k), ctypes.byref(i), ctypes.byref(c)),
+                  "swrt_get_integrator")
+        return k.value, i.value, c.value
+
+    integrator_weights = staticmethod(integrator_weights)
 
     def set_packet_streams(self, streams=2):
         """swrt_set_packet_streams: 2 (default: tile launches split over two streams) or 1; same bits."""

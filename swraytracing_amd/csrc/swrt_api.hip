@@ -526,6 +526,41 @@ int swrt_set_gather_mode(swrt_ctx* c, int mode) {
   return SWRT_OK;
 }
 
+int swrt_set_integrator(swrt_ctx* c, int kick, int iterations, int composition) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (conservative: settings and syncs may precede packet-stream work)
+  if (kick != 0 && kick != 1) return fail(c, SWRT_ERR_ARG, "integrator kick must be 0 (Euler) or 1 (implicit midpoint)");
+  if (composition < 0 || composition > 2)
+    return fail(c, SWRT_ERR_ARG, "integrator composition must be 0 (none), 1 (Yoshida) or 2 (Suzuki)");
+  if (kick == 1 && (iterations < 1 || iterations > 4))
+    return fail(c, SWRT_ERR_ARG, "midpoint iterations must be 1..4");
+  c->integ_kick = kick;
+  c->integ_iters = kick == 1 ? iterations : 1;
+  c->integ_comp = composition;
+  return SWRT_OK;
+}
+
+int swrt_get_integrator(const swrt_ctx* c, int* kick, int* iterations, int* composition) {
+  if (!c) return SWRT_ERR_ARG;
+  if (kick) *kick = c->integ_kick;
+  if (iterations) *iterations = c->integ_iters;
+  if (composition) *composition = c->integ_comp;
+  return SWRT_OK;
+}
+
+int swrt_integrator_weights(int composition, double* w5, double* off5, int* nstages) {
+  if (!w5 || !off5 || !nstages) return SWRT_ERR_ARG;
+  double w[kMaxStages] = {}, off[kMaxStages] = {};
+  const int S = integrator_stages(composition, w, off);
+  if (S == 0) return SWRT_ERR_ARG;
+  for (int j = 0; j < kMaxStages; ++j) {
+    w5[j] = w[j];
+    off5[j] = off[j];
+  }
+  *nstages = S;
+  return SWRT_OK;
+}
+
 int swrt_set_packet_streams(swrt_ctx* c, int streams) {
   if (!c) return SWRT_ERR_ARG;
   c->s0_dirty = true;  // (conservative: settings and syncs may precede packet-stream work)
@@ -577,6 +612,10 @@ int swrt_advance(swrt_ctx* c, double dt, int64_t nsteps, double f, double gH, in
   if (nsteps < 0) return fail(c, SWRT_ERR_ARG, "nsteps < 0");
   if (nslots != 1 && nslots != 2) return fail(c, SWRT_ERR_ARG, "nslots must be 1 or 2");
   if (save_every < 0) return fail(c, SWRT_ERR_ARG, "save_every < 0");
+  if (!default_integrator(c) && c->gather_mode == 1)
+    return fail(c, SWRT_ERR_ARG,
+                "the FMA gather (swrt_set_gather_mode 1) has the leapfrog step only: set the integrator back to "
+                "(0, 1, 0) or the gather mode to 0");
   for (int s = 0; s < nslots; ++s)
     if (!c->slot[s].set) return fail(c, SWRT_ERR_STATE, "field slot not set");
   if (nslots == 2 && (c->slot[1].nx != c->slot[0].nx || c->slot[1].L != c->slot[0].L ||
@@ -609,6 +648,10 @@ int swrt_advance_intervals(swrt_ctx* c, int nintervals, const double* dts, int64
     return fail(c, SWRT_ERR_ARG, "nintervals must be 1..SWRT_MAX_SLOTS-1");
   if (!dts) return fail(c, SWRT_ERR_ARG, "dts is NULL");
   if (nsub < 1) return fail(c, SWRT_ERR_ARG, "nsub must be >= 1");
+  if (!default_integrator(c) && c->gather_mode == 1)
+    return fail(c, SWRT_ERR_ARG,
+                "the FMA gather (swrt_set_gather_mode 1) has the leapfrog step only: set the integrator back to "
+                "(0, 1, 0) or the gather mode to 0");
   if (save_every < 0 || (save_every > 0 && nsub % save_every))
     return fail(c, SWRT_ERR_ARG, "save_every must divide nsub");
   for (int s = 0; s <= nintervals; ++s) {
@@ -657,6 +700,10 @@ int swrt_leapfrog(swrt_ctx* c, double* x, double* k, int64_t n, double dt, int64
                   int64_t save_every, double* hist_x, double* hist_k) {
   if (!c) return SWRT_ERR_ARG;
   int rc;
+  if (!default_integrator(c) && c->gather_mode == 1)
+    return fail(c, SWRT_ERR_ARG,
+                "the FMA gather (swrt_set_gather_mode 1) has the leapfrog step only: set the integrator back to "
+                "(0, 1, 0) or the gather mode to 0");
   if ((rc = swrt_packets_set(c, x, k, n))) return rc;
   const int64_t se = (hist_x && hist_k) ? save_every : 0;
   if ((rc = swrt_advance(c, dt, nsteps, f, gH, nslots, alpha0, dalpha, bump, se))) return rc;

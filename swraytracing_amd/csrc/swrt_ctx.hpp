@@ -558,6 +558,9 @@ struct swrt_ctx {
   bool sort_lead = SWRT_SORT_LEAD;  // in-tile sort keys lead by the group-velocity drift
   int gather_mode = 0;      // 0: stencil sums mul then add (bit-exact); 1: fused multiply-add (tolerance)
   int sparse_mode = 0;      // sparse-tile launches: 0 auto (below kSparseBelow packets per tile), 1 never, 2 always
+  // the packet step (swrt_set_integrator): the kick (0 Euler, 1 implicit midpoint with integ_iters
+  // fixed-point passes) and the composition (0 none, 1 Yoshida, 2 Suzuki); (0, 1, 0) = the leapfrog step
+  int integ_kick = 0, integ_iters = 1, integ_comp = 0;
   // Two packet streams (swrt_set_packet_streams 2, the default): each
   // LDS-tiled leapfrog launch runs as 2 part launches — the even and the odd
   // band positions of every XCD band — on `stream` and the extra stream

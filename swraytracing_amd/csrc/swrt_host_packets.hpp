@@ -27,6 +27,54 @@ bool use_tile_kernel(const swrt_ctx* c) {
 // a binning of slot 0's grid into the tile kernel's tiles is in force
 bool tile_binned(const swrt_ctx* c) { return use_tile_kernel(c) && c->bin.tiled_for(tiles_per_side(c->slot[0].nx)); }
 
+// the packet step is the leapfrog step (swrt_set_integrator's default)
+bool default_integrator(const swrt_ctx* c) { return c->integ_kick == 0 && c->integ_comp == 0; }
+
+// Stage weights w and blend offsets off (in steps) of a composition: 0 none,
+// 1 Yoshida's triple jump, 2 Suzuki's five stages; the stage count, or 0 for
+// an unknown composition.  The literals are 1/(2 - 2^(1/3)) and
+// 1/(4 - 4^(1/3)) to within an ulp, as constants rather than a cbrt call (the
+// remaining weight is formed from them, so the sum is 1 to rounding).  Stage j sits at the midpoint of its
+// own share of the step: off_j = (w_1 + .. + w_{j-1}) + w_j/2 - 0.5, summed
+// left to right over the first half and mirrored with the opposite sign, the
+// middle one exactly 0.  The one place these numbers are made: the kernels
+// and swrt_integrator_weights take them from here.
+int integrator_stages(int composition, double* w, double* off) {
+  int S;
+  if (composition == 0) {
+    S = 1;
+    w[0] = 1.0;
+  } else if (composition == 1) {
+    const double w1 = 1.3512071919596578;
+    S = 3;
+    w[0] = w[2] = w1;
+    w[1] = 1.0 - 2.0 * w1;
+  } else if (composition == 2) {
+    const double s = 0.4144907717943757;
+    S = 5;
+    w[0] = w[1] = w[3] = w[4] = s;
+    w[2] = 1.0 - 4.0 * s;
+  } else {
+    return 0;
+  }
+  double acc = 0.0;
+  for (int j = 0; j < S / 2; ++j) {
+    off[j] = (acc + w[j] / 2) - 0.5;
+    off[S - 1 - j] = -off[j];
+    acc = acc + w[j];
+  }
+  off[S / 2] = 0.0;
+  return S;
+}
+
+StageArgs stage_args(const swrt_ctx* c) {
+  StageArgs g = {};
+  g.kick = c->integ_kick;
+  g.iters = c->integ_iters;
+  g.nstages = integrator_stages(c->integ_comp, g.w, g.off);
+  return g;
+}
+
 // the intervals of one multi-interval tile launch (swrt_advance_intervals)
 struct IvLaunch {
   int nint;
@@ -157,6 +205,7 @@ int launch_tiles(swrt_ctx* c, void (*kernel)(TileArgs), int nt, TileArgs t, bool
 // The sparse-tile launch shape (kSparseThreads threads, prefetch depth
 // kSparsePrefetch) for the two-snapshot five-sum launches over `ntiles` tiles.
 bool sparse_tiles(const swrt_ctx* c, int64_t ntiles) {
+  if (!default_integrator(c)) return false;  // the staged step has the dense shape only
   if (c->sparse_mode == 1) return false;
   if (c->sparse_mode == 2) return true;
   return c->n < (int64_t)kSparseBelow * ntiles;
@@ -189,6 +238,11 @@ int tile_cells(const swrt_ctx* c, int64_t nx) {
 // the per-packet leapfrog kernel blending `nslots` snapshots
 using LeapKernel = void (*)(StepArgs);
 LeapKernel leap_kernel(int nslots) { return nslots == 2 ? leapfrog_kernel<true> : leapfrog_kernel<false>; }
+// ... and its staged form (swrt_set_integrator)
+using LeapStageKernel = void (*)(StepArgs, StageArgs);
+LeapStageKernel leap_stage_kernel(int nslots) {
+  return nslots == 2 ? leapfrog_stage_kernel<true> : leapfrog_stage_kernel<false>;
+}
 
 // Counting-sort the packets by spatial tile of slot 0's grid (swrt_bin.hpp).
 // indirect: only build the source index of the binned order (c->src_idx);
@@ -277,6 +331,15 @@ TileKernel tile_kernel_of(bool two, bool v5, bool fma, bool sparse) {
 TileKernel tile_kernel_of(bool two, bool v5, bool fma, bool sparse, bool hist, bool multi) {
   return hist || multi ? tile_kernel_of<true>(two, v5, fma, sparse) : tile_kernel_of<false>(two, v5, fma, sparse);
 }
+// The staged step (swrt_set_integrator): the general form in the dense shape, mul-then-add sums.
+TileKernel tile_stage_kernel_of(bool two, bool v5) {
+  constexpr int T = kTile, M = kMargin, NT = kTileThreads, W4 = SWRT_TILE_MIN_WAVES;
+  if (two)
+    return {v5 ? tile_leapfrog_kernel<true, T, M, NT, true, false, 1, W4, true, true, true>
+               : tile_leapfrog_kernel<true, T, M, NT, false, false, 1, W4, true, true, true>, NT};
+  return {v5 ? tile_leapfrog_kernel<false, T, M, NT, true, false, 1, W4, true, true, true>
+             : tile_leapfrog_kernel<false, T, M, NT, false, false, 1, W4, true, true, true>, NT};
+}
 
 int tile_launch(swrt_ctx* c, const StepArgs& a, bool count_next, const IvLaunch* iv = nullptr) {
   TileArgs t;
@@ -287,6 +350,7 @@ int tile_launch(swrt_ctx* c, const StepArgs& a, bool count_next, const IvLaunch*
     for (int i = 0; i <= iv->nint; ++i) t.ivn[i] = iv->views[i].nodes;
     for (int i = 0; i < iv->nint; ++i) t.ivdt[i] = iv->dts[i];
   }
+  t.stg = stage_args(c);
   t.x_out = c->pk.out.x.get();
   t.k_out = c->pk.out.k.get();
   t.perm_out = c->pk.out.perm.get();
@@ -313,9 +377,11 @@ int tile_launch(swrt_ctx* c, const StepArgs& a, bool count_next, const IvLaunch*
   }
   const bool two = a.nslots == 2;
   const bool v5 = two ? (iv ? iv->div_free : two_v5(c, 2, 0)) : c->slot[0].div_free;
-  const TileKernel tk = tile_kernel_of(two, v5, c->gather_mode == 1,
-                                       two && v5 && tile_threads(c, true, ntiles) == kSparseThreads,
-                                       a.hist_x != nullptr, iv != nullptr);
+  const TileKernel tk = !default_integrator(c)
+                            ? tile_stage_kernel_of(two, v5)
+                            : tile_kernel_of(two, v5, c->gather_mode == 1,
+                                             two && v5 && tile_threads(c, true, ntiles) == kSparseThreads,
+                                             a.hist_x != nullptr, iv != nullptr);
   HIPCHK_RC(launch_tiles(c, tk.fn, tk.threads, t, zero));
   HIPCHK(c, hipGetLastError());
   // (a.f0: the view this launch bins by; a multi-interval launch: slot i0's)
@@ -350,7 +416,9 @@ int leap_launch(swrt_ctx* c, const StepArgs& a, unsigned grid) {
       return fail(c, SWRT_ERR_STATE, h.err);
   }
   c->bin.per_packet_launched();
-  if (c->kev1) {  // a timed launch: the dispatch stamps the events
+  if (!default_integrator(c)) {
+    launch_k(c, leap_stage_kernel(a.nslots), dim3(grid), dim3(256), a, stage_args(c));
+  } else if (c->kev1) {  // a timed launch: the dispatch stamps the events
     launch_k(c, leap_kernel(a.nslots), dim3(grid), dim3(256), a);
   } else {
     hipLaunchKernelGGL(leap_kernel(a.nslots), dim3(grid), dim3(256), 0, c->stream, a);

@@ -117,6 +117,24 @@ __device__ __forceinline__ void drift_inc(double k, double l, double f2, double 
   }
 }
 
+// The quotients of drift_inc alone, (qx, qy) = (gH*k/omega, gH*l/omega): a
+// staged step (StageArgs) multiplies them by the half sizes of the two stages
+// that share this k — the bits of two drift_inc calls.
+__device__ __forceinline__ void drift_quot(double k, double l, double f2, double gH, bool fast, double& qx,
+                                           double& qy) {
+  const double x = f2 + gH * (k * k + l * l);
+  if (fast) {
+    const double w = sqrt_rn_normal(x);
+    const double rw = rcp_rn_normal(w);
+    qx = div_rn_z(gH * k, w, rw);
+    qy = div_rn_z(gH * l, w, rw);
+  } else {
+    const double w = sqrt(x);
+    qx = gH * k / w;
+    qy = gH * l / w;
+  }
+}
+
 // n1 / sqrt(r) and n2 / sqrt(r) in IEEE operations (odefun's Cg*k/s,
 // qgsw_raytrace.m:262-263): fast (r >= f^2 >= 2^-767, uniform) as drift_inc.
 __device__ __forceinline__ void quot2_sqrt(double r, double n1, double n2, bool fast, double& q1, double& q2) {
@@ -571,6 +589,156 @@ __global__ void __launch_bounds__(256) leapfrog_kernel(StepArgs a) {
     y0 = y2 + hcy;
     k0 = k2;
     l0 = l2;
+    if (a.hist_x != nullptr && ((sg + 1) % a.save_every) == 0) {
+      const int64_t fr = a.frame0 + (sg + 1) / a.save_every - 1;
+      double* hx = a.hist_x + fr * 2 * a.n;
+      double* hk = a.hist_k + fr * 2 * a.n;
+      const int64_t o = a.perm[p];  // frames are stored in the original packet order
+      hx[o] = x0; hx[a.n + o] = y0;
+      hk[o] = k0; hk[a.n + o] = l0;
+    }
+  }
+  a.x[p] = x0; a.x[a.n + p] = y0;
+  a.k[p] = k0; a.k[a.n + p] = l0;
+}
+
+// ---------------------------------------------------------------------------
+// Staged steps (swrt_set_integrator): a step of S stages, stage j being
+//   drift(h_j/2), kick(h_j, a_j), drift(h_j/2),  h_j = w_j*dt,
+//   a_j = (alpha0 + s*dalpha) + off_j*dalpha,
+// with the weights and blend offsets of swrt_integrator_weights.  The kick is
+// phi2 of ode_symplectic.m:18-21 (kick 0: one explicit Euler step of the
+// sub-flow of U(x).k, first order) or its implicit midpoint rule (kick 1:
+// symmetric, second order; `iters` fixed-point passes for the midpoint
+// position, a 2x2 solve for the linear k equation).  S = 1 with kick 0 is
+// leapfrog_kernel's step, bit for bit; a staged step is, bit for bit, its S
+// stages as single steps of size h_j at blend a_j.
+// ---------------------------------------------------------------------------
+constexpr int kMaxStages = 5;
+
+struct StageArgs {
+  int kick;     // 0: Euler kick, 1: implicit midpoint
+  int iters;    // kick 1: passes of xm = x1 + (h/2)*U(xm)
+  int nstages;  // 1, 3 (Yoshida) or 5 (Suzuki)
+  int pad_;
+  double w[kMaxStages];
+  double off[kMaxStages];
+};
+
+// Stage weights by constant-index selects (see iv_nodes: a runtime index into
+// a by-value kernel argument would copy it to scratch).
+__device__ __forceinline__ double stage_sel(const double (&v)[kMaxStages], int j) {
+  double r = v[0];
+#pragma unroll
+  for (int q = 1; q < kMaxStages; ++q)
+    if (j == q) r = v[q];
+  return r;
+}
+
+// The u and v sums of gather6 alone: the same products in the same order, so
+// the bits of gather6's first two sums at the same stencil.  LEAN: a
+// scheduling barrier after every tap (gather6_lean's register-light form).
+template <bool TWO, bool LEAN>
+__device__ __forceinline__ void gather2(const double* nodes0, const double* nodes1, int npad, const Stencil& s,
+                                        double o0[2], double o1[2]) {
+  o0[0] = o0[1] = -0.0;
+  o1[0] = o1[1] = -0.0;
+  const size_t off = ((size_t)s.ic * npad + s.jc) * kRec;
+#pragma unroll
+  for (int i = 0; i < kNT; ++i) {
+    const size_t ro = off + (size_t)i * npad * kRec;
+    const double2* r0 = reinterpret_cast<const double2*>(nodes0 + ro);
+    const double2* r1 = reinterpret_cast<const double2*>(nodes1 + ro);
+#pragma unroll
+    for (int j = 0; j < kNT; ++j) {
+      const double wij = s.wx[i] * s.wy[j];
+      const double2 a0 = r0[3 * j];
+      o0[0] = o0[0] + wij * a0.x; o0[1] = o0[1] + wij * a0.y;
+      if constexpr (TWO) {
+        const double2 b0 = r1[3 * j];
+        o1[0] = o1[0] + wij * b0.x; o1[1] = o1[1] + wij * b0.y;
+      }
+      if constexpr (LEAN) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+// eval_flow_t's blended u and v alone.
+template <bool TWO>
+__device__ __forceinline__ void eval_uv_t(const FieldView& f0, const FieldView& f1, double alpha, double x, double y,
+                                          double bump, double& u, double& v) {
+  Stencil s;
+  stencil_at(f0, x, y, bump, s);
+  double I[2], J[2];
+  gather2<TWO, false>(f0.nodes, f1.nodes, f0.npad, s, I, J);
+  if constexpr (TWO) {
+    const double oma = 1 - alpha;
+    I[0] = oma * I[0] + alpha * J[0];
+    I[1] = oma * I[1] + alpha * J[1];
+  }
+  u = I[0];
+  v = I[1];
+}
+
+// The kick's k update from the flow record I at the kick's evaluation point:
+// Euler, k2 = k1 - h*(grad U)^T k1 (RaytracingScheme.m:14-15), or the implicit
+// midpoint rule (1 + hh*A) k2 = (1 - hh*A) k1 with A = (grad U)^T, hh = h/2,
+// solved by Cramer's rule with IEEE divisions.
+__device__ __forceinline__ void kick_k(bool midpoint, double h, double hh, const double I[kRec], double k1, double l1,
+                                       double& k2, double& l2) {
+  if (midpoint) {
+    const double ux = I[2], uy = I[3], vx = I[4], vy = I[5];
+    const double r1 = k1 - hh * (ux * k1 + vx * l1);
+    const double r2 = l1 - hh * (uy * k1 + vy * l1);
+    const double a11 = 1 + hh * ux, a12 = hh * vx, a21 = hh * uy, a22 = 1 + hh * vy;
+    const double det = a11 * a22 - a12 * a21;
+    k2 = (a22 * r1 - a12 * r2) / det;
+    l2 = (a11 * r2 - a21 * r1) / det;
+  } else {
+    k2 = k1 - h * (I[2] * k1 + I[4] * l1);
+    l2 = l1 - h * (I[3] * k1 + I[5] * l1);
+  }
+}
+
+// leapfrog_kernel with the stage loop: one lane per packet, global gathers.
+template <bool TWO>
+__global__ void __launch_bounds__(256) leapfrog_stage_kernel(StepArgs a, StageArgs g) {
+  const int64_t p = xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
+  if (p >= a.n) return;
+  double x0 = a.x[p], y0 = a.x[a.n + p];
+  double k0 = a.k[p], l0 = a.k[a.n + p];
+  const bool midpoint = g.kick != 0;
+  const int nit = midpoint ? g.iters : 0;
+  double qx, qy;  // gH*k/omega of the current k: both drifts around a kick boundary
+  drift_quot(k0, l0, a.f2, a.gH, a.fastdisp, qx, qy);
+  for (int s = 0; s < a.nsteps; ++s) {
+    const int64_t sg = a.s0 + s;
+    const double alpha_s = a.alpha0 + (double)sg * a.dalpha;
+    for (int j = 0; j < g.nstages; ++j) {
+      const double h = stage_sel(g.w, j) * a.dt;
+      const double hh = 0.5 * h;
+      const double alpha = alpha_s + stage_sel(g.off, j) * a.dalpha;
+      const double x1 = x0 + hh * qx;
+      const double y1 = y0 + hh * qy;
+      double xm = x1, ym = y1;
+      for (int it = 0; it < nit; ++it) {
+        double u, v;
+        eval_uv_t<TWO>(a.f0, a.f1, alpha, xm, ym, a.bump, u, v);
+        xm = x1 + hh * u;
+        ym = y1 + hh * v;
+      }
+      double I[kRec];
+      eval_flow_t<TWO>(a.f0, a.f1, alpha, xm, ym, a.bump, I);
+      const double x2 = x1 + h * I[0];
+      const double y2 = y1 + h * I[1];
+      double k2, l2;
+      kick_k(midpoint, h, hh, I, k0, l0, k2, l2);
+      drift_quot(k2, l2, a.f2, a.gH, a.fastdisp, qx, qy);
+      x0 = x2 + hh * qx;
+      y0 = y2 + hh * qy;
+      k0 = k2;
+      l0 = l2;
+    }
     if (a.hist_x != nullptr && ((sg + 1) % a.save_every) == 0) {
       const int64_t fr = a.frame0 + (sg + 1) / a.save_every - 1;
       double* hx = a.hist_x + fr * 2 * a.n;

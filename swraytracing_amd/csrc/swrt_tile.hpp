@@ -56,6 +56,9 @@ struct TileArgs {
   int nint;
   const double* ivn[kMaxIntervals + 1];
   double ivdt[kMaxIntervals];
+  // the staged step (swrt_set_integrator; read by the STG instantiations only,
+  // from the kernarg segment inside the stage loop)
+  StageArgs stg;
 };
 
 // The kernel's argument block read again from the kernarg segment (scalar
@@ -286,6 +289,47 @@ __device__ __forceinline__ void gather5_lds(const double2* lds, int node0, const
   o1[5] = -o1[2];
 }
 
+// The u and v sums alone (a midpoint kick's fixed-point passes): the {u,v}
+// chunks of the window — chunk 0 and, with two snapshots, chunk 3 in the
+// five-sum and the six-sum layout alike — one ds_read_b128 a tap and
+// snapshot, pipelined one tap ahead like gather5_lds.  The same products in
+// the same order: the bits of the full gathers' first two sums.
+template <bool TWO, int W, int WN>
+__device__ __forceinline__ void gather2_lds(const double2* lds, int node0, const Stencil& s, double o0[2],
+                                            double o1[2]) {
+  constexpr int NTAP = kNT * kNT;
+  o0[0] = o0[1] = -0.0;
+  o1[0] = o1[1] = -0.0;
+  const double2* p = lds + node0;
+  double wx[kNT], wy[kNT];
+#pragma unroll
+  for (int q = 0; q < kNT; ++q) {
+    wx[q] = s.wx[q];
+    wy[q] = s.wy[q];
+    asm volatile("" : "+v"(wx[q]));
+    asm volatile("" : "+v"(wy[q]));
+  }
+  double2 ra[2], rb[2];
+  ra[0] = p[0];
+  if constexpr (TWO) rb[0] = p[3 * WN];
+#pragma unroll
+  for (int t = 0; t < NTAP; ++t) {
+    const int i = t / kNT, j = t % kNT;
+    if (t + 1 < NTAP) {
+      const int e = ((t + 1) / kNT) * W + (t + 1) % kNT;
+      ra[(t + 1) & 1] = p[e];
+      if constexpr (TWO) rb[(t + 1) & 1] = p[3 * WN + e];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const double wij = wx[i] * wy[j];
+    o0[0] = o0[0] + wij * ra[t & 1].x; o0[1] = o0[1] + wij * ra[t & 1].y;
+    if constexpr (TWO) {
+      o1[0] = o1[0] + wij * rb[t & 1].x; o1[1] = o1[1] + wij * rb[t & 1].y;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // Stage tile (ox, oy)'s window into LDS, chunk-major (chunk c of node e at
 // win[c*WN + e]): node (wi, wj) <-> global node (ox-M-2+wi, oy-M-2+wj) mod nx.
 // Register staging: each lane copies whole 48-B records, 3 or 6 loads back
@@ -485,6 +529,56 @@ __device__ __forceinline__ void sort_batch_by_cell(int b0, int nb, bool first_ba
   __syncthreads();
 }
 
+// The blended flow at (x, y) for a staged step (the STG instantiations of
+// tile_leapfrog_kernel): the step loop's stencil, window test, LDS or global
+// gather and blend, as a function of the point.  UV: u and v only, into
+// I[0..1] (gather2_lds / gather2).  The blend value of stage j of the step
+// with index sgd, (alpha0 + sgd*dalpha) + off_j*dalpha, is formed after the
+// gather from the kernarg segment: launch-uniform, but an fp64 value lives in
+// vector registers, and the gather has none to spare.
+template <bool TWO, int T, int M, int WS, int WNP, bool V5, bool UV>
+__device__ __forceinline__ void tile_flow_at(const double2* win, const FieldView& f0, const double* n0,
+                                             const double* n1, int oxm, int oym, double x, double y, double bump,
+                                             double sgd, int j, double I[kRec]) {
+  const int nx = f0.nx;
+  Stencil sc;
+  stencil_at(f0, x, y, bump, sc);
+  const int d0 = sc.ic - oxm, d1 = sc.jc - oym;
+  const unsigned ux = min((unsigned)d0, (unsigned)(d0 + nx)), uy = min((unsigned)d1, (unsigned)(d1 + nx));
+  const bool inwin = max(ux, uy) < (unsigned)(T + 2 * M);
+  double J[kRec];
+  if constexpr (UV) {
+    if (inwin)
+      gather2_lds<TWO, WS, WNP>(win, (int)(ux * WS + uy), sc, I, J);
+    else
+      gather2<TWO, true>(n0, n1, f0.npad, sc, I, J);
+  } else {
+    if (inwin) {
+      if constexpr (V5)
+        gather5_lds<TWO, WS, WNP>(win, (int)(ux * WS + uy), sc, I, J);
+      else
+        gather6_lds<TWO, WS, WNP>(win, (int)(ux * WS + uy), sc, I, J);
+    } else {
+      gather6_lean<TWO>(n0, n1, f0.npad, sc, I, J);
+    }
+  }
+  if constexpr (TWO) {
+    const auto* g = tile_args_again();
+    const double dalpha = g->s.dalpha;
+    const double alpha = (g->s.alpha0 + sgd * dalpha) + g->stg.off[j] * dalpha;
+    const double oma = 1 - alpha;
+#pragma unroll
+    for (int q = 0; q < (UV ? 2 : (V5 ? 5 : kRec)); ++q) I[q] = oma * I[q] + alpha * J[q];
+    if constexpr (V5 && !UV) I[5] = -I[2];
+  }
+}
+
+// Stage j's size h_j = w_j*dt, from the kernarg segment (as above).
+__device__ __forceinline__ double tile_stage_h(int j, double dt) {
+  const auto* g = tile_args_again();
+  return g->stg.w[j] * dt;
+}
+
 #ifndef SWRT_TILE_MIN_WAVES
 #define SWRT_TILE_MIN_WAVES 4
 #endif
@@ -499,10 +593,14 @@ __device__ __forceinline__ void sort_batch_by_cell(int b0, int nb, bool first_ba
 // selects, no save_every / frame0 arithmetic, and none of their arguments
 // live.  The other one (both) takes every call; the host picks
 // (tile_kernel_of).  Same arithmetic in both.
+// STG: the staged step (TileArgs::stg, swrt_set_integrator) in place of the
+// leapfrog step: runtime loops over the stages and the midpoint kick's
+// passes, uniform across the launch; the general form only (HIST and MULTI).
 template <bool TWO, int T, int M, int NT, bool V5 = false, bool FMA = false, int PF = 1,
-          int MINW = SWRT_TILE_MIN_WAVES, bool HIST = true, bool MULTI = true>
+          int MINW = SWRT_TILE_MIN_WAVES, bool HIST = true, bool MULTI = true, bool STG = false>
 __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
   static_assert(!FMA || V5, "the FMA gather exists for the five-sum window only");
+  static_assert(!STG || (HIST && MULTI && !FMA && PF == 1), "the staged step exists for the general form only");
   constexpr int W = T + 5 + 2 * M;  // window side in nodes
   // row stride = 12 (mod 16) nodes: any 4x4 block of window nodes falls on
   // 16 distinct ds_read_b128 bank quads (node n -> quad (n mod 16)), so lanes
@@ -653,7 +751,48 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
       // the blend's step index as a double, counted up by exact additions
       // (integers < 2^53): (double)sg without an int64 conversion per step
       double sgd = (double)(ivmode ? (int64_t)0 : sbase);
+      // (staged step) gH*k/omega of the current k, for the drifts either side of a kick
+      double qx = 0.0, qy = 0.0;
+      if constexpr (STG) drift_quot(k0, l0, a.f2, a.gH, a.fastdisp, qx, qy);
       for (int st = 0; st < a.nsteps; ++st) {
+        if constexpr (STG) {
+          const auto* gk = tile_args_again();
+          const int nstages = gk->stg.nstages;
+          const bool midpoint = gk->stg.kick != 0;
+          const int nit = midpoint ? gk->stg.iters : 0;
+          for (int j = 0; j < nstages; ++j) {
+            // (the stage's size is formed again wherever it is used, not held across a gather)
+            double x1, y1;
+            {
+              const double hh = 0.5 * tile_stage_h(j, dt);
+              x1 = x0 + hh * qx;
+              y1 = y0 + hh * qy;
+            }
+            double xm = x1, ym = y1;
+            double I[kRec];
+            for (int it = 0; it < nit; ++it) {
+              tile_flow_at<TWO, T, M, WS, WNP, V5, true>(win, a.f0, fa.nodes, fb.nodes, oxm, oym, xm, ym, a.bump,
+                                                         sgd, j, I);
+              const double hh = 0.5 * tile_stage_h(j, dt);
+              xm = x1 + hh * I[0];
+              ym = y1 + hh * I[1];
+            }
+            tile_flow_at<TWO, T, M, WS, WNP, V5, false>(win, a.f0, fa.nodes, fb.nodes, oxm, oym, xm, ym, a.bump,
+                                                        sgd, j, I);
+            const double h = tile_stage_h(j, dt);
+            const double hh = 0.5 * h;
+            const double x2 = x1 + h * I[0];
+            const double y2 = y1 + h * I[1];
+            double k2, l2;
+            kick_k(midpoint, h, hh, I, k0, l0, k2, l2);
+            drift_quot(k2, l2, a.f2, a.gH, a.fastdisp, qx, qy);
+            x0 = x2 + hh * qx;
+            y0 = y2 + hh * qy;
+            k0 = k2;
+            l0 = l2;
+          }
+          sgd = sgd + 1.0;
+        } else {
         const double alpha = a.alpha0 + sgd * a.dalpha;
         sgd = sgd + 1.0;
         const double x1 = x0 + hcx;
@@ -703,6 +842,7 @@ __global__ void __launch_bounds__(NT, MINW) tile_leapfrog_kernel(TileArgs ta) {
         y0 = y2 + hcy;
         k0 = k2;
         l0 = l2;
+        }  // the leapfrog step
         if constexpr (HIST) {
           const int64_t sg = sbase + st;
           if (a.hist_x != nullptr && ((sg + 1) % a.save_every) == 0) {

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._lib import Context, SwrtError
+from ._lib import Context, integrator_weights, SwrtError
 from .io import write_field
 from .scheme import BUMP_QG, SnapshotPairScheme, SpectralScheme, flow_planes
 
@@ -497,8 +497,70 @@ def combine_tracks(parts, ids, bounds):
     return out
 
 
-def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False):
+# method -> (kick, composition, default fixed-point iterations) of swrt_set_integrator
+METHODS = {"leapfrog": ("euler", None, 1), "midpoint": ("midpoint", None, 2),
+           "yoshida4": ("midpoint", "yoshida", 4), "suzuki4": ("midpoint", "suzuki", 4)}
+
+
+def packet_method(method="leapfrog", iterations=None):
+    """(kick, iterations, composition) of a packet-step method: "leapfrog" (the
+    reference's step, first order), "midpoint" (implicit-midpoint kick, second
+    order, 2 iterations) or "yoshida4" / "suzuki4" (fourth-order compositions
+    of the midpoint step, 4 iterations)."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {list(METHODS)}, got {method!r}")
+    kick, comp, it = METHODS[method]
+    if iterations is not None:
+        if method == "leapfrog":
+            raise ValueError("iterations belongs to the midpoint kick (method 'midpoint', 'yoshida4', 'suzuki4')")
+        it = int(iterations)
+        if not 1 <= it <= 4:
+            raise ValueError("iterations must be 1..4")
+    return kick, it, comp
+
+
+def _host_stage(xc, kc, h, f, gH, scheme, midpoint, iters):
+    """One stage drift(h/2), kick(h), drift(h/2) of the generic host path on
+    1 x 2 x P state (the arithmetic of swrt_set_integrator, include/swrt.h)."""
+
+    def gv(kk):
+        w = np.sqrt(f * f + gH * (kk[:, 0:1, :] * kk[:, 0:1, :] + kk[:, 1:2, :] * kk[:, 1:2, :]))
+        return gH * kk / w
+
+    hh = 0.5 * h
+    x1 = xc + hh * gv(kc)
+    if not midpoint:
+        x2 = x1 + h * scheme.U(x1)
+        k2 = kc - h * scheme.grad_U_times_k(x1, kc, 0)
+        return x2 + hh * gv(k2), k2
+    xm = x1
+    for _ in range(iters):
+        xm = x1 + hh * scheme.U(xm)
+    x2 = x1 + h * scheme.U(xm)
+    nab = scheme.grad_U(xm)
+    shp = kc[:, 0, ...].shape
+    ux, uy, vx, vy = (np.reshape(nab[n], shp, order="F") for n in ("u_x", "u_y", "v_x", "v_y"))
+    k1, l1 = kc[:, 0, ...], kc[:, 1, ...]
+    r1 = k1 - hh * (ux * k1 + vx * l1)
+    r2 = l1 - hh * (uy * k1 + vy * l1)
+    a11, a12, a21, a22 = 1 + hh * ux, hh * vx, hh * uy, 1 + hh * vy
+    det = a11 * a22 - a12 * a21
+    k2 = np.empty_like(kc)
+    k2[:, 0, ...] = (a22 * r1 - a12 * r2) / det
+    k2[:, 1, ...] = (a11 * r2 - a21 * r1) / det
+    return x2 + hh * gv(k2), k2
+
+
+def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False, method="leapfrog", iterations=None):
     """[x, k, t] = ode_symplectic(x0, k0, dt, T, f, gH, scheme).
+
+    ``method``: "leapfrog" (default: ode_symplectic.m:13-37, whose Euler kick
+    makes it first order), "midpoint" (implicit-midpoint kick, second order),
+    "yoshida4" or "suzuki4" (fourth order); ``iterations``: the midpoint's
+    fixed-point passes (default 2 for "midpoint", 4 for the compositions).
+    GPU-backed schemes run swrt_set_integrator's kernels (the context's
+    setting is restored on return); any other RaytracingScheme takes the same
+    arithmetic on the host.
 
     x0, k0: 1 x 2 x P.  Returns x, k: Nsteps x 2 x P (row 1 = initial state)
     and t: (Nsteps,) with t(i) = (i-1)*dt (ode_symplectic.m:2-8,23-28).
@@ -527,44 +589,48 @@ def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False):
     k[0] = k0[0]
     if Nsteps == 1 and not diagnostics:
         return x, k, t
+    kick, iters, comp = packet_method(method, iterations)
     if gpu:
-        nslots = 1 if isinstance(scheme, SpectralScheme) else 2
-        xs = np.asfortranarray(x0[0].T)  # P x 2
-        ks = np.asfortranarray(k0[0].T)
         ctx = scheme.ctx
-        if not diagnostics:
-            _, _, hx, hk = ctx.leapfrog(xs, ks, dt, Nsteps - 1, f, gH, nslots=nslots, alpha0=0.0,
-                                        dalpha=0.0, bump=scheme.bump, save_every=1)
-            x[1:] = hx
-            k[1:] = hk
-            return x, k, t
-        phys = dict(nslots=nslots, alpha=0.0, bump=scheme.bump)
-        ctx.packets_set(xs, ks)  # (starts a new history)
-        ctx.raydiag_series_reset()
-        ctx.raydiag_mark(f, gH, **phys)
-        ctx.raydiag_record(f, gH, **phys)
-        for _ in range(Nsteps - 1):
-            ctx.advance(dt, 1, f, gH, nslots=nslots, alpha0=0.0, dalpha=0.0, bump=scheme.bump, save_every=1)
-            ctx.raydiag_record(f, gH, **phys)
-        if Nsteps > 1:
-            x[1:], k[1:] = ctx.history()
-        return x, k, t, ctx.raydiag_series()
+        before = ctx.get_integrator()
+        ctx.set_integrator(kick, iters, comp)
+        try:
+            return _ode_symplectic_gpu(ctx, scheme, x, k, t, x0, k0, dt, Nsteps, f, gH, diagnostics)
+        finally:
+            ctx.set_integrator(*before)
     # generic host path (arbitrary RaytracingScheme)
+    w, _ = integrator_weights(comp)
     xc, kc = x0.copy(), k0.copy()
-
-    def gv(kk):
-        w = np.sqrt(f ** 2 + gH * (kk[:, 0:1, :] * kk[:, 0:1, :] + kk[:, 1:2, :] * kk[:, 1:2, :]))
-        return gH * kk / w
-
     for i in range(1, Nsteps):
-        x1 = xc + (dt / 2) * gv(kc)
-        x2 = x1 + dt * scheme.U(x1)
-        k2 = kc - dt * scheme.grad_U_times_k(x1, kc, 0)
-        xc = x2 + (dt / 2) * gv(k2)
-        kc = k2
+        for wj in w:
+            xc, kc = _host_stage(xc, kc, float(wj) * dt, f, gH, scheme, kick == "midpoint", iters)
         x[i] = xc[0]
         k[i] = kc[0]
     return x, k, t
+
+
+def _ode_symplectic_gpu(ctx, scheme, x, k, t, x0, k0, dt, Nsteps, f, gH, diagnostics):
+    """ode_symplectic on the device, under the context's integrator setting."""
+    nslots = 1 if isinstance(scheme, SpectralScheme) else 2
+    xs = np.asfortranarray(x0[0].T)  # P x 2
+    ks = np.asfortranarray(k0[0].T)
+    if not diagnostics:
+        _, _, hx, hk = ctx.leapfrog(xs, ks, dt, Nsteps - 1, f, gH, nslots=nslots, alpha0=0.0,
+                                    dalpha=0.0, bump=scheme.bump, save_every=1)
+        x[1:] = hx
+        k[1:] = hk
+        return x, k, t
+    phys = dict(nslots=nslots, alpha=0.0, bump=scheme.bump)
+    ctx.packets_set(xs, ks)  # (starts a new history)
+    ctx.raydiag_series_reset()
+    ctx.raydiag_mark(f, gH, **phys)
+    ctx.raydiag_record(f, gH, **phys)
+    for _ in range(Nsteps - 1):
+        ctx.advance(dt, 1, f, gH, nslots=nslots, alpha0=0.0, dalpha=0.0, bump=scheme.bump, save_every=1)
+        ctx.raydiag_record(f, gH, **phys)
+    if Nsteps > 1:
+        x[1:], k[1:] = ctx.history()
+    return x, k, t, ctx.raydiag_series()
 
 
 def ode23_packets(ctx: Context, tspan, tmax, f, Cg, nslots=2, rtol=1e-3, atol=1e-6, bump=BUMP_QG,
@@ -797,15 +863,20 @@ class PacketEnsemble:
     """
 
     def __init__(self, x, k, L, f, Cg, nx, K_d2, shear=0.0, k_scale=1.0, nlayers=1, device=0,
-                 bump=BUMP_QG, ctx: Context | None = None, shard=None, bounds=None):
+                 bump=BUMP_QG, ctx: Context | None = None, shard=None, bounds=None, method="leapfrog",
+                 iterations=None):
         """``shard`` = (rank, world): x, k are the whole ensemble (the same on
         every rank) and this rank advances its contiguous shard (SURVEY §8e);
         frames are gathered to rank 0 on the device (dist.gather_packets) and
         ode23's error norm is max-reduced over the ranks.  ``bounds``: every
         rank's [lo, hi) (dist.shard_bounds / owner_bounds; default the even
         split).  A rank's shard may be empty (the PDE owner's, with weight 0):
-        it then only takes part in the collectives."""
+        it then only takes part in the collectives.  ``method``,
+        ``iterations``: the packet step (packet_method), set on the context."""
         self.ctx = ctx if ctx is not None else Context(device)
+        # the packet step of advance / advance_intervals (packet_method; not advance_ode23's)
+        self.method = packet_method(method, iterations)
+        self.ctx.set_integrator(*self.method)
         self.L, self.f, self.Cg, self.nx = float(L), float(f), float(Cg), int(nx)
         self.gH = self.Cg ** 2
         self.K_d2, self.shear, self.k_scale = float(K_d2), float(shear), float(k_scale)
@@ -828,6 +899,11 @@ class PacketEnsemble:
         self.n = x.shape[0]
         self._k0 = k  # (this shard's initial wavevectors: begin_recycle's home)
         self._rebin = None
+
+    def set_method(self, method="leapfrog", iterations=None):
+        """The packet step of advance / advance_intervals from here on (packet_method)."""
+        self.method = packet_method(method, iterations)
+        self.ctx.set_integrator(*self.method)
 
     def set_snapshots(self, prev_qk, qk):
         """grid_U(prev_qk) -> slot 0, grid_U(qk) -> slot 1 (layer 1 if 3-D)."""

@@ -282,9 +282,11 @@ class _IntervalGroup:
     swrt_advance_intervals call — the same bits as one advance per step.  The
     PDE runs up to k steps ahead of the packets; a frame write flushes."""
 
-    def __init__(self, ctx, ens, k, nsub, integrator="leapfrog"):
+    def __init__(self, ctx, ens, k, nsub, integrator="leapfrog", packet_method=None, packet_iterations=None):
         if integrator not in ("leapfrog", "ode23"):
             raise ValueError("integrator must be 'leapfrog' or 'ode23'")
+        if packet_method is not None or packet_iterations is not None:  # (None: the ensemble's own setting stays)
+            ens.set_method(*_packet_method_args(packet_method or "leapfrog", packet_iterations, integrator))
         self.ctx, self.ens, self.nsub, self.integrator = ctx, ens, nsub, integrator
         # ode23 (the reference's own packet integrator) takes one interval per call
         self.k = 1 if integrator == "ode23" else max(1, min(int(k), 4))
@@ -468,6 +470,23 @@ def _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges):
     if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
         raise ValueError("absfreq_edges: at most 4096 classes and (no + 2) * (nbins + 2) <= 65536 cells a frame")
     return edges, int(absfreq_frac_bits)
+
+
+def _packet_method_args(packet_method, packet_iterations, integrator):
+    """The drivers' ``packet_method`` / ``packet_iterations`` checked before
+    anything runs: (method, iterations), the arguments of PacketEnsemble."""
+    from .integrate import packet_method as check
+    if integrator == "ode23" and (packet_method != "leapfrog" or packet_iterations is not None):
+        raise ValueError('packet_method / packet_iterations belong to integrator="leapfrog"')
+    check(packet_method, packet_iterations)
+    return packet_method, packet_iterations
+
+
+def _packet_method_line(method, iterations):
+    """The one extra log line of a run whose packet step is not the leapfrog step."""
+    from .integrate import packet_method as check
+    kick, it, comp = check(method, iterations)
+    return f"Packet step: {method} ({kick} kick, {it} iterations" + (f", {comp} composition)" if comp else ")")
 
 
 def _absfreq_line(edges, frac_bits):
@@ -674,7 +693,8 @@ class TwoLayerLoop:
     SPEC_SLOT = 2  # ode23 + speculate: where the next step's snapshot is packed ahead (slots 0/1: the interval's)
 
     def __init__(self, model, ens, dt, U0, cfl_fraction=0.25, packet_delay=0.0, nsub=5, packet_intervals=1,
-                 integrator="leapfrog", log=None, speculate=True, link=None):
+                 integrator="leapfrog", log=None, speculate=True, link=None, packet_method=None,
+                 packet_iterations=None):
         self.model, self.ens, self.dt, self.U0 = model, ens, dt, U0
         self.link = link
         # speculate: each step also queues the NEXT PDE step with this step's
@@ -690,7 +710,8 @@ class TwoLayerLoop:
         self.dts = []
         self.have_cur = False
         self.log = log
-        self.group = _IntervalGroup(model.ctx, ens, packet_intervals, nsub, integrator) if ens is not None else None
+        self.group = _IntervalGroup(model.ctx, ens, packet_intervals, nsub, integrator, packet_method,
+                                    packet_iterations) if ens is not None else None
         # ode23 with speculation: the speculative step's snapshot is packed into
         # slot SPEC_SLOT while the interval runs; an accepted step takes it by
         # a slot swap instead of a snapshot launch between the intervals
@@ -799,14 +820,15 @@ class ReceiverLoop:
     TwoLayerLoop does (same t, dt sequence, active steps and frame points)."""
 
     def __init__(self, link, ens, dt, packet_delay=0.0, nsub=5, packet_intervals=1, integrator="leapfrog",
-                 ahead=None):
+                 ahead=None, packet_method=None, packet_iterations=None):
         self.link, self.ens, self.dt = link, ens, dt
         self.packet_delay = packet_delay
         self.t = 0.0
         self.steps = 0
         self.dts = []
         self.have_cur = False
-        self.group = _IntervalGroup(ens.ctx, ens, packet_intervals, nsub, integrator) if ens is not None else None
+        self.group = _IntervalGroup(ens.ctx, ens, packet_intervals, nsub, integrator, packet_method,
+                                    packet_iterations) if ens is not None else None
         # The host queues step n only once the packet work of step n - ahead
         # has finished.  Unpaced, a receiver whose packets are slower than the
         # owner's PDE queues snapshots until every spare slot buffer still
@@ -880,7 +902,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                   cond_by=None, cond_edges=None, cond_frac_bits=20,
                   trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20,
                   recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20,
-                  refr_edges=None, refr_frac_bits=20, absfreq_edges=None, absfreq_frac_bits=20):
+                  refr_edges=None, refr_frac_bits=20, absfreq_edges=None, absfreq_frac_bits=20,
+                  packet_method="leapfrog", packet_iterations=None):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
     Writes ``out_dir``/packet_x.bin, packet_k.bin, packet_time.bin, pv.bin,
@@ -894,6 +917,10 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     packet launch, bounds a driver step).  ``integrator``:
     "leapfrog" (``nsub`` fused symplectic substeps per PDE interval) or
     "ode23" (the reference's own ode23 over each interval, qgsw_raytrace.m:149).
+    ``packet_method``, ``packet_iterations`` (leapfrog integrator only): the
+    packet step, "leapfrog" (the reference's, first order), "midpoint",
+    "yoshida4" or "suzuki4" (integrate.packet_method); a step other than the
+    default adds one line to run.log after the parameter block.
     ``fresh``: remove earlier output files first (default) or append to
     them as write_field.m:31 does.  ``pde``, ``owner_weight``: the sharded
     forms, as in :func:`qg2layersw_raytrace`.  ``spectrum_edges`` (nbins + 1
@@ -1031,6 +1058,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     cond_args = _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges)
     refr_args = _refr_args(refr_edges, refr_frac_bits, spectrum_edges)
     absfreq_args = _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges)
+    method_args = _packet_method_args(packet_method, packet_iterations, integrator)
     trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
     if trans_args is not None and Npackets <= 0:
         raise ValueError("the transition series needs packets")
@@ -1039,6 +1067,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
+    integ = ctx.get_integrator()  # (the ensemble sets the packet step on the context; restored at the end)
     rank, world = _dist_info()  # sharded run: packets split over the ranks
     if rank == 0:
         _fresh_outputs(out_dir, fresh)
@@ -1077,8 +1106,10 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
         log(_rings_line(ring_factors, f, Cg))
     if absfreq_args is not None:
         log(("\n" if several_rings else "") + _absfreq_line(*absfreq_args) + "\n")  # (a line of its own)
+    if method_args != ("leapfrog", None):
+        log(("\n" if several_rings and absfreq_args is None else "") + _packet_method_line(*method_args) + "\n")
     ens = PacketEnsemble(x, k, L, f, Cg, nx, K_d2, shear=0.0, k_scale=1.0, nlayers=1, bump=BUMP_QG, ctx=ctx,
-                         shard=(rank, world), bounds=bounds) \
+                         shard=(rank, world), bounds=bounds, method=method_args[0], iterations=method_args[1]) \
         if Npackets > 0 else None
 
     def snapshot(slot, which):
@@ -1184,6 +1215,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     flow_frames = frames if flow_spectrum else 0
     ctx.synchronize()
     ctx.set_timing(timing)
+    ctx.set_integrator(*integ)
     log.finish()
     log.close()
     return dict(dt=dt, Nsteps=Nsteps, steps=nrun, packet_frames=frames, t=t, U0=U0,
@@ -1202,12 +1234,14 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                         cond_by=None, cond_edges=None, cond_frac_bits=20,
                         trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20,
                         recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20,
-                        refr_edges=None, refr_frac_bits=20, absfreq_edges=None, absfreq_frac_bits=20):
+                        refr_edges=None, refr_frac_bits=20, absfreq_edges=None, absfreq_frac_bits=20,
+                        packet_method="leapfrog", packet_iterations=None):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
     interpolate's 2*nx y-period).  Same packet outputs as :func:`qgsw_raytrace`;
     pv.bin holds the initial nx x nx x 2 frame only, as in the reference.
-    ``packet_intervals``, ``integrator``, ``fresh``, ``spectrum_edges``,
+    ``packet_intervals``, ``integrator``, ``packet_method``,
+    ``packet_iterations``, ``fresh``, ``spectrum_edges``,
     ``packet_files``, ``map_cells``, ``map_frac_bits``, ``kmap_cells``,
     ``kmap_kmax``, ``kmap_frac_bits``, ``track_ids``,
     ``track_every`` (default: this driver's packet cadence, 25),
@@ -1237,6 +1271,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     cond_args = _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges)
     refr_args = _refr_args(refr_edges, refr_frac_bits, spectrum_edges)
     absfreq_args = _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges)
+    method_args = _packet_method_args(packet_method, packet_iterations, integrator)
     trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
     if trans_args is not None and Npackets <= 0:
         raise ValueError("the transition series needs packets")
@@ -1246,6 +1281,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     ctx = ctx if ctx is not None else Context(0)
     timing = getattr(ctx, "timing_every", 1)
     ctx.set_timing(0)  # (no HIP-event pair around every packet launch; restored at the end)
+    integ = ctx.get_integrator()  # (the ensemble sets the packet step on the context; restored at the end)
     rank, world = _dist_info()  # sharded run: packets split over the ranks
     if rank == 0:
         _fresh_outputs(out_dir, fresh)
@@ -1282,8 +1318,11 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
         log(_rings_line(ring_factors, f, Cg))
     if absfreq_args is not None:
         log(("\n" if several_rings else "") + _absfreq_line(*absfreq_args) + "\n")  # (a line of its own)
+    if method_args != ("leapfrog", None):
+        log(("\n" if several_rings and absfreq_args is None else "") + _packet_method_line(*method_args) + "\n")
     ens = PacketEnsemble(x, k, L, f, Cg, nx, K_d2, shear=shear, k_scale=2 * math.pi / L, nlayers=2,
-                         bump=BUMP_QG, ctx=ctx, shard=(rank, world), bounds=bounds) if Npackets > 0 else None
+                         bump=BUMP_QG, ctx=ctx, shard=(rank, world), bounds=bounds, method=method_args[0],
+                         iterations=method_args[1]) if Npackets > 0 else None
     t = 0.0
     frames = 1
     spectrum = ens is not None and spectrum_edges is not None
@@ -1375,6 +1414,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     flow_frames = frames if flow_spectrum else 0
     ctx.synchronize()
     ctx.set_timing(timing)
+    ctx.set_integrator(*integ)
     log.finish()
     log.close()
     dt, dts, step, t = loop.dt, loop.dts, loop.steps, loop.t
