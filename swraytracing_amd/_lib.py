@@ -243,6 +243,16 @@ DEBUG_TRANS_GLOBAL = 21
 DEBUG_REFR_GLOBAL = 22
 DEBUG_ABSFREQ_GLOBAL = 23
 COND_WHICH = {"zeta": 0, "sigma": 1, "D": 2}  # swrt_cond_series_begin's ``which``
+# The class-plane series' tails (PlaneLayout, swrt_packet_state.hpp): sums per
+# omega class, sums per class of the second axis, stats words.
+PLANE_TAILS = {"cond": (0, 1, 2), "trans": (0, 3, 3), "refr": (3, 1, 2), "absfreq": (3, 2, 2)}
+
+
+def plane_sums_shape(prefix, nw, n2):
+    """A frame's ``sums`` as ``<prefix>_series_get`` shapes them: flat, per
+    omega class first; trans's (ns + 2, 3), its three sums side by side."""
+    wsums, csums, _ = PLANE_TAILS[prefix]
+    return (n2 + 2, csums) if prefix == "trans" else (wsums * (nw + 2) + csums * (n2 + 2),)
 
 _lib = None
 
@@ -762,6 +772,46 @@ class Context:
     def kmap_series_reset(self):
         self._chk(self._L.swrt_kmap_series_reset(self._h), "swrt_kmap_series_reset")
 
+    # ---- what the four class-plane series (cond, trans, refr, absfreq) share ----
+    def _plane_begin(self, prefix, f, Cg, omega_edges, edges2, frac_bits, *own):
+        """swrt_<prefix>_series_begin; ``own`` goes between the two edge arrays."""
+        wedges = _f64(np.asarray(omega_edges, dtype=np.float64).ravel())
+        edges2 = _f64(np.asarray(edges2, dtype=np.float64).ravel())
+        name = f"swrt_{prefix}_series_begin"
+        self._chk(getattr(self._L, name)(self._h, float(f), float(Cg), _p(wedges), wedges.size - 1, *own,
+                                         _p(edges2), edges2.size - 1, int(frac_bits)), name)
+
+    def _plane_bins(self, prefix):
+        nw, n2 = ctypes.c_int64(0), ctypes.c_int64(0)
+        name = f"swrt_{prefix}_series_bins"
+        self._chk(getattr(self._L, name)(self._h, ctypes.byref(nw), ctypes.byref(n2)), name)
+        return int(nw.value), int(n2.value)
+
+    def _plane_get(self, prefix, first, count):
+        """Frames [first, first + count) -> counts (count, n2 + 2, nw + 2),
+        sums (count, *plane_sums_shape) and stats, all int64."""
+        if count is None:
+            count = int(getattr(self._L, f"swrt_{prefix}_series_frames")(self._h)) - first
+        nw, n2 = self._plane_bins(prefix)
+        counts = np.zeros((max(count, 0), n2 + 2, nw + 2), dtype=np.int64)
+        sums = np.zeros((max(count, 0),) + plane_sums_shape(prefix, nw, n2), dtype=np.int64)
+        stats = np.zeros((max(count, 0), PLANE_TAILS[prefix][2]), dtype=np.int64)
+        i64 = ctypes.POINTER(ctypes.c_int64)
+        name = f"swrt_{prefix}_series_get"
+        self._chk(getattr(self._L, name)(self._h, int(first), int(count), counts.ctypes.data_as(i64),
+                                         sums.ctypes.data_as(i64), stats.ctypes.data_as(i64)), name)
+        return counts, sums, stats
+
+    @staticmethod
+    def _history_alphas(alphas, count):
+        """record_history's ``alphas`` as the library takes them (None stays)."""
+        if alphas is None:
+            return None
+        alphas = np.ascontiguousarray(alphas, dtype=np.float64)
+        if alphas.shape != (int(count),):
+            raise ValueError("alphas must hold one value per frame")
+        return alphas
+
     # ---- the conditional spectrum series (swrt_cond_series_*: omega classes by a flow scalar's classes) ----
     def cond_series_begin(self, f, Cg, omega_edges, which, q_edges, frac_bits=20):
         """Open a series of (nq + 2) x (nw + 2) count planes: omega classes
@@ -769,12 +819,8 @@ class Context:
         flow scalar ``which`` (0 / "zeta", 1 / "sigma", 2 / "D") at the packets
         over ``q_edges`` (nq + 1 increasing values); the per-class omega sums
         quantised to 2^-frac_bits.  Empties the series."""
-        wedges = _f64(np.asarray(omega_edges, dtype=np.float64).ravel())
-        qedges = _f64(np.asarray(q_edges, dtype=np.float64).ravel())
         which = COND_WHICH.get(which, which) if isinstance(which, str) else which
-        self._chk(self._L.swrt_cond_series_begin(self._h, float(f), float(Cg), _p(wedges), wedges.size - 1, int(which),
-                                                 _p(qedges), qedges.size - 1, int(frac_bits)),
-                  "swrt_cond_series_begin")
+        self._plane_begin("cond", f, Cg, omega_edges, q_edges, frac_bits, int(which))
 
     def cond_series_record(self, nslots=1, alpha=0.0, bump=1e-13):
         """Append the current packets' frame in the flow of slot 0 (nslots 1)
@@ -785,10 +831,7 @@ class Context:
     def cond_series_record_history(self, first, count, nslots=1, alphas=None, bump=1e-13):
         """One frame per history frame [first, first + count), frame i with
         the snapshot blend ``alphas[i]`` (None with one snapshot: 0)."""
-        if alphas is not None:
-            alphas = np.ascontiguousarray(alphas, dtype=np.float64)
-            if alphas.shape != (int(count),):
-                raise ValueError("alphas must hold one value per frame")
+        alphas = self._history_alphas(alphas, count)
         self._chk(self._L.swrt_cond_series_record_history(self._h, int(first), int(count), int(nslots), _p(alphas),
                                                           float(bump)), "swrt_cond_series_record_history")
 
@@ -797,25 +840,14 @@ class Context:
 
     def cond_series_bins(self):
         """(nw, nq) of the open series, (0, 0) if none."""
-        nw, nq = ctypes.c_int64(0), ctypes.c_int64(0)
-        self._chk(self._L.swrt_cond_series_bins(self._h, ctypes.byref(nw), ctypes.byref(nq)), "swrt_cond_series_bins")
-        return int(nw.value), int(nq.value)
+        return self._plane_bins("cond")
 
     def cond_series_get(self, first=0, count=None):
         """Recorded frames [first, first + count) -> (counts (count, nq + 2,
         nw + 2) int64, counts[t, qc, wc]; sums (count, nq + 2) int64, the sum
         of rint(omega * 2^frac_bits) per q class; stats (count, 2) int64
         [n, rejected])."""
-        count = self.cond_series_frames() - first if count is None else count
-        nw, nq = self.cond_series_bins()
-        counts = np.zeros((max(count, 0), nq + 2, nw + 2), dtype=np.int64)
-        sums = np.zeros((max(count, 0), nq + 2), dtype=np.int64)
-        stats = np.zeros((max(count, 0), 2), dtype=np.int64)
-        i64 = ctypes.POINTER(ctypes.c_int64)
-        self._chk(self._L.swrt_cond_series_get(self._h, int(first), int(count), counts.ctypes.data_as(i64),
-                                               sums.ctypes.data_as(i64), stats.ctypes.data_as(i64)),
-                  "swrt_cond_series_get")
-        return counts, sums, stats
+        return self._plane_get("cond", first, count)
 
     def cond_series_reset(self):
         self._chk(self._L.swrt_cond_series_reset(self._h), "swrt_cond_series_reset")
@@ -827,11 +859,7 @@ class Context:
         packet's source value over ``src_edges`` (ns + 1 increasing values);
         the per-class sums quantised to 2^-frac_bits.  Empties the series and
         drops the mark."""
-        wedges = _f64(np.asarray(omega_edges, dtype=np.float64).ravel())
-        sedges = _f64(np.asarray(src_edges, dtype=np.float64).ravel())
-        self._chk(self._L.swrt_trans_series_begin(self._h, float(f), float(Cg), _p(wedges), wedges.size - 1,
-                                                  _p(sedges), sedges.size - 1, int(frac_bits)),
-                  "swrt_trans_series_begin")
+        self._plane_begin("trans", f, Cg, omega_edges, src_edges, frac_bits)
 
     def trans_series_mark(self):
         """Source of every packet := its current omega (queued; no host wait)."""
@@ -856,10 +884,7 @@ class Context:
 
     def trans_series_bins(self):
         """(nw, ns) of the open series, (0, 0) if none."""
-        nw, ns = ctypes.c_int64(0), ctypes.c_int64(0)
-        self._chk(self._L.swrt_trans_series_bins(self._h, ctypes.byref(nw), ctypes.byref(ns)),
-                  "swrt_trans_series_bins")
-        return int(nw.value), int(ns.value)
+        return self._plane_bins("trans")
 
     def trans_series_get(self, first=0, count=None):
         """Recorded frames [first, first + count) -> (counts (count, ns + 2,
@@ -867,16 +892,7 @@ class Context:
         source class the sums of rint(omega * 2^frac_bits), rint(d * ...) and
         rint(d^2 * ...) with d = omega - source; stats (count, 3) int64
         [n, rejected, mark serial])."""
-        count = self.trans_series_frames() - first if count is None else count
-        nw, ns = self.trans_series_bins()
-        counts = np.zeros((max(count, 0), ns + 2, nw + 2), dtype=np.int64)
-        sums = np.zeros((max(count, 0), ns + 2, 3), dtype=np.int64)
-        stats = np.zeros((max(count, 0), 3), dtype=np.int64)
-        i64 = ctypes.POINTER(ctypes.c_int64)
-        self._chk(self._L.swrt_trans_series_get(self._h, int(first), int(count), counts.ctypes.data_as(i64),
-                                                sums.ctypes.data_as(i64), stats.ctypes.data_as(i64)),
-                  "swrt_trans_series_get")
-        return counts, sums, stats
+        return self._plane_get("trans", first, count)
 
     def trans_series_reset(self):
         self._chk(self._L.swrt_trans_series_reset(self._h), "swrt_trans_series_reset")
@@ -888,11 +904,7 @@ class Context:
         alignment c = 2 gamma / sigma over ``a_edges`` (na + 1 increasing
         values); the per-class sums of omega-dot, omega-dot^2 and gamma
         quantised to 2^-frac_bits.  Empties the series."""
-        wedges = _f64(np.asarray(omega_edges, dtype=np.float64).ravel())
-        aedges = _f64(np.asarray(a_edges, dtype=np.float64).ravel())
-        self._chk(self._L.swrt_refr_series_begin(self._h, float(f), float(Cg), _p(wedges), wedges.size - 1,
-                                                 _p(aedges), aedges.size - 1, int(frac_bits)),
-                  "swrt_refr_series_begin")
+        self._plane_begin("refr", f, Cg, omega_edges, a_edges, frac_bits)
 
     def refr_series_record(self, nslots=1, alpha=0.0, bump=1e-13):
         """Append the current packets' frame in the flow of slot 0 (nslots 1)
@@ -903,10 +915,7 @@ class Context:
     def refr_series_record_history(self, first, count, nslots=1, alphas=None, bump=1e-13):
         """One frame per history frame [first, first + count), frame i with
         the snapshot blend ``alphas[i]`` (None with one snapshot: 0)."""
-        if alphas is not None:
-            alphas = np.ascontiguousarray(alphas, dtype=np.float64)
-            if alphas.shape != (int(count),):
-                raise ValueError("alphas must hold one value per frame")
+        alphas = self._history_alphas(alphas, count)
         self._chk(self._L.swrt_refr_series_record_history(self._h, int(first), int(count), int(nslots), _p(alphas),
                                                           float(bump)), "swrt_refr_series_record_history")
 
@@ -915,9 +924,7 @@ class Context:
 
     def refr_series_bins(self):
         """(nw, na) of the open series, (0, 0) if none."""
-        nw, na = ctypes.c_int64(0), ctypes.c_int64(0)
-        self._chk(self._L.swrt_refr_series_bins(self._h, ctypes.byref(nw), ctypes.byref(na)), "swrt_refr_series_bins")
-        return int(nw.value), int(na.value)
+        return self._plane_bins("refr")
 
     def refr_series_get(self, first=0, count=None):
         """Recorded frames [first, first + count) -> (counts (count, na + 2,
@@ -926,16 +933,7 @@ class Context:
         rint(omega-dot^2 * ...) and rint(gamma * ...), then per alignment
         class the sum of rint(omega-dot * ...); stats (count, 2) int64
         [n, rejected])."""
-        count = self.refr_series_frames() - first if count is None else count
-        nw, na = self.refr_series_bins()
-        counts = np.zeros((max(count, 0), na + 2, nw + 2), dtype=np.int64)
-        sums = np.zeros((max(count, 0), 3 * (nw + 2) + na + 2), dtype=np.int64)
-        stats = np.zeros((max(count, 0), 2), dtype=np.int64)
-        i64 = ctypes.POINTER(ctypes.c_int64)
-        self._chk(self._L.swrt_refr_series_get(self._h, int(first), int(count), counts.ctypes.data_as(i64),
-                                               sums.ctypes.data_as(i64), stats.ctypes.data_as(i64)),
-                  "swrt_refr_series_get")
-        return counts, sums, stats
+        return self._plane_get("refr", first, count)
 
     def refr_series_reset(self):
         self._chk(self._L.swrt_refr_series_reset(self._h), "swrt_refr_series_reset")
@@ -948,11 +946,7 @@ class Context:
         increasing values); the per-class sums of dOmega/dt, its square and
         the Doppler shift U.k quantised to 2^-frac_bits.  Empties the
         series."""
-        wedges = _f64(np.asarray(omega_edges, dtype=np.float64).ravel())
-        oedges = _f64(np.asarray(abs_edges, dtype=np.float64).ravel())
-        self._chk(self._L.swrt_absfreq_series_begin(self._h, float(f), float(Cg), _p(wedges), wedges.size - 1,
-                                                    _p(oedges), oedges.size - 1, int(frac_bits)),
-                  "swrt_absfreq_series_begin")
+        self._plane_begin("absfreq", f, Cg, omega_edges, abs_edges, frac_bits)
 
     def absfreq_series_record(self, slot_a=0, slot_b=-1, alpha=0.0, tau=1.0, bump=1e-13):
         """Append the current packets' frame in the flow of ``slot_a``
@@ -965,10 +959,7 @@ class Context:
     def absfreq_series_record_history(self, first, count, slot_a=0, slot_b=-1, alphas=None, tau=1.0, bump=1e-13):
         """One frame per history frame [first, first + count), frame i with
         the snapshot blend ``alphas[i]`` (None with one snapshot)."""
-        if alphas is not None:
-            alphas = np.ascontiguousarray(alphas, dtype=np.float64)
-            if alphas.shape != (int(count),):
-                raise ValueError("alphas must hold one value per frame")
+        alphas = self._history_alphas(alphas, count)
         self._chk(self._L.swrt_absfreq_series_record_history(self._h, int(first), int(count), int(slot_a), int(slot_b),
                                                              _p(alphas), float(tau), float(bump)),
                   "swrt_absfreq_series_record_history")
@@ -978,10 +969,7 @@ class Context:
 
     def absfreq_series_bins(self):
         """(nw, no) of the open series, (0, 0) if none."""
-        nw, no = ctypes.c_int64(0), ctypes.c_int64(0)
-        self._chk(self._L.swrt_absfreq_series_bins(self._h, ctypes.byref(nw), ctypes.byref(no)),
-                  "swrt_absfreq_series_bins")
-        return int(nw.value), int(no.value)
+        return self._plane_bins("absfreq")
 
     def absfreq_series_get(self, first=0, count=None):
         """Recorded frames [first, first + count) -> (counts (count, no + 2,
@@ -990,16 +978,7 @@ class Context:
         rint(Omega-dot^2 * ...) and rint(U.k * ...), then per Omega class the
         sums of rint(Omega-dot * ...) and rint(Omega-dot^2 * ...); stats
         (count, 2) int64 [n, rejected])."""
-        count = self.absfreq_series_frames() - first if count is None else count
-        nw, no = self.absfreq_series_bins()
-        counts = np.zeros((max(count, 0), no + 2, nw + 2), dtype=np.int64)
-        sums = np.zeros((max(count, 0), 3 * (nw + 2) + 2 * (no + 2)), dtype=np.int64)
-        stats = np.zeros((max(count, 0), 2), dtype=np.int64)
-        i64 = ctypes.POINTER(ctypes.c_int64)
-        self._chk(self._L.swrt_absfreq_series_get(self._h, int(first), int(count), counts.ctypes.data_as(i64),
-                                                  sums.ctypes.data_as(i64), stats.ctypes.data_as(i64)),
-                  "swrt_absfreq_series_get")
-        return counts, sums, stats
+        return self._plane_get("absfreq", first, count)
 
     def absfreq_series_reset(self):
         self._chk(self._L.swrt_absfreq_series_reset(self._h), "swrt_absfreq_series_reset")
@@ -1074,10 +1053,7 @@ class Context:
     def track_record_history(self, first, count, f, gH, nslots=1, alphas=None, bump=1e-13):
         """One track frame per history frame [first, first + count) (queued; no
         host wait), frame i with the snapshot blend ``alphas[i]`` (None: 0)."""
-        if alphas is not None:
-            alphas = np.ascontiguousarray(alphas, dtype=np.float64)
-            if alphas.shape != (int(count),):
-                raise ValueError("alphas must hold one value per frame")
+        alphas = self._history_alphas(alphas, count)
         self._chk(self._L.swrt_track_record_history(self._h, int(first), int(count), float(f), float(gH),
                                                     int(nslots), _p(alphas), float(bump)),
                   "swrt_track_record_history")
@@ -1176,10 +1152,7 @@ class Context:
         """swrt_raydiag_record_history: one series frame per history frame
         [first, first + count) (queued; no host wait), frame i with the
         snapshot blend ``alphas[i]`` (None with one snapshot: 0)."""
-        if alphas is not None:
-            alphas = np.ascontiguousarray(alphas, dtype=np.float64)
-            if alphas.shape != (int(count),):
-                raise ValueError("alphas must hold one value per frame")
+        alphas = self._history_alphas(alphas, count)
         self._chk(self._L.swrt_raydiag_record_history(self._h, int(first), int(count), float(f), float(gH),
                                                       int(nslots), _p(alphas), float(bump)),
                   "swrt_raydiag_record_history")

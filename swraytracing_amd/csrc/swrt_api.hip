@@ -1363,11 +1363,9 @@ int swrt_map_series_record_history(swrt_ctx* c, int64_t first, int64_t count) {
   if (count == 0) return SWRT_OK;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK_RC(map_reserve_zeroed(c, count));
-  for (int64_t i = 0; i < count; i += kMapHistoryChunk) {
-    const int64_t nf = std::min<int64_t>(kMapHistoryChunk, count - i), off = (first + i) * 2 * c->n;
-    HIPCHK_RC(map_general_launch(c, c->hist.a.get() + off, c->hist.b.get() + off, 2 * c->n, nf));
-  }
-  return SWRT_OK;
+  return history_chunks(c, first, count, kMapHistoryChunk, [&](int64_t, int64_t off, int64_t nf) {
+    return map_general_launch(c, c->hist.a.get() + off, c->hist.b.get() + off, 2 * c->n, nf);
+  });
   GUARD_END(c)
 }
 
@@ -1428,11 +1426,9 @@ int swrt_kmap_series_record_history(swrt_ctx* c, int64_t first, int64_t count) {
   if (count == 0) return SWRT_OK;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK_RC(kmap_reserve_zeroed(c, count));
-  for (int64_t i = 0; i < count; i += kKmapHistoryChunk) {
-    const int64_t nf = std::min<int64_t>(kKmapHistoryChunk, count - i);
-    HIPCHK_RC(kmap_launch(c, c->hist.b.get() + (first + i) * 2 * c->n, 2 * c->n, nf));
-  }
-  return SWRT_OK;
+  return history_chunks(c, first, count, kKmapHistoryChunk, [&](int64_t, int64_t off, int64_t nf) {
+    return kmap_launch(c, c->hist.b.get() + off, 2 * c->n, nf);
+  });
   GUARD_END(c)
 }
 
@@ -1622,27 +1618,10 @@ int swrt_cond_series_begin(swrt_ctx* c, double f, double Cg, const double* omega
                            const double* q_edges, int64_t nq, int frac_bits) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  HIPCHK_RC(omega_edges_check(c, omega_edges, nw));
-  HIPCHK_RC(omega_edges_check(c, q_edges, nq));
-  if ((nq + 2) * (nw + 2) > kCondMaxCells) return fail(c, SWRT_ERR_ARG, "(nq + 2) * (nw + 2) must be at most 65536");
-  if (which < 0 || which > 2) return fail(c, SWRT_ERR_ARG, "which must be 0 (zeta), 1 (sigma) or 2 (D)");
-  if (frac_bits < 0 || frac_bits > kCondMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
-  HIPCHK(c, hipSetDevice(c->device));
-  CondSeriesState& cs = c->cond;
-  HIPCHK_RC(series_release(c, cs.series));  // (waits: queued records read the old edges too)
-  cs.open = false;
-  HIPCHK(c, cs.edges.alloc(nw + nq + 2));
-  HIPCHK(c, hipMemcpyAsync(cs.edges.get(), omega_edges, sizeof(double) * (nw + 1), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(cs.edges.get() + nw + 1, q_edges, sizeof(double) * (nq + 1), hipMemcpyHostToDevice,
-                           c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  cs.nw = (int)nw;
-  cs.nq = (int)nq;
-  cs.which = which;
-  cs.frac_bits = frac_bits;
-  cs.f2 = f * f;
-  cs.Cg2 = Cg * Cg;
-  cs.open = true;
+  const char* which_err = which < 0 || which > 2 ? "which must be 0 (zeta), 1 (sigma) or 2 (D)" : nullptr;
+  HIPCHK_RC(plane_series_begin(c, c->cond, f, Cg, omega_edges, nw, q_edges, nq, frac_bits,
+                               "(nq + 2) * (nw + 2) must be at most 65536", which_err, [] {}));
+  c->cond.which = which;
   return SWRT_OK;
   GUARD_END(c)
 }
@@ -1653,7 +1632,7 @@ int swrt_cond_series_record(swrt_ctx* c, int nslots, double alpha, double bump) 
   SlotUse slot_use(c, false, track_slot_mask(nslots));
   HIPCHK_RC(cond_series_check(c, nslots));
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK_RC(cond_reserve_zeroed(c, 1));
+  HIPCHK_RC(plane_reserve_zeroed(c, c->cond, 1));
   return cond_launch(c, nslots, alpha, nullptr, bump, c->pk.cur.x.get(), c->pk.cur.k.get(), 0, 1);
   GUARD_END(c)
 }
@@ -1664,83 +1643,40 @@ int swrt_cond_series_record_history(swrt_ctx* c, int64_t first, int64_t count, i
   GUARD_BEGIN
   SlotUse slot_use(c, false, track_slot_mask(nslots));
   HIPCHK_RC(cond_series_check(c, nslots));
-  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
-  if (nslots == 2 && !alphas && count > 0) return fail(c, SWRT_ERR_ARG, "NULL buffer (alphas, two snapshots)");
-  if (count == 0) return SWRT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  CondSeriesState& cs = c->cond;
-  const double* dalphas = nullptr;
-  if (nslots == 2) {  // the frames' alphas to the device; the caller's buffer is free on return
-    if (count > cs.acap) {  // (releasing the old buffer waits for queued readers)
-      cs.acap = 0;
-      HIPCHK(c, cs.alphas.alloc(count));
-      cs.acap = count;
-    }
-    HIPCHK(c, hipMemcpyAsync(cs.alphas.get(), alphas, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    dalphas = cs.alphas.get();
-  }
-  HIPCHK_RC(cond_reserve_zeroed(c, count));
-  for (int64_t i = 0; i < count; i += kCondHistoryChunk) {
-    const int64_t nf = std::min<int64_t>(kCondHistoryChunk, count - i), off = (first + i) * 2 * c->n;
-    HIPCHK_RC(cond_launch(c, nslots, 0.0, dalphas ? dalphas + i : nullptr, bump, c->hist.a.get() + off,
-                          c->hist.b.get() + off, 2 * c->n, nf));
-  }
-  return SWRT_OK;
+  return plane_record_history(c, c->cond, first, count, nslots == 2, alphas, kCondHistoryChunk,
+                              [&](const double* dalphas, const double* x, const double* k, int64_t nf) {
+                                return cond_launch(c, nslots, 0.0, dalphas, bump, x, k, 2 * c->n, nf);
+                              });
   GUARD_END(c)
 }
 
-int64_t swrt_cond_series_frames(const swrt_ctx* c) { return c ? c->cond.series.ext.frames() : -1; }
+int64_t swrt_cond_series_frames(const swrt_ctx* c) { return plane_series_frames(c, &swrt_ctx::cond); }
 
 int swrt_cond_series_bins(const swrt_ctx* c, int64_t* nw_out, int64_t* nq_out) {
-  if (!c) return SWRT_ERR_ARG;
-  if (nw_out) *nw_out = c->cond.open ? c->cond.nw : 0;
-  if (nq_out) *nq_out = c->cond.open ? c->cond.nq : 0;
-  return SWRT_OK;
+  return plane_series_bins(c, &swrt_ctx::cond, nw_out, nq_out);
 }
 
 int swrt_cond_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
                          int64_t* stats2_out) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  return cond_series_get(c, first, count, counts_out, sums_out, stats2_out);
+  return plane_series_get(c, c->cond, first, count, counts_out, sums_out, stats2_out);
   GUARD_END(c)
 }
 
-int swrt_cond_series_reset(swrt_ctx* c) {
-  if (!c) return SWRT_ERR_ARG;
-  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
-  c->cond.series.ext.cleared();
-  return SWRT_OK;
-}
+int swrt_cond_series_reset(swrt_ctx* c) { return plane_series_reset(c, &swrt_ctx::cond); }
 
 // ---- the transition series (swrt_trans.hpp, swrt_host_diag.hpp) ----
 int swrt_trans_series_begin(swrt_ctx* c, double f, double Cg, const double* omega_edges, int64_t nw,
                             const double* src_edges, int64_t ns, int frac_bits) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  HIPCHK_RC(omega_edges_check(c, omega_edges, nw));
-  HIPCHK_RC(omega_edges_check(c, src_edges, ns));
-  if ((ns + 2) * (nw + 2) > kTransMaxCells) return fail(c, SWRT_ERR_ARG, "(ns + 2) * (nw + 2) must be at most 65536");
-  if (frac_bits < 0 || frac_bits > kTransMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
-  HIPCHK(c, hipSetDevice(c->device));
   TransSeriesState& ts = c->trans;
-  HIPCHK_RC(series_release(c, ts.series));  // (waits: queued records read the old edges too)
-  ts.open = false;
-  ts.marked = false;  // (a mark of omega belongs to the f and Cg it was taken with)
-  ts.serial = 0;
-  HIPCHK(c, ts.edges.alloc(nw + ns + 2));
-  HIPCHK(c, hipMemcpyAsync(ts.edges.get(), omega_edges, sizeof(double) * (nw + 1), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(ts.edges.get() + nw + 1, src_edges, sizeof(double) * (ns + 1), hipMemcpyHostToDevice,
-                           c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  ts.nw = (int)nw;
-  ts.ns = (int)ns;
-  ts.frac_bits = frac_bits;
-  ts.f2 = f * f;
-  ts.Cg2 = Cg * Cg;
-  ts.open = true;
-  return SWRT_OK;
+  return plane_series_begin(c, ts, f, Cg, omega_edges, nw, src_edges, ns, frac_bits,
+                            "(ns + 2) * (nw + 2) must be at most 65536", nullptr, [&ts] {
+                              ts.marked = false;  // (a mark of omega belongs to the f and Cg it was taken with)
+                              ts.serial = 0;
+                            });
   GUARD_END(c)
 }
 
@@ -1783,7 +1719,7 @@ int swrt_trans_series_record(swrt_ctx* c) {
   GUARD_BEGIN
   HIPCHK_RC(trans_series_check(c, true));
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK_RC(trans_reserve_zeroed(c, 1));
+  HIPCHK_RC(plane_reserve_zeroed(c, c->trans, 1));
   return trans_launch(c, c->pk.cur.k.get(), c->pk.cur.perm.get(), 0, 1);
   GUARD_END(c)
 }
@@ -1792,41 +1728,28 @@ int swrt_trans_series_record_history(swrt_ctx* c, int64_t first, int64_t count) 
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
   HIPCHK_RC(trans_series_check(c, true));
-  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
-  if (count == 0) return SWRT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK_RC(trans_reserve_zeroed(c, count));
-  for (int64_t i = 0; i < count; i += kTransHistoryChunk) {
-    const int64_t nf = std::min<int64_t>(kTransHistoryChunk, count - i);
-    HIPCHK_RC(trans_launch(c, c->hist.b.get() + (first + i) * 2 * c->n, nullptr, 2 * c->n, nf));
-  }
-  return SWRT_OK;
+  return plane_record_history(c, c->trans, first, count, false, nullptr, kTransHistoryChunk,
+                              [&](const double*, const double*, const double* k, int64_t nf) {
+                                return trans_launch(c, k, nullptr, 2 * c->n, nf);
+                              });
   GUARD_END(c)
 }
 
-int64_t swrt_trans_series_frames(const swrt_ctx* c) { return c ? c->trans.series.ext.frames() : -1; }
+int64_t swrt_trans_series_frames(const swrt_ctx* c) { return plane_series_frames(c, &swrt_ctx::trans); }
 
 int swrt_trans_series_bins(const swrt_ctx* c, int64_t* nw_out, int64_t* ns_out) {
-  if (!c) return SWRT_ERR_ARG;
-  if (nw_out) *nw_out = c->trans.open ? c->trans.nw : 0;
-  if (ns_out) *ns_out = c->trans.open ? c->trans.ns : 0;
-  return SWRT_OK;
+  return plane_series_bins(c, &swrt_ctx::trans, nw_out, ns_out);
 }
 
 int swrt_trans_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
                           int64_t* stats3_out) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  return trans_series_get(c, first, count, counts_out, sums_out, stats3_out);
+  return plane_series_get(c, c->trans, first, count, counts_out, sums_out, stats3_out);
   GUARD_END(c)
 }
 
-int swrt_trans_series_reset(swrt_ctx* c) {
-  if (!c) return SWRT_ERR_ARG;
-  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
-  c->trans.series.ext.cleared();
-  return SWRT_OK;
-}
+int swrt_trans_series_reset(swrt_ctx* c) { return plane_series_reset(c, &swrt_ctx::trans); }
 
 // ---- packet recycling (swrt_recycle.hpp, swrt_host_diag.hpp) ----
 int swrt_recycle_begin(swrt_ctx* c, double f, double Cg, double omega_cut, double L, uint64_t seed, int64_t index_base,
@@ -1956,26 +1879,8 @@ int swrt_refr_series_begin(swrt_ctx* c, double f, double Cg, const double* omega
                            const double* a_edges, int64_t na, int frac_bits) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  HIPCHK_RC(omega_edges_check(c, omega_edges, nw));
-  HIPCHK_RC(omega_edges_check(c, a_edges, na));
-  if ((na + 2) * (nw + 2) > kRefrMaxCells) return fail(c, SWRT_ERR_ARG, "(na + 2) * (nw + 2) must be at most 65536");
-  if (frac_bits < 0 || frac_bits > kRefrMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
-  HIPCHK(c, hipSetDevice(c->device));
-  RefrSeriesState& rs = c->refr;
-  HIPCHK_RC(series_release(c, rs.series));  // (waits: queued records read the old edges too)
-  rs.open = false;
-  HIPCHK(c, rs.edges.alloc(nw + na + 2));
-  HIPCHK(c, hipMemcpyAsync(rs.edges.get(), omega_edges, sizeof(double) * (nw + 1), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(rs.edges.get() + nw + 1, a_edges, sizeof(double) * (na + 1), hipMemcpyHostToDevice,
-                           c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rs.nw = (int)nw;
-  rs.na = (int)na;
-  rs.frac_bits = frac_bits;
-  rs.f2 = f * f;
-  rs.Cg2 = Cg * Cg;
-  rs.open = true;
-  return SWRT_OK;
+  return plane_series_begin(c, c->refr, f, Cg, omega_edges, nw, a_edges, na, frac_bits,
+                            "(na + 2) * (nw + 2) must be at most 65536", nullptr, [] {});
   GUARD_END(c)
 }
 
@@ -1985,7 +1890,7 @@ int swrt_refr_series_record(swrt_ctx* c, int nslots, double alpha, double bump) 
   SlotUse slot_use(c, false, track_slot_mask(nslots));
   HIPCHK_RC(refr_series_check(c, nslots));
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK_RC(refr_reserve_zeroed(c, 1));
+  HIPCHK_RC(plane_reserve_zeroed(c, c->refr, 1));
   return refr_launch(c, nslots, alpha, nullptr, bump, c->pk.cur.x.get(), c->pk.cur.k.get(), 0, 1);
   GUARD_END(c)
 }
@@ -1996,81 +1901,36 @@ int swrt_refr_series_record_history(swrt_ctx* c, int64_t first, int64_t count, i
   GUARD_BEGIN
   SlotUse slot_use(c, false, track_slot_mask(nslots));
   HIPCHK_RC(refr_series_check(c, nslots));
-  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
-  if (nslots == 2 && !alphas && count > 0) return fail(c, SWRT_ERR_ARG, "NULL buffer (alphas, two snapshots)");
-  if (count == 0) return SWRT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  RefrSeriesState& rs = c->refr;
-  const double* dalphas = nullptr;
-  if (nslots == 2) {  // the frames' alphas to the device; the caller's buffer is free on return
-    if (count > rs.acap) {  // (releasing the old buffer waits for queued readers)
-      rs.acap = 0;
-      HIPCHK(c, rs.alphas.alloc(count));
-      rs.acap = count;
-    }
-    HIPCHK(c, hipMemcpyAsync(rs.alphas.get(), alphas, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    dalphas = rs.alphas.get();
-  }
-  HIPCHK_RC(refr_reserve_zeroed(c, count));
-  for (int64_t i = 0; i < count; i += kRefrHistoryChunk) {
-    const int64_t nf = std::min<int64_t>(kRefrHistoryChunk, count - i), off = (first + i) * 2 * c->n;
-    HIPCHK_RC(refr_launch(c, nslots, 0.0, dalphas ? dalphas + i : nullptr, bump, c->hist.a.get() + off,
-                          c->hist.b.get() + off, 2 * c->n, nf));
-  }
-  return SWRT_OK;
+  return plane_record_history(c, c->refr, first, count, nslots == 2, alphas, kRefrHistoryChunk,
+                              [&](const double* dalphas, const double* x, const double* k, int64_t nf) {
+                                return refr_launch(c, nslots, 0.0, dalphas, bump, x, k, 2 * c->n, nf);
+                              });
   GUARD_END(c)
 }
 
-int64_t swrt_refr_series_frames(const swrt_ctx* c) { return c ? c->refr.series.ext.frames() : -1; }
+int64_t swrt_refr_series_frames(const swrt_ctx* c) { return plane_series_frames(c, &swrt_ctx::refr); }
 
 int swrt_refr_series_bins(const swrt_ctx* c, int64_t* nw_out, int64_t* na_out) {
-  if (!c) return SWRT_ERR_ARG;
-  if (nw_out) *nw_out = c->refr.open ? c->refr.nw : 0;
-  if (na_out) *na_out = c->refr.open ? c->refr.na : 0;
-  return SWRT_OK;
+  return plane_series_bins(c, &swrt_ctx::refr, nw_out, na_out);
 }
 
 int swrt_refr_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
                          int64_t* stats2_out) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  return refr_series_get(c, first, count, counts_out, sums_out, stats2_out);
+  return plane_series_get(c, c->refr, first, count, counts_out, sums_out, stats2_out);
   GUARD_END(c)
 }
 
-int swrt_refr_series_reset(swrt_ctx* c) {
-  if (!c) return SWRT_ERR_ARG;
-  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
-  c->refr.series.ext.cleared();
-  return SWRT_OK;
-}
+int swrt_refr_series_reset(swrt_ctx* c) { return plane_series_reset(c, &swrt_ctx::refr); }
 
 // ---- the absolute-frequency series (swrt_absfreq.hpp, swrt_host_diag.hpp) ----
 int swrt_absfreq_series_begin(swrt_ctx* c, double f, double Cg, const double* omega_edges, int64_t nw,
                               const double* abs_edges, int64_t no, int frac_bits) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  HIPCHK_RC(omega_edges_check(c, omega_edges, nw));
-  HIPCHK_RC(omega_edges_check(c, abs_edges, no));
-  if ((no + 2) * (nw + 2) > kAbsfreqMaxCells) return fail(c, SWRT_ERR_ARG, "(no + 2) * (nw + 2) must be at most 65536");
-  if (frac_bits < 0 || frac_bits > kAbsfreqMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
-  HIPCHK(c, hipSetDevice(c->device));
-  AbsfreqSeriesState& as = c->absfreq;
-  HIPCHK_RC(series_release(c, as.series));  // (waits: queued records read the old edges too)
-  as.open = false;
-  HIPCHK(c, as.edges.alloc(nw + no + 2));
-  HIPCHK(c, hipMemcpyAsync(as.edges.get(), omega_edges, sizeof(double) * (nw + 1), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(as.edges.get() + nw + 1, abs_edges, sizeof(double) * (no + 1), hipMemcpyHostToDevice,
-                           c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  as.nw = (int)nw;
-  as.no = (int)no;
-  as.frac_bits = frac_bits;
-  as.f2 = f * f;
-  as.Cg2 = Cg * Cg;
-  as.open = true;
-  return SWRT_OK;
+  return plane_series_begin(c, c->absfreq, f, Cg, omega_edges, nw, abs_edges, no, frac_bits,
+                            "(no + 2) * (nw + 2) must be at most 65536", nullptr, [] {});
   GUARD_END(c)
 }
 
@@ -2080,7 +1940,7 @@ int swrt_absfreq_series_record(swrt_ctx* c, int slot_a, int slot_b, double alpha
   SlotUse slot_use(c, false, absfreq_slot_mask(slot_a, slot_b));
   HIPCHK_RC(absfreq_series_check(c, slot_a, slot_b, tau));
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK_RC(absfreq_reserve_zeroed(c, 1));
+  HIPCHK_RC(plane_reserve_zeroed(c, c->absfreq, 1));
   return absfreq_launch(c, slot_a, slot_b, alpha, nullptr, tau, bump, c->pk.cur.x.get(), c->pk.cur.k.get(), 0, 1);
   GUARD_END(c)
 }
@@ -2091,55 +1951,28 @@ int swrt_absfreq_series_record_history(swrt_ctx* c, int64_t first, int64_t count
   GUARD_BEGIN
   SlotUse slot_use(c, false, absfreq_slot_mask(slot_a, slot_b));
   HIPCHK_RC(absfreq_series_check(c, slot_a, slot_b, tau));
-  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
-  if (slot_b >= 0 && !alphas && count > 0) return fail(c, SWRT_ERR_ARG, "NULL buffer (alphas, two snapshots)");
-  if (count == 0) return SWRT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  AbsfreqSeriesState& as = c->absfreq;
-  const double* dalphas = nullptr;
-  if (slot_b >= 0) {  // the frames' alphas to the device; the caller's buffer is free on return
-    if (count > as.acap) {  // (releasing the old buffer waits for queued readers)
-      as.acap = 0;
-      HIPCHK(c, as.alphas.alloc(count));
-      as.acap = count;
-    }
-    HIPCHK(c, hipMemcpyAsync(as.alphas.get(), alphas, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    dalphas = as.alphas.get();
-  }
-  HIPCHK_RC(absfreq_reserve_zeroed(c, count));
-  for (int64_t i = 0; i < count; i += kAbsfreqHistoryChunk) {
-    const int64_t nf = std::min<int64_t>(kAbsfreqHistoryChunk, count - i), off = (first + i) * 2 * c->n;
-    HIPCHK_RC(absfreq_launch(c, slot_a, slot_b, 0.0, dalphas ? dalphas + i : nullptr, tau, bump,
-                             c->hist.a.get() + off, c->hist.b.get() + off, 2 * c->n, nf));
-  }
-  return SWRT_OK;
+  return plane_record_history(c, c->absfreq, first, count, slot_b >= 0, alphas, kAbsfreqHistoryChunk,
+                              [&](const double* dalphas, const double* x, const double* k, int64_t nf) {
+                                return absfreq_launch(c, slot_a, slot_b, 0.0, dalphas, tau, bump, x, k, 2 * c->n, nf);
+                              });
   GUARD_END(c)
 }
 
-int64_t swrt_absfreq_series_frames(const swrt_ctx* c) { return c ? c->absfreq.series.ext.frames() : -1; }
+int64_t swrt_absfreq_series_frames(const swrt_ctx* c) { return plane_series_frames(c, &swrt_ctx::absfreq); }
 
 int swrt_absfreq_series_bins(const swrt_ctx* c, int64_t* nw_out, int64_t* no_out) {
-  if (!c) return SWRT_ERR_ARG;
-  if (nw_out) *nw_out = c->absfreq.open ? c->absfreq.nw : 0;
-  if (no_out) *no_out = c->absfreq.open ? c->absfreq.no : 0;
-  return SWRT_OK;
+  return plane_series_bins(c, &swrt_ctx::absfreq, nw_out, no_out);
 }
 
 int swrt_absfreq_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
                             int64_t* stats2_out) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
-  return absfreq_series_get(c, first, count, counts_out, sums_out, stats2_out);
+  return plane_series_get(c, c->absfreq, first, count, counts_out, sums_out, stats2_out);
   GUARD_END(c)
 }
 
-int swrt_absfreq_series_reset(swrt_ctx* c) {
-  if (!c) return SWRT_ERR_ARG;
-  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
-  c->absfreq.series.ext.cleared();
-  return SWRT_OK;
-}
+int swrt_absfreq_series_reset(swrt_ctx* c) { return plane_series_reset(c, &swrt_ctx::absfreq); }
 
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {
   if (!c) return SWRT_ERR_ARG;

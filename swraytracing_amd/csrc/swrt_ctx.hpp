@@ -401,83 +401,56 @@ struct FlowSpecState {
   size_t frame() const { return (size_t)3 * nshell; }
 };
 
-// the conditional spectrum series (swrt_cond_series_*, swrt_cond.hpp).
-// Buffers of its own, as the other recorders'; a frame is self-contained (its
-// n is in its stats), so swrt_packets_set with another N keeps the series.
-struct CondSeriesState {
-  bool open = false;        // swrt_cond_series_begin was called
-  int nw = 0, nq = 0;       // omega and q bins of the open series
-  int which = 0;            // 0 zeta, 1 sigma, 2 D
+// What the four class-plane series share (swrt_host_diag.hpp's plane_*
+// functions work on this part alone).  Buffers of its own, as the other
+// recorders'; a frame is self-contained (its n is in its stats), so
+// swrt_packets_set with another N keeps the series.  `lay` says what a frame
+// holds: (n2 + 2) x (nw + 2) counts in the series' first column, the sums and
+// then the stats in its second.
+struct PlaneSeriesState {
+  bool open = false;        // swrt_*_series_begin was called
+  PlaneLayout lay;          // bins of the open series; the sums and stats the series' kernels write
   int frac_bits = 0;
   double f2 = 0.0, Cg2 = 0.0;
-  DevBuf<double> edges;     // nw + 1 omega edges, then nq + 1 q edges
+  DevBuf<double> edges;     // nw + 1 omega edges, then n2 + 1 edges of the second axis
   DevBuf<double> alphas;    // record_history's alphas, one per frame of the call
   int64_t acap = 0;         // frames alphas is sized for
-  bool lds_attr = false;    // the kernels' dynamic LDS limit was raised
-  // recorded frames: (nq + 2) x (nw + 2) counts each, and their nq + 2 sums followed by [n, rejected]
-  Series<unsigned long long> series;
-  size_t frame() const { return (size_t)(nq + 2) * (nw + 2); }
-  size_t tail() const { return (size_t)nq + 4; }
+  bool lds_attr = false;    // the dynamic LDS limit of this series' kernel pair was raised
+  Series<unsigned long long> series;  // recorded frames
+  PlaneSeriesState(int wsums, int csums, int stats) { lay.wsums = wsums, lay.csums = csums, lay.stats = stats; }
 };
 
-// the transition series (swrt_trans_series_*, swrt_trans.hpp).  Buffers of its
-// own, as the other recorders'.  The mark (src, one value per packet by
-// original index) belongs to the packet set: swrt_packets_set drops it, the
-// recorded frames stay (each holds its n and its mark's serial).
-struct TransSeriesState {
-  bool open = false;        // swrt_trans_series_begin was called
+// the conditional spectrum series (swrt_cond_series_*, swrt_cond.hpp): a sum
+// per q class, then [n, rejected]
+struct CondSeriesState : PlaneSeriesState {
+  CondSeriesState() : PlaneSeriesState(0, 1, 2) {}
+  int which = 0;            // 0 zeta, 1 sigma, 2 D
+};
+
+// the transition series (swrt_trans_series_*, swrt_trans.hpp): 3 sums per
+// source class, then [n, rejected, serial].  The mark (src, one value per
+// packet by original index) belongs to the packet set: swrt_packets_set drops
+// it, the recorded frames stay (each holds its n and its mark's serial).
+struct TransSeriesState : PlaneSeriesState {
+  TransSeriesState() : PlaneSeriesState(0, 3, 3) {}
   bool marked = false;      // src holds a value for every packet of the current set
-  int nw = 0, ns = 0;       // omega and source bins of the open series
-  int frac_bits = 0;
-  double f2 = 0.0, Cg2 = 0.0;
   int64_t serial = 0;       // marks since begin
-  DevBuf<double> edges;     // nw + 1 omega edges, then ns + 1 source edges
   DevBuf<double> src;       // the source value by original packet index
   int64_t scap = 0;         // packets src is sized for
-  bool lds_attr = false;    // the kernels' dynamic LDS limit was raised
-  // recorded frames: (ns + 2) x (nw + 2) counts each, and their 3 (ns + 2) sums followed by [n, rejected, serial]
-  Series<unsigned long long> series;
-  size_t frame() const { return (size_t)(ns + 2) * (nw + 2); }
-  size_t tail() const { return (size_t)3 * (ns + 2) + 3; }
   void drop() { marked = false; }  // another packet set: the mark describes the old one
 };
 
-// the refraction series (swrt_refr_series_*, swrt_refr.hpp).  Buffers of its
-// own, as the other recorders'; a frame is self-contained (its n is in its
-// stats), so swrt_packets_set with another N keeps the series.
-struct RefrSeriesState {
-  bool open = false;        // swrt_refr_series_begin was called
-  int nw = 0, na = 0;       // omega and alignment bins of the open series
-  int frac_bits = 0;
-  double f2 = 0.0, Cg2 = 0.0;
-  DevBuf<double> edges;     // nw + 1 omega edges, then na + 1 alignment edges
-  DevBuf<double> alphas;    // record_history's alphas, one per frame of the call
-  int64_t acap = 0;         // frames alphas is sized for
-  bool lds_attr = false;    // the kernels' dynamic LDS limit was raised
-  // recorded frames: (na + 2) x (nw + 2) counts each, and their 3 (nw + 2) + (na + 2) sums followed by [n, rejected]
-  Series<unsigned long long> series;
-  size_t frame() const { return (size_t)(na + 2) * (nw + 2); }
-  size_t nsums() const { return (size_t)3 * (nw + 2) + (na + 2); }
-  size_t tail() const { return nsums() + 2; }
+// the refraction series (swrt_refr_series_*, swrt_refr.hpp): 3 sums per omega
+// class and one per alignment class, then [n, rejected]
+struct RefrSeriesState : PlaneSeriesState {
+  RefrSeriesState() : PlaneSeriesState(3, 1, 2) {}
 };
 
-// the absolute-frequency series (swrt_absfreq_series_*, swrt_absfreq.hpp).
-// Buffers of its own, laid out as the refraction series'; swrt_packets_set
-// with another N drops the frames (drop()), the edges stay.
-struct AbsfreqSeriesState {
-  bool open = false;        // swrt_absfreq_series_begin was called
-  int nw = 0, no = 0;       // omega and Omega bins of the open series
-  int frac_bits = 0;
-  double f2 = 0.0, Cg2 = 0.0;
-  DevBuf<double> edges;     // nw + 1 omega edges, then no + 1 Omega edges
-  DevBuf<double> alphas;    // record_history's alphas, one per frame of the call
-  int64_t acap = 0;         // frames alphas is sized for
-  bool lds_attr = false;    // the kernels' dynamic LDS limit was raised
-  // recorded frames: (no + 2) x (nw + 2) counts each, and their 3 (nw + 2) + 2 (no + 2) sums followed by [n, rejected]
-  Series<unsigned long long> series;
-  size_t frame() const { return (size_t)(no + 2) * (nw + 2); }
-  size_t nsums() const { return (size_t)3 * (nw + 2) + (size_t)2 * (no + 2); }
-  size_t tail() const { return nsums() + 2; }
+// the absolute-frequency series (swrt_absfreq_series_*, swrt_absfreq.hpp): 3
+// sums per omega class and 2 per Omega class, then [n, rejected].
+// swrt_packets_set with another N drops the frames (drop()), the edges stay.
+struct AbsfreqSeriesState : PlaneSeriesState {
+  AbsfreqSeriesState() : PlaneSeriesState(3, 2, 2) {}
   void drop() { series.ext.cleared(); }  // the ensemble changed size: the frames describe another one
 };
 

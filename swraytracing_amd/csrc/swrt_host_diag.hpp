@@ -3,15 +3,20 @@
 // diagnostics (swrt_raydiag.hpp), the spectrum series (swrt_diag.hpp), the
 // map series (swrt_map.hpp), the wave-vector plane series (swrt_kmap.hpp),
 // the track series (swrt_track.hpp), the flow spectrum series
-// (swrt_flowspec.hpp), the conditional spectrum series (swrt_cond.hpp), the
-// transition series (swrt_trans.hpp), the refraction series (swrt_refr.hpp)
-// and the absolute-frequency series (swrt_absfreq.hpp, last below).
+// (swrt_flowspec.hpp) and the four class-plane series: conditional spectrum
+// (swrt_cond.hpp), transition (swrt_trans.hpp), refraction (swrt_refr.hpp)
+// and absolute frequency (swrt_absfreq.hpp, last below).
 // Each appends frames to a Series of its
 // state (swrt_ctx.hpp) without a host wait: a reserve, the launches that write
-// at the series' end, a commit.  The order below (ray, spectrum, map, k-plane,
+// at the series' end, a commit.  The class-plane series share one state
+// (PlaneSeriesState) and the plane_* functions ahead of them: begin, reserve,
+// the history call, the launch's end, the read-back; what stays per series is
+// its check, its kernel arguments and its choice of the LDS or global form.
+// The order below (ray, spectrum, map, k-plane,
 // track, flow, conditional, transition, recycling, refraction, absolute
 // frequency) is the order their template kernels are first named in, hence
-// emitted in.
+// emitted in: plane_launch takes a series' kernel pair as pointers and names
+// no kernel itself.
 #pragma once
 #include <cmath>
 
@@ -164,6 +169,27 @@ int omega_frames_launch(swrt_ctx* c, bool from_k, const double* src, int64_t src
   return SWRT_OK;
 }
 
+// ---- the count series' zeroed frames (map, k-plane, class planes) ----
+// Room in s for `count` more frames of pa and pb words, zeroed on the stream:
+// the launches that fill them only add.
+int reserve_zeroed(swrt_ctx* c, Series<unsigned long long>& s, size_t pa, size_t pb, int64_t count) {
+  using word = unsigned long long;
+  HIPCHK_RC(series_reserve(c, s, pa, pb, count, map_series_min(pa * sizeof(word))));
+  HIPCHK(c, hipMemsetAsync(s.end_a(pa), 0, sizeof(word) * pa * count, c->stream));
+  HIPCHK(c, hipMemsetAsync(s.end_b(pb), 0, sizeof(word) * pb * count, c->stream));
+  return SWRT_OK;
+}
+
+// `count` history frames from `first` on in launches of at most `chunk`
+// frames: launch(i, off, nf) takes nf frames, the i-th of the call first,
+// whose x and k start `off` doubles into the history's columns.
+template <typename Launch>
+int history_chunks(swrt_ctx* c, int64_t first, int64_t count, int64_t chunk, Launch launch) {
+  for (int64_t i = 0; i < count; i += chunk)
+    HIPCHK_RC(launch(i, (first + i) * 2 * c->n, std::min<int64_t>(chunk, count - i)));
+  return SWRT_OK;
+}
+
 // ---- the map series ----
 int map_series_check(swrt_ctx* c) {
   if (!c->map.open) return fail(c, SWRT_ERR_STATE, "call swrt_map_series_begin first");
@@ -172,15 +198,8 @@ int map_series_check(swrt_ctx* c) {
   return SWRT_OK;
 }
 
-// Room for `count` more frames, zeroed on the stream (planes and stats): the
-// launches that fill them only add.
 int map_reserve_zeroed(swrt_ctx* c, int64_t count) {
-  MapSeriesState& ms = c->map;
-  const size_t fr = ms.frame();
-  HIPCHK_RC(series_reserve(c, ms.series, fr, kMapStats, count, map_series_min(fr * sizeof(unsigned long long))));
-  HIPCHK(c, hipMemsetAsync(ms.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
-  HIPCHK(c, hipMemsetAsync(ms.series.end_b(kMapStats), 0, sizeof(unsigned long long) * kMapStats * count, c->stream));
-  return SWRT_OK;
+  return reserve_zeroed(c, c->map.series, c->map.frame(), kMapStats, count);
 }
 
 MapGeom map_geom(const MapSeriesState& ms) {
@@ -250,15 +269,8 @@ int kmap_series_check(swrt_ctx* c) {
   return SWRT_OK;
 }
 
-// Room for `count` more frames, zeroed on the stream (planes and stats): the
-// launches that fill them only add.
 int kmap_reserve_zeroed(swrt_ctx* c, int64_t count) {
-  KmapSeriesState& ks = c->kmap;
-  const size_t fr = ks.frame();
-  HIPCHK_RC(series_reserve(c, ks.series, fr, kKmapStats, count, map_series_min(fr * sizeof(unsigned long long))));
-  HIPCHK(c, hipMemsetAsync(ks.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
-  HIPCHK(c, hipMemsetAsync(ks.series.end_b(kKmapStats), 0, sizeof(unsigned long long) * kKmapStats * count, c->stream));
-  return SWRT_OK;
+  return reserve_zeroed(c, c->kmap.series, c->kmap.frame(), kKmapStats, count);
 }
 
 // `count` frames from the series' end on: frame i from the packets' k at
@@ -397,23 +409,168 @@ int flow_spectrum_get(swrt_ctx* c, int64_t first, int64_t count, double* spectra
   return SWRT_OK;
 }
 
+// ---- the class-plane series: what cond, trans, refr and absfreq share ----
+// The four keep a PlaneSeriesState (swrt_ctx.hpp) and differ in their kernels,
+// their own checks and the members beside it; the frame's layout is
+// PlaneLayout's (swrt_packet_state.hpp), filled in by each state's constructor.
+static_assert(kTransMaxCells == kCondMaxCells && kRefrMaxCells == kCondMaxCells && kAbsfreqMaxCells == kCondMaxCells &&
+              kTransMaxFracBits == kCondMaxFracBits && kRefrMaxFracBits == kCondMaxFracBits &&
+              kAbsfreqMaxFracBits == kCondMaxFracBits, "plane_series_begin checks the four against one cap");
+static_assert(kCondStats == 2 && kTransSums == 3 && kTransStats == 3 && kRefrWSums == 3 && kRefrStats == 2 &&
+              kAbsfreqWSums == 3 && kAbsfreqOSums == 2 && kAbsfreqStats == 2,
+              "the states' PlaneLayout (swrt_ctx.hpp) restates what the kernels write");
+
+// swrt_*_series_begin after the guard.  cap_msg names the second axis' count;
+// own_err, when not NULL, is the failed check of the series' own argument
+// (cond's `which`); `released` runs once the old series is gone, before the
+// edges are replaced (trans forgets its mark there).
+template <typename Released>
+int plane_series_begin(swrt_ctx* c, PlaneSeriesState& ps, double f, double Cg, const double* omega_edges, int64_t nw,
+                       const double* edges2, int64_t n2, int frac_bits, const char* cap_msg, const char* own_err,
+                       Released released) {
+  HIPCHK_RC(omega_edges_check(c, omega_edges, nw));
+  HIPCHK_RC(omega_edges_check(c, edges2, n2));
+  if ((n2 + 2) * (nw + 2) > kCondMaxCells) return fail(c, SWRT_ERR_ARG, cap_msg);
+  if (own_err) return fail(c, SWRT_ERR_ARG, own_err);
+  if (frac_bits < 0 || frac_bits > kCondMaxFracBits) return fail(c, SWRT_ERR_ARG, "frac_bits must be 0..32");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(series_release(c, ps.series));  // (waits: queued records read the old edges too)
+  ps.open = false;
+  released();
+  HIPCHK(c, ps.edges.alloc(nw + n2 + 2));
+  HIPCHK(c, hipMemcpyAsync(ps.edges.get(), omega_edges, sizeof(double) * (nw + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(ps.edges.get() + nw + 1, edges2, sizeof(double) * (n2 + 1), hipMemcpyHostToDevice,
+                           c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  ps.lay.nw = (int)nw;
+  ps.lay.n2 = (int)n2;
+  ps.frac_bits = frac_bits;
+  ps.f2 = f * f;
+  ps.Cg2 = Cg * Cg;
+  ps.open = true;
+  return SWRT_OK;
+}
+
+int plane_reserve_zeroed(swrt_ctx* c, PlaneSeriesState& ps, int64_t count) {
+  return reserve_zeroed(c, ps.series, ps.lay.frame(), ps.lay.tail(), count);
+}
+
+// The frames' alphas of a two-snapshot record_history to the device (*dalphas);
+// the caller's buffer is free on return.
+int history_alphas(swrt_ctx* c, PlaneSeriesState& ps, const double* alphas, int64_t count, const double** dalphas) {
+  if (count > ps.acap) {  // (releasing the old buffer waits for queued readers)
+    ps.acap = 0;
+    HIPCHK(c, ps.alphas.alloc(count));
+    ps.acap = count;
+  }
+  HIPCHK(c, hipMemcpyAsync(ps.alphas.get(), alphas, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *dalphas = ps.alphas.get();
+  return SWRT_OK;
+}
+
+// swrt_*_series_record_history after the series' own check: `count` history
+// frames from `first` on, `chunk` a launch; two: the flow between two
+// snapshots at alphas[i].  launch(dalphas, x, k, nf) queues nf frames from the
+// history's x and k (dalphas: the first frame's alpha on the device, or NULL).
+template <typename Launch>
+int plane_record_history(swrt_ctx* c, PlaneSeriesState& ps, int64_t first, int64_t count, bool two,
+                         const double* alphas, int64_t chunk, Launch launch) {
+  HIPCHK_RC(frame_range_check(c, c->hist.ext, first, count, "history frame range out of bounds"));
+  if (two && !alphas && count > 0) return fail(c, SWRT_ERR_ARG, "NULL buffer (alphas, two snapshots)");
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const double* dalphas = nullptr;
+  if (two) HIPCHK_RC(history_alphas(c, ps, alphas, count, &dalphas));
+  HIPCHK_RC(plane_reserve_zeroed(c, ps, count));
+  return history_chunks(c, first, count, chunk, [&](int64_t i, int64_t off, int64_t nf) {
+    return launch(dalphas ? dalphas + i : nullptr, c->hist.a.get() + off, c->hist.b.get() + off, nf);
+  });
+}
+
+// How a series' kernel pair is launched: the most blocks by the launch's
+// dynamic LDS bytes, and the limit the pair asks for above 64 KB.
+struct PlaneLaunchShape {
+  int threads, max_lds_bytes;
+  int blocks, big_blocks, huge_blocks;  // up to big_bytes, above it, above huge_bytes
+  size_t big_bytes, huge_bytes;
+};
+
+// The end of the four launches: `count` frames at the series' end by the LDS
+// or the global kernel of the pair with `bytes` of dynamic LDS, committed.
+template <typename Args>
+int plane_launch(swrt_ctx* c, PlaneSeriesState& ps, void (*lds_kernel)(Args), void (*global_kernel)(Args), bool lds,
+                 size_t bytes, const PlaneLaunchShape& sh, const Args& a, int64_t count) {
+  if (bytes > ((size_t)64 << 10) && !ps.lds_attr) {  // (above 64 KB of dynamic LDS a kernel has to ask once)
+    for (auto* kernel : {lds_kernel, global_kernel})
+      HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    sh.max_lds_bytes));
+    ps.lds_attr = true;
+  }
+  const int most = bytes > sh.huge_bytes ? sh.huge_blocks : bytes > sh.big_bytes ? sh.big_blocks : sh.blocks;
+  const int nblk = (int)std::min<int64_t>(most, nblocks(c->n, sh.threads));
+  hipLaunchKernelGGL(lds ? lds_kernel : global_kernel, dim3(nblk, (unsigned)count), dim3(sh.threads), bytes, c->stream,
+                     a);
+  HIPCHK(c, hipGetLastError());
+  ps.series.ext.committed(count);
+  return SWRT_OK;
+}
+
+// Frames [first, first + count) to the host, synchronously; every output may
+// be NULL.  The sums and the stats share the series' second column.
+int plane_series_get(swrt_ctx* c, const PlaneSeriesState& ps, int64_t first, int64_t count, int64_t* counts_out,
+                     int64_t* sums_out, int64_t* stats_out) {
+  HIPCHK_RC(frame_range_check(c, ps.series.ext, first, count, "frame range out of bounds"));
+  if (count == 0) return SWRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t fr = ps.lay.frame(), tl = ps.lay.tail(), nsum = ps.lay.nsums();
+  std::vector<int64_t> tails;
+  if (counts_out)
+    HIPCHK(c, hipMemcpyAsync(counts_out, ps.series.a.get() + fr * first, sizeof(int64_t) * fr * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  if (sums_out || stats_out) {
+    tails.resize(tl * count);
+    HIPCHK(c, hipMemcpyAsync(tails.data(), ps.series.b.get() + tl * first, sizeof(int64_t) * tl * count,
+                             hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int64_t t = 0; t < count && !tails.empty(); ++t) {
+    const int64_t *row = tails.data() + tl * t, *stats = row + nsum;
+    if (sums_out) std::copy(row, stats, sums_out + nsum * t);
+    if (stats_out) std::copy(stats, row + tl, stats_out + (size_t)ps.lay.stats * t);
+  }
+  return dev_err_check(c);
+}
+
+// The bodies of swrt_*_series_frames, _bins and _reset (c may be NULL).
+template <typename S>
+int64_t plane_series_frames(const swrt_ctx* c, S swrt_ctx::*which) {
+  return c ? (c->*which).series.ext.frames() : -1;
+}
+
+template <typename S>
+int plane_series_bins(const swrt_ctx* c, S swrt_ctx::*which, int64_t* nw_out, int64_t* n2_out) {
+  if (!c) return SWRT_ERR_ARG;
+  const PlaneSeriesState& ps = c->*which;
+  if (nw_out) *nw_out = ps.open ? ps.lay.nw : 0;
+  if (n2_out) *n2_out = ps.open ? ps.lay.n2 : 0;
+  return SWRT_OK;
+}
+
+template <typename S>
+int plane_series_reset(swrt_ctx* c, S swrt_ctx::*which) {
+  if (!c) return SWRT_ERR_ARG;
+  c->s0_dirty = true;  // (as swrt_raydiag_series_reset)
+  (c->*which).series.ext.cleared();
+  return SWRT_OK;
+}
+
 // ---- the conditional spectrum series ----
 // The records' common checks: an open series, then swrt_raydiag_record's.
 int cond_series_check(swrt_ctx* c, int nslots) {
   if (!c->cond.open) return fail(c, SWRT_ERR_STATE, "call swrt_cond_series_begin first");
   HIPCHK_RC(raydiag_check(c, nslots));
   if (c->n > kCondMaxPackets) return fail(c, SWRT_ERR_ARG, "a conditional spectrum frame takes at most 2^24 packets");
-  return SWRT_OK;
-}
-
-// Room for `count` more frames, zeroed on the stream (counts, sums and
-// stats): the launches that fill them only add.
-int cond_reserve_zeroed(swrt_ctx* c, int64_t count) {
-  CondSeriesState& cs = c->cond;
-  const size_t fr = cs.frame(), tl = cs.tail();
-  HIPCHK_RC(series_reserve(c, cs.series, fr, tl, count, map_series_min(fr * sizeof(unsigned long long))));
-  HIPCHK(c, hipMemsetAsync(cs.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
-  HIPCHK(c, hipMemsetAsync(cs.series.end_b(tl), 0, sizeof(unsigned long long) * tl * count, c->stream));
   return SWRT_OK;
 }
 
@@ -439,57 +596,19 @@ int cond_launch(swrt_ctx* c, int nslots, double alpha, const double* alphas, dou
   a.f2 = cs.f2;
   a.Cg2 = cs.Cg2;
   a.wedges = cs.edges.get();
-  a.qedges = cs.edges.get() + cs.nw + 1;
-  a.nw = cs.nw;
-  a.nq = cs.nq;
+  a.qedges = cs.edges.get() + cs.lay.nw + 1;
+  a.nw = cs.lay.nw;
+  a.nq = cs.lay.n2;
   a.which = cs.which;
   a.scale = std::ldexp(1.0, cs.frac_bits);
-  a.counts = cs.series.end_a(cs.frame());
-  a.tail = cs.series.end_b(cs.tail());
-  const bool lds = !c->dbg.cond_global && cs.frame() <= (size_t)kCondLdsCells;
-  const size_t bytes = cond_lds_bytes(cs.nw, cs.nq, lds);
-  if (bytes > ((size_t)64 << 10) && !cs.lds_attr) {  // (above 64 KB of dynamic LDS a kernel has to ask once)
-    constexpr int kMost = 128 << 10;  // edges 33 KB at most, sums 32 KB at most (never both), the plane 64 KB
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&cond_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kMost));
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&cond_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kMost));
-    cs.lds_attr = true;
-  }
-  const int most = bytes > kCondBigPlaneBytes ? kCondBigPlaneBlocks : kCondBlocks;
-  const int nblk = (int)std::min<int64_t>(most, nblocks(c->n, kCondThreads));
-  hipLaunchKernelGGL(lds ? cond_kernel<true> : cond_kernel<false>, dim3(nblk, (unsigned)count), dim3(kCondThreads),
-                     bytes, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  cs.series.ext.committed(count);
-  return SWRT_OK;
-}
-
-// Frames [first, first + count) to the host, synchronously; every output may
-// be NULL.  The sums and the stats share the series' second column.
-int cond_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
-                    int64_t* stats_out) {
-  const CondSeriesState& cs = c->cond;
-  HIPCHK_RC(frame_range_check(c, cs.series.ext, first, count, "frame range out of bounds"));
-  if (count == 0) return SWRT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t fr = cs.frame(), tl = cs.tail(), nqs = (size_t)cs.nq + 2;
-  std::vector<int64_t> tails;
-  if (counts_out)
-    HIPCHK(c, hipMemcpyAsync(counts_out, cs.series.a.get() + fr * first, sizeof(int64_t) * fr * count,
-                             hipMemcpyDeviceToHost, c->stream));
-  if (sums_out || stats_out) {
-    tails.resize(tl * count);
-    HIPCHK(c, hipMemcpyAsync(tails.data(), cs.series.b.get() + tl * first, sizeof(int64_t) * tl * count,
-                             hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int64_t t = 0; t < count && !tails.empty(); ++t) {
-    const int64_t* row = tails.data() + tl * t;
-    if (sums_out) std::copy(row, row + nqs, sums_out + nqs * t);
-    if (stats_out) std::copy(row + nqs, row + tl, stats_out + (size_t)kCondStats * t);
-  }
-  return dev_err_check(c);
+  a.counts = cs.series.end_a(cs.lay.frame());
+  a.tail = cs.series.end_b(cs.lay.tail());
+  const bool lds = !c->dbg.cond_global && cs.lay.frame() <= (size_t)kCondLdsCells;
+  const size_t bytes = cond_lds_bytes(cs.lay.nw, cs.lay.n2, lds);
+  // (the limit: edges 33 KB at most, sums 32 KB at most (never both), the plane 64 KB)
+  const PlaneLaunchShape shape = {kCondThreads, 128 << 10, kCondBlocks, kCondBigPlaneBlocks, kCondBigPlaneBlocks,
+                                         kCondBigPlaneBytes, SIZE_MAX};
+  return plane_launch(c, cs, cond_kernel<true>, cond_kernel<false>, lds, bytes, shape, a, count);
 }
 
 // ---- the transition series ----
@@ -516,17 +635,6 @@ int trans_src_reserve(swrt_ctx* c) {
   return SWRT_OK;
 }
 
-// Room for `count` more frames, zeroed on the stream (counts, sums and
-// stats): the launches that fill them only add.
-int trans_reserve_zeroed(swrt_ctx* c, int64_t count) {
-  TransSeriesState& ts = c->trans;
-  const size_t fr = ts.frame(), tl = ts.tail();
-  HIPCHK_RC(series_reserve(c, ts.series, fr, tl, count, map_series_min(fr * sizeof(unsigned long long))));
-  HIPCHK(c, hipMemsetAsync(ts.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
-  HIPCHK(c, hipMemsetAsync(ts.series.end_b(tl), 0, sizeof(unsigned long long) * tl * count, c->stream));
-  return SWRT_OK;
-}
-
 // `count` frames from the series' end on: frame i from the k at k + i*stride
 // in the order `perm` names (NULL: the original order), joined to the mark.
 // The LDS kernel while the count plane fits a workgroup's LDS, the global one
@@ -542,57 +650,19 @@ int trans_launch(swrt_ctx* c, const double* k, const int* perm, int64_t stride, 
   a.f2 = ts.f2;
   a.Cg2 = ts.Cg2;
   a.wedges = ts.edges.get();
-  a.sedges = ts.edges.get() + ts.nw + 1;
-  a.nw = ts.nw;
-  a.ns = ts.ns;
+  a.sedges = ts.edges.get() + ts.lay.nw + 1;
+  a.nw = ts.lay.nw;
+  a.ns = ts.lay.n2;
   a.scale = std::ldexp(1.0, ts.frac_bits);
   a.serial = (unsigned long long)ts.serial;
-  a.counts = ts.series.end_a(ts.frame());
-  a.tail = ts.series.end_b(ts.tail());
-  const bool lds = !c->dbg.trans_global && ts.frame() <= (size_t)kCondLdsCells;
-  const size_t bytes = trans_lds_bytes(ts.nw, ts.ns, lds);
-  if (bytes > ((size_t)64 << 10) && !ts.lds_attr) {  // (above 64 KB of dynamic LDS a kernel has to ask once)
-    constexpr int kMost = 128 << 10;  // edges 33 KB at most, sums 24 KB at most, the plane 64 KB
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&trans_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kMost));
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&trans_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kMost));
-    ts.lds_attr = true;
-  }
-  const int most = bytes > kTransBigPlaneBytes ? kTransBigPlaneBlocks : kTransBlocks;
-  const int nblk = (int)std::min<int64_t>(most, nblocks(c->n, kTransThreads));
-  hipLaunchKernelGGL(lds ? trans_kernel<true> : trans_kernel<false>, dim3(nblk, (unsigned)count), dim3(kTransThreads),
-                     bytes, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  ts.series.ext.committed(count);
-  return SWRT_OK;
-}
-
-// Frames [first, first + count) to the host, synchronously; every output may
-// be NULL.  The sums and the stats share the series' second column.
-int trans_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
-                     int64_t* stats_out) {
-  const TransSeriesState& ts = c->trans;
-  HIPCHK_RC(frame_range_check(c, ts.series.ext, first, count, "frame range out of bounds"));
-  if (count == 0) return SWRT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t fr = ts.frame(), tl = ts.tail(), nsum = (size_t)kTransSums * (ts.ns + 2);
-  std::vector<int64_t> tails;
-  if (counts_out)
-    HIPCHK(c, hipMemcpyAsync(counts_out, ts.series.a.get() + fr * first, sizeof(int64_t) * fr * count,
-                             hipMemcpyDeviceToHost, c->stream));
-  if (sums_out || stats_out) {
-    tails.resize(tl * count);
-    HIPCHK(c, hipMemcpyAsync(tails.data(), ts.series.b.get() + tl * first, sizeof(int64_t) * tl * count,
-                             hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int64_t t = 0; t < count && !tails.empty(); ++t) {
-    const int64_t* row = tails.data() + tl * t;
-    if (sums_out) std::copy(row, row + nsum, sums_out + nsum * t);
-    if (stats_out) std::copy(row + nsum, row + tl, stats_out + (size_t)kTransStats * t);
-  }
-  return dev_err_check(c);
+  a.counts = ts.series.end_a(ts.lay.frame());
+  a.tail = ts.series.end_b(ts.lay.tail());
+  const bool lds = !c->dbg.trans_global && ts.lay.frame() <= (size_t)kCondLdsCells;
+  const size_t bytes = trans_lds_bytes(ts.lay.nw, ts.lay.n2, lds);
+  // (the limit: edges 33 KB at most, sums 24 KB at most, the plane 64 KB)
+  const PlaneLaunchShape shape = {kTransThreads, 128 << 10, kTransBlocks, kTransBigPlaneBlocks,
+                                         kTransBigPlaneBlocks, kTransBigPlaneBytes, SIZE_MAX};
+  return plane_launch(c, ts, trans_kernel<true>, trans_kernel<false>, lds, bytes, shape, a, count);
 }
 
 // ---- packet recycling ----
@@ -651,17 +721,6 @@ int refr_series_check(swrt_ctx* c, int nslots) {
   return SWRT_OK;
 }
 
-// Room for `count` more frames, zeroed on the stream (counts, sums and
-// stats): the launches that fill them only add.
-int refr_reserve_zeroed(swrt_ctx* c, int64_t count) {
-  RefrSeriesState& rs = c->refr;
-  const size_t fr = rs.frame(), tl = rs.tail();
-  HIPCHK_RC(series_reserve(c, rs.series, fr, tl, count, map_series_min(fr * sizeof(unsigned long long))));
-  HIPCHK(c, hipMemsetAsync(rs.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
-  HIPCHK(c, hipMemsetAsync(rs.series.end_b(tl), 0, sizeof(unsigned long long) * tl * count, c->stream));
-  return SWRT_OK;
-}
-
 // `count` frames from the series' end on: frame i from the packets at
 // x + i*stride, k + i*stride (any order) and the flow at alphas[i] (device;
 // NULL: `alpha` for every frame).  The LDS kernel for refr_lds_form's shapes,
@@ -683,56 +742,17 @@ int refr_launch(swrt_ctx* c, int nslots, double alpha, const double* alphas, dou
   a.f2 = rs.f2;
   a.Cg2 = rs.Cg2;
   a.wedges = rs.edges.get();
-  a.aedges = rs.edges.get() + rs.nw + 1;
-  a.nw = rs.nw;
-  a.na = rs.na;
+  a.aedges = rs.edges.get() + rs.lay.nw + 1;
+  a.nw = rs.lay.nw;
+  a.na = rs.lay.n2;
   a.scale = std::ldexp(1.0, rs.frac_bits);
-  a.counts = rs.series.end_a(rs.frame());
-  a.tail = rs.series.end_b(rs.tail());
-  const bool lds = !c->dbg.refr_global && refr_lds_form(rs.nw, rs.na);
-  const size_t bytes = refr_lds_bytes(rs.nw, rs.na, lds);
-  if (bytes > ((size_t)64 << 10) && !rs.lds_attr) {  // (above 64 KB of dynamic LDS a kernel has to ask once)
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&refr_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kRefrMaxLdsBytes));
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&refr_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kRefrMaxLdsBytes));
-    rs.lds_attr = true;
-  }
-  const int most = bytes > kRefrLdsFormBytes ? kRefrHugeTailBlocks
-                   : bytes > kRefrBigPlaneBytes ? kRefrBigPlaneBlocks : kRefrBlocks;
-  const int nblk = (int)std::min<int64_t>(most, nblocks(c->n, kRefrThreads));
-  hipLaunchKernelGGL(lds ? refr_kernel<true> : refr_kernel<false>, dim3(nblk, (unsigned)count), dim3(kRefrThreads),
-                     bytes, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  rs.series.ext.committed(count);
-  return SWRT_OK;
-}
-
-// Frames [first, first + count) to the host, synchronously; every output may
-// be NULL.  The sums and the stats share the series' second column.
-int refr_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
-                    int64_t* stats_out) {
-  const RefrSeriesState& rs = c->refr;
-  HIPCHK_RC(frame_range_check(c, rs.series.ext, first, count, "frame range out of bounds"));
-  if (count == 0) return SWRT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t fr = rs.frame(), tl = rs.tail(), nsum = rs.nsums();
-  std::vector<int64_t> tails;
-  if (counts_out)
-    HIPCHK(c, hipMemcpyAsync(counts_out, rs.series.a.get() + fr * first, sizeof(int64_t) * fr * count,
-                             hipMemcpyDeviceToHost, c->stream));
-  if (sums_out || stats_out) {
-    tails.resize(tl * count);
-    HIPCHK(c, hipMemcpyAsync(tails.data(), rs.series.b.get() + tl * first, sizeof(int64_t) * tl * count,
-                             hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int64_t t = 0; t < count && !tails.empty(); ++t) {
-    const int64_t* row = tails.data() + tl * t;
-    if (sums_out) std::copy(row, row + nsum, sums_out + nsum * t);
-    if (stats_out) std::copy(row + nsum, row + tl, stats_out + (size_t)kRefrStats * t);
-  }
-  return dev_err_check(c);
+  a.counts = rs.series.end_a(rs.lay.frame());
+  a.tail = rs.series.end_b(rs.lay.tail());
+  const bool lds = !c->dbg.refr_global && refr_lds_form(rs.lay.nw, rs.lay.n2);
+  const size_t bytes = refr_lds_bytes(rs.lay.nw, rs.lay.n2, lds);
+  const PlaneLaunchShape shape = {kRefrThreads, kRefrMaxLdsBytes, kRefrBlocks, kRefrBigPlaneBlocks,
+                                         kRefrHugeTailBlocks, kRefrBigPlaneBytes, kRefrLdsFormBytes};
+  return plane_launch(c, rs, refr_kernel<true>, refr_kernel<false>, lds, bytes, shape, a, count);
 }
 
 // ---- the absolute-frequency series ----
@@ -766,17 +786,6 @@ inline unsigned absfreq_slot_mask(int slot_a, int slot_b) {
   return m;
 }
 
-// Room for `count` more frames, zeroed on the stream (counts, sums and
-// stats): the launches that fill them only add.
-int absfreq_reserve_zeroed(swrt_ctx* c, int64_t count) {
-  AbsfreqSeriesState& as = c->absfreq;
-  const size_t fr = as.frame(), tl = as.tail();
-  HIPCHK_RC(series_reserve(c, as.series, fr, tl, count, map_series_min(fr * sizeof(unsigned long long))));
-  HIPCHK(c, hipMemsetAsync(as.series.end_a(fr), 0, sizeof(unsigned long long) * fr * count, c->stream));
-  HIPCHK(c, hipMemsetAsync(as.series.end_b(tl), 0, sizeof(unsigned long long) * tl * count, c->stream));
-  return SWRT_OK;
-}
-
 // `count` frames from the series' end on: frame i from the packets at
 // x + i*stride, k + i*stride (any order) and the flow of slots a and b at
 // alphas[i] (device; NULL: `alpha` for every frame).  The LDS kernel for
@@ -800,56 +809,17 @@ int absfreq_launch(swrt_ctx* c, int slot_a, int slot_b, double alpha, const doub
   a.f2 = as.f2;
   a.Cg2 = as.Cg2;
   a.wedges = as.edges.get();
-  a.oedges = as.edges.get() + as.nw + 1;
-  a.nw = as.nw;
-  a.no = as.no;
+  a.oedges = as.edges.get() + as.lay.nw + 1;
+  a.nw = as.lay.nw;
+  a.no = as.lay.n2;
   a.scale = std::ldexp(1.0, as.frac_bits);
-  a.counts = as.series.end_a(as.frame());
-  a.tail = as.series.end_b(as.tail());
-  const bool lds = !c->dbg.absfreq_global && absfreq_lds_form(as.nw, as.no);
-  const size_t bytes = absfreq_lds_bytes(as.nw, as.no, lds);
-  if (bytes > ((size_t)64 << 10) && !as.lds_attr) {  // (above 64 KB of dynamic LDS a kernel has to ask once)
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&absfreq_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kAbsfreqMaxLdsBytes));
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&absfreq_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kAbsfreqMaxLdsBytes));
-    as.lds_attr = true;
-  }
-  const int most = bytes > kAbsfreqLdsFormBytes ? kAbsfreqHugeTailBlocks
-                   : bytes > kAbsfreqBigPlaneBytes ? kAbsfreqBigPlaneBlocks : kAbsfreqBlocks;
-  const int nblk = (int)std::min<int64_t>(most, nblocks(c->n, kAbsfreqThreads));
-  hipLaunchKernelGGL(lds ? absfreq_kernel<true> : absfreq_kernel<false>, dim3(nblk, (unsigned)count),
-                     dim3(kAbsfreqThreads), bytes, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  as.series.ext.committed(count);
-  return SWRT_OK;
-}
-
-// Frames [first, first + count) to the host, synchronously; every output may
-// be NULL.  The sums and the stats share the series' second column.
-int absfreq_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
-                       int64_t* stats_out) {
-  const AbsfreqSeriesState& as = c->absfreq;
-  HIPCHK_RC(frame_range_check(c, as.series.ext, first, count, "frame range out of bounds"));
-  if (count == 0) return SWRT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t fr = as.frame(), tl = as.tail(), nsum = as.nsums();
-  std::vector<int64_t> tails;
-  if (counts_out)
-    HIPCHK(c, hipMemcpyAsync(counts_out, as.series.a.get() + fr * first, sizeof(int64_t) * fr * count,
-                             hipMemcpyDeviceToHost, c->stream));
-  if (sums_out || stats_out) {
-    tails.resize(tl * count);
-    HIPCHK(c, hipMemcpyAsync(tails.data(), as.series.b.get() + tl * first, sizeof(int64_t) * tl * count,
-                             hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int64_t t = 0; t < count && !tails.empty(); ++t) {
-    const int64_t* row = tails.data() + tl * t;
-    if (sums_out) std::copy(row, row + nsum, sums_out + nsum * t);
-    if (stats_out) std::copy(row + nsum, row + tl, stats_out + (size_t)kAbsfreqStats * t);
-  }
-  return dev_err_check(c);
+  a.counts = as.series.end_a(as.lay.frame());
+  a.tail = as.series.end_b(as.lay.tail());
+  const bool lds = !c->dbg.absfreq_global && absfreq_lds_form(as.lay.nw, as.lay.n2);
+  const size_t bytes = absfreq_lds_bytes(as.lay.nw, as.lay.n2, lds);
+  const PlaneLaunchShape shape = {kAbsfreqThreads, kAbsfreqMaxLdsBytes, kAbsfreqBlocks, kAbsfreqBigPlaneBlocks,
+                                         kAbsfreqHugeTailBlocks, kAbsfreqBigPlaneBytes, kAbsfreqLdsFormBytes};
+  return plane_launch(c, as, absfreq_kernel<true>, absfreq_kernel<false>, lds, bytes, shape, a, count);
 }
 
 }  // namespace

@@ -1,9 +1,11 @@
 // swrt_packet_state.hpp — the host's bookkeeping of the packet steppers: which
-// of the three packet sets is which (SetRing) and the host's picture of the
-// device's binning (Binning).  Plain host code, no HIP type: the library uses
+// of the three packet sets is which (SetRing), the host's picture of the
+// device's binning (Binning), the frame series' counting (SeriesExtent) and
+// the class-plane series' frame layout (PlaneLayout).  Plain host code, no HIP type: the library uses
 // it in swrt_ctx, the CPU model tests/hazard_model.cpp on its own.
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <utility>
 
@@ -112,6 +114,18 @@ class SeriesExtent {
 
  private:
   int64_t frames_ = 0, words_ = 0;
+};
+
+// A class-plane frame (the conditional, transition, refraction and
+// absolute-frequency series): a count plane over the omega classes and the
+// classes of a second axis, under- and overflow included, then a tail of
+// per-class sums followed by a few stats words.
+struct PlaneLayout {
+  int nw = 0, n2 = 0;                       // omega classes, classes of the second axis
+  int wsums = 0, csums = 0, stats = 0;      // sums per omega class, per second-axis class; stats words
+  size_t frame() const { return (size_t)(n2 + 2) * (nw + 2); }
+  size_t nsums() const { return (size_t)wsums * (nw + 2) + (size_t)csums * (n2 + 2); }
+  size_t tail() const { return nsums() + stats; }
 };
 
 }  // namespace swrt

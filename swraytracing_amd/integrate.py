@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from ._lib import Context, integrator_weights, SwrtError
+from ._lib import COND_WHICH, Context, integrator_weights, PLANE_TAILS, plane_sums_shape, SwrtError
 from .io import write_field
 from .scheme import BUMP_QG, SnapshotPairScheme, SpectralScheme, flow_planes
 
@@ -162,24 +162,31 @@ def kmap_moments(stats, frac_bits):
     return dict(n_used=n_used, mean=m1, cov=cov)
 
 
-def combine_conds(parts):
-    """The conditional spectrum series of an ensemble from its shards' series
-    (swrt_cond_series_*).  ``parts``: a sequence of (counts, sums, stats)
-    triples, one per shard, counts (T, nq + 2, nw + 2) int64, sums (T, nq + 2)
-    int64 and stats (T, 2) int64 [n, rejected]: the element-wise sum (integer,
-    exact and order-free).  A shard without packets stands as zeros."""
+def _stack_planes(parts, prefix, shapes_msg):
+    """The shards' (counts, sums, stats) of a class-plane series stacked along
+    a new first axis, their shapes checked against the series' layout
+    (_lib.PLANE_TAILS) for whatever nw and n2 the counts have."""
     parts = list(parts)
     if not parts:
         raise ValueError("no series to combine")
     shapes = {tuple(np.shape(a) for a in p) for p in parts}
     if len(shapes) != 1:
         raise ValueError("every shard must give counts, sums and stats of the same shapes")
-    counts = np.stack([np.asarray(p[0], dtype=np.int64) for p in parts])
-    sums = np.stack([np.asarray(p[1], dtype=np.int64) for p in parts])
-    stats = np.stack([np.asarray(p[2], dtype=np.int64) for p in parts])
-    if counts.ndim != 4 or sums.shape != counts.shape[:3] or stats.shape != counts.shape[:2] + (2,):
-        raise ValueError("every shard must give counts (T, nq + 2, nw + 2), sums (T, nq + 2) and stats (T, 2)")
-    return counts.sum(axis=0), sums.sum(axis=0), stats.sum(axis=0)
+    counts, sums, stats = (np.stack([np.asarray(p[i], dtype=np.int64) for p in parts]) for i in range(3))
+    if counts.ndim != 4 or stats.shape != counts.shape[:2] + (PLANE_TAILS[prefix][2],) \
+            or sums.shape != counts.shape[:2] + plane_sums_shape(prefix, counts.shape[3] - 2, counts.shape[2] - 2):
+        raise ValueError(shapes_msg)
+    return counts, sums, stats
+
+
+def combine_conds(parts):
+    """The conditional spectrum series of an ensemble from its shards' series
+    (swrt_cond_series_*).  ``parts``: a sequence of (counts, sums, stats)
+    triples, one per shard, counts (T, nq + 2, nw + 2) int64, sums (T, nq + 2)
+    int64 and stats (T, 2) int64 [n, rejected]: the element-wise sum (integer,
+    exact and order-free).  A shard without packets stands as zeros."""
+    return tuple(a.sum(axis=0) for a in _stack_planes(
+        parts, "cond", "every shard must give counts (T, nq + 2, nw + 2), sums (T, nq + 2) and stats (T, 2)"))
 
 
 def cond_spectra(counts, sums, frac_bits):
@@ -211,20 +218,9 @@ def combine_refrs(parts):
     (T, 3 (nw + 2) + (na + 2)) int64 and stats (T, 2) int64 [n, rejected]: the
     element-wise sum (integer, exact and order-free).  A shard without packets
     stands as zeros."""
-    parts = list(parts)
-    if not parts:
-        raise ValueError("no series to combine")
-    shapes = {tuple(np.shape(a) for a in p) for p in parts}
-    if len(shapes) != 1:
-        raise ValueError("every shard must give counts, sums and stats of the same shapes")
-    counts = np.stack([np.asarray(p[0], dtype=np.int64) for p in parts])
-    sums = np.stack([np.asarray(p[1], dtype=np.int64) for p in parts])
-    stats = np.stack([np.asarray(p[2], dtype=np.int64) for p in parts])
-    if counts.ndim != 4 or sums.shape != counts.shape[:2] + (3 * counts.shape[3] + counts.shape[2],) \
-            or stats.shape != counts.shape[:2] + (2,):
-        raise ValueError("every shard must give counts (T, na + 2, nw + 2), sums (T, 3 (nw + 2) + (na + 2)) "
-                         "and stats (T, 2)")
-    return counts.sum(axis=0), sums.sum(axis=0), stats.sum(axis=0)
+    return tuple(a.sum(axis=0) for a in _stack_planes(
+        parts, "refr", "every shard must give counts (T, na + 2, nw + 2), sums (T, 3 (nw + 2) + (na + 2)) "
+                       "and stats (T, 2)"))
 
 
 def alignment_edges(na):
@@ -282,20 +278,9 @@ def combine_absfreqs(parts):
     (T, 3 (nw + 2) + 2 (no + 2)) int64 and stats (T, 2) int64 [n, rejected]:
     the element-wise sum (integer, exact and order-free).  A shard without
     packets stands as zeros."""
-    parts = list(parts)
-    if not parts:
-        raise ValueError("no series to combine")
-    shapes = {tuple(np.shape(a) for a in p) for p in parts}
-    if len(shapes) != 1:
-        raise ValueError("every shard must give counts, sums and stats of the same shapes")
-    counts = np.stack([np.asarray(p[0], dtype=np.int64) for p in parts])
-    sums = np.stack([np.asarray(p[1], dtype=np.int64) for p in parts])
-    stats = np.stack([np.asarray(p[2], dtype=np.int64) for p in parts])
-    if counts.ndim != 4 or sums.shape != counts.shape[:2] + (3 * counts.shape[3] + 2 * counts.shape[2],) \
-            or stats.shape != counts.shape[:2] + (2,):
-        raise ValueError("every shard must give counts (T, no + 2, nw + 2), sums (T, 3 (nw + 2) + 2 (no + 2)) "
-                         "and stats (T, 2)")
-    return counts.sum(axis=0), sums.sum(axis=0), stats.sum(axis=0)
+    return tuple(a.sum(axis=0) for a in _stack_planes(
+        parts, "absfreq", "every shard must give counts (T, no + 2, nw + 2), sums (T, 3 (nw + 2) + 2 (no + 2)) "
+                          "and stats (T, 2)"))
 
 
 def absfreq_rates(counts, sums, stats, frac_bits):
@@ -347,17 +332,8 @@ def combine_transitions(parts):
     serial is the shards' common one.  Frames whose shards marked a different
     number of times describe different lags and are refused.  A shard without
     packets stands as zeros (its serial does not count)."""
-    parts = list(parts)
-    if not parts:
-        raise ValueError("no series to combine")
-    shapes = {tuple(np.shape(a) for a in p) for p in parts}
-    if len(shapes) != 1:
-        raise ValueError("every shard must give counts, sums and stats of the same shapes")
-    counts = np.stack([np.asarray(p[0], dtype=np.int64) for p in parts])
-    sums = np.stack([np.asarray(p[1], dtype=np.int64) for p in parts])
-    stats = np.stack([np.asarray(p[2], dtype=np.int64) for p in parts])
-    if counts.ndim != 4 or sums.shape != counts.shape[:3] + (3,) or stats.shape != counts.shape[:2] + (3,):
-        raise ValueError("every shard must give counts (T, ns + 2, nw + 2), sums (T, ns + 2, 3) and stats (T, 3)")
+    counts, sums, stats = _stack_planes(
+        parts, "trans", "every shard must give counts (T, ns + 2, nw + 2), sums (T, ns + 2, 3) and stats (T, 3)")
     holds = stats[..., 0] > 0                       # (shard, frame): the shard had packets
     serial = np.where(holds, stats[..., 2], 0).max(axis=0)
     if np.any(holds & (stats[..., 2] != serial[None, :])):
@@ -850,6 +826,223 @@ class _EmptyShard:
         pass
 
 
+class _Recorder:
+    """One drained count series of a PacketEnsemble run (the map, k-plane and
+    class-plane series): the frames recorded in all, those still on the
+    device (``pending``), the drained parts rank 0 keeps when there is no
+    ``directory`` to append them to, and the drain itself.  A series supplies
+    ``layout`` (per part of a frame its shape and dtype, the ``ndev`` parts
+    the device holds first), ``frame_bytes`` for the drain threshold,
+    ``get`` / ``reset`` into the context, ``combine`` (None: the shards' parts
+    add, one all_reduce each; else one all_gather each and combine on rank
+    0), ``append`` and, where it has one, ``geometry``."""
+
+    combine = None
+
+    def __init__(self, ens, begin, directory):
+        self.ens, self.begin, self.directory = ens, begin, directory
+        self.frames = self.pending = 0
+        self.kept = []
+
+    def host_part(self, T):
+        """The parts of the T pending frames that the host kept (none)."""
+        return ()
+
+    def geometry(self, directory):
+        pass
+
+    def record(self, call):
+        """One more frame: ``call`` queues this shard's; then the drain when
+        the device series has grown past MAP_DRAIN_BYTES."""
+        self.frames += 1
+        self.pending += 1
+        if self.ens.n > 0:
+            call()
+        if self.pending * self.frame_bytes > MAP_DRAIN_BYTES:
+            self.drain()
+
+    def drain(self):
+        """The frames on the device, combined over the shards, to the files or
+        the host list of rank 0; the device series emptied."""
+        T, ens = self.pending, self.ens
+        if T == 0:
+            return
+        if ens.n > 0:
+            part = self.get(T)
+            self.reset()
+        else:
+            part = tuple(np.zeros((T,) + shape, dtype=dt) for shape, dt in self.layout[:self.ndev])
+        self.pending = 0
+        host = self.host_part(T)
+        if ens.world > 1:
+            import torch
+            import torch.distributed as dist
+
+            from .dist import _device_for
+            dev = _device_for(dist.get_backend())
+            shards = []
+            for a in part:
+                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                if self.combine is None:
+                    dist.all_reduce(buf, op=dist.ReduceOp.SUM)  # (int64: exact, order-free)
+                    shards.append(buf.cpu().numpy())
+                else:
+                    out = [torch.empty_like(buf) for _ in range(ens.world)]
+                    dist.all_gather(out, buf)
+                    shards.append([o.cpu().numpy() for o in out])
+            if ens.rank != 0:
+                return
+            part = shards if self.combine is None else self.combine(zip(*shards))
+        part = tuple(part) + host
+        if self.directory is None:
+            self.kept.append(part)
+        else:
+            self.append(self.directory, *part)
+
+    def series(self, caller):
+        """The ensemble's frames still held (not drained into files): a
+        collective; rank 0 gets them, the others None."""
+        if self.directory is not None:
+            raise ValueError(f"{caller}: {self.begin} drains into a directory (read its files)")
+        self.drain()
+        if self.ens.rank != 0:
+            return None
+        if not self.kept:
+            return tuple(np.zeros((0,) + shape, dtype=dt) for shape, dt in self.layout)
+        return tuple(np.concatenate([p[i] for p in self.kept]) for i in range(len(self.layout)))
+
+    def write(self, caller, directory):
+        """What is left on the device and in ``kept`` to the files, then the
+        geometry file; returns the frames recorded."""
+        if self.directory is not None and os.path.abspath(self.directory) != os.path.abspath(directory):
+            raise ValueError(f"{caller}: {self.begin} drained into another directory")
+        self.drain()
+        if self.ens.rank == 0:
+            if self.directory is None:
+                for part in self.kept:
+                    self.append(directory, *part)
+                self.kept = []
+            self.geometry(directory)
+        return self.frames
+
+
+class _MapRecorder(_Recorder):
+    ndev = 2
+
+    def __init__(self, ens, directory, m, frac_bits):
+        super().__init__(ens, "begin_map", directory)
+        self.m, self.frac_bits = m, frac_bits
+        self.layout = [((4, m, m), np.int64), ((2,), np.int64)]
+        self.frame_bytes = 32 * m * m
+
+    def get(self, T):
+        return self.ens.ctx.map_series(0, T)
+
+    def reset(self):
+        self.ens.ctx.map_series_reset()
+
+    def append(self, directory, planes, stats):
+        for fr, s in zip(planes, stats):
+            for name, plane in zip(("map_n", "map_omega", "map_k", "map_l"), fr):
+                write_field(plane, os.path.join(directory, name))
+            write_field(np.array([s[0], s[1], self.m, self.frac_bits], dtype=np.float64),
+                        os.path.join(directory, "map_stats"))
+
+
+class _KmapRecorder(_Recorder):
+    ndev = 2
+
+    def __init__(self, ens, directory, K, m, frac_bits):
+        super().__init__(ens, "begin_kmap", directory)
+        self.K, self.m, self.frac_bits = K, m, frac_bits
+        self.layout = [((m, m), np.int64), ((8,), np.int64)]
+        self.frame_bytes = 8 * (m * m + 8)
+
+    def get(self, T):
+        return self.ens.ctx.kmap_series_get(0, T)
+
+    def reset(self):
+        self.ens.ctx.kmap_series_reset()
+
+    @staticmethod
+    def append(directory, planes, stats):
+        with open(os.path.join(directory, "kmap_n.bin"), "ab") as fn, \
+                open(os.path.join(directory, "kmap_stats.bin"), "ab") as fs:
+            for fr, s in zip(planes, stats):
+                fn.write(np.asarray(fr, dtype=np.int64).tobytes(order="F"))  # (cell (i, j) at i + m*j)
+                fs.write(np.asarray(s, dtype=np.int64).tobytes())
+
+    def geometry(self, directory):
+        with open(os.path.join(directory, "kmap_geom.bin"), "wb") as fh:
+            fh.write(np.array([self.K, self.m, self.frac_bits], dtype=np.float64).tobytes())
+
+
+class _PlaneRecorder(_Recorder):
+    """The four class-plane series: ``prefix`` names the context's calls and
+    the files, ``head`` leads <prefix>_geom.bin before the second axis' edges
+    and the omega edges."""
+    ndev = 3
+    files = ("hist", "sums", "stats")
+
+    def __init__(self, ens, directory, prefix, wedges, edges2, frac_bits, head, combine):
+        super().__init__(ens, "begin_" + prefix, directory)
+        self.prefix, self.wedges, self.edges2, self.combine = prefix, wedges, edges2, combine
+        self.head = [edges2.size - 1, wedges.size - 1, frac_bits] if head is None else head
+        nw, n2 = wedges.size - 1, edges2.size - 1
+        self.layout = [((n2 + 2, nw + 2), np.int64), (plane_sums_shape(prefix, nw, n2), np.int64),
+                       ((PLANE_TAILS[prefix][2],), np.int64)]
+        self.frame_bytes = 8 * sum(int(np.prod(shape)) for shape, _ in self.layout)
+
+    def get(self, T):
+        return getattr(self.ens.ctx, self.prefix + "_series_get")(0, T)
+
+    def reset(self):
+        getattr(self.ens.ctx, self.prefix + "_series_reset")()
+
+    def append(self, directory, *part):
+        # (hist: the cell (class of the second axis c, omega class wc) at c*(nw + 2) + wc)
+        for name, frames, (_, dt) in zip(self.files, part, self.layout):
+            with open(os.path.join(directory, f"{self.prefix}_{name}.bin"), "ab") as fh:
+                for fr in frames:
+                    fh.write(np.ascontiguousarray(fr, dtype=dt).tobytes())
+
+    def geometry(self, directory):
+        with open(os.path.join(directory, self.prefix + "_geom.bin"), "wb") as fh:
+            head = np.array(self.head, dtype=np.float64)
+            fh.write(np.concatenate([head, self.edges2, self.wedges]).tobytes())
+
+
+class _TransRecorder(_PlaneRecorder):
+    """The transition series keeps [t, t_mark] of every frame on the host."""
+    files = _PlaneRecorder.files + ("time",)
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.layout.append(((2,), np.float64))
+        self.times, self.t_mark = [], None
+
+    def host_part(self, T):
+        times, self.times = np.array(self.times, dtype=np.float64).reshape(T, 2), []
+        return (times,)
+
+
+def _plane_args(omega_edges, edges2, frac_bits, axis, series, frame, n2):
+    """begin_cond / _refr / _absfreq / _trans's checks of the two edge arrays,
+    frac_bits and the cell cap; ``axis``, ``series``, ``frame`` and ``n2``
+    are the series' words in the messages."""
+    wedges = np.array(omega_edges, dtype=np.float64).ravel()
+    edges2 = np.array(edges2, dtype=np.float64).ravel()
+    for name, e in (("omega", wedges), (axis, edges2)):
+        if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+            raise ValueError(f"the {name} edges must be at least two finite increasing values")
+    frac_bits = int(frac_bits)
+    if not 0 <= frac_bits <= 32:
+        raise ValueError(f"{series} frac_bits must be 0..32")
+    if (edges2.size + 1) * (wedges.size + 1) > 65536:
+        raise ValueError(f"{frame} frame holds at most 65536 cells, ({n2} + 2) * (nw + 2)")
+    return wedges, edges2, frac_bits
+
+
 class PacketEnsemble:
     """Device-resident packets advanced through a sequence of background
     snapshots — the packet branch of qgsw_raytrace.m:140-163 /
@@ -898,6 +1091,7 @@ class PacketEnsemble:
         self.ctx.packets_set(x, k)
         self.n = x.shape[0]
         self._k0 = k  # (this shard's initial wavevectors: begin_recycle's home)
+        self._recorders = {}  # the drained count series by name (begin_map ... begin_trans)
         self._rebin = None
 
     def set_method(self, method="leapfrog", iterations=None):
@@ -1033,6 +1227,19 @@ class PacketEnsemble:
             write_field(self._spec_edges, os.path.join(directory, "omega_edges"))
         return self._spec_frames
 
+    def _recorder(self, name, caller):
+        """The recorder begin_<name> opened, for the public method ``caller``."""
+        rec = self._recorders.get(name)
+        if rec is None:
+            raise SwrtError(f"{caller}: call begin_{name} first")
+        return rec
+
+    def _record_blended(self, name, alpha):
+        """record_cond / record_refr: slot 0 alone, or slots 0 and 1 at ``alpha``."""
+        record = getattr(self.ctx, name + "_series_record")
+        blend = dict(nslots=1) if alpha is None else dict(nslots=2, alpha=alpha)
+        self._recorder(name, "record_" + name).record(lambda: record(bump=self.bump, **blend))
+
     def begin_map(self, m, frac_bits=20, directory=None):
         """Open the series of m x m packet density and wave-energy maps of
         this run over the ensemble's periodic square (swrt_map_series_begin
@@ -1044,7 +1251,7 @@ class PacketEnsemble:
             raise ValueError("map cells must be 1..4096")
         if not 0 <= frac_bits <= 32:
             raise ValueError("map frac_bits must be 0..32")
-        self._map = dict(m=m, frac_bits=frac_bits, directory=directory, frames=0, pending=0, kept=[])
+        self._recorders["map"] = _MapRecorder(self, directory, m, frac_bits)
         if self.n > 0:
             self.ctx.map_series_begin(self.L, m, self.f, self.Cg, frac_bits)
 
@@ -1054,55 +1261,7 @@ class PacketEnsemble:
         nothing.  When the device series holds more than 256 MB it is drained
         (get, combine, append, reset): a collective when sharded, at the same
         frame on every rank."""
-        st = getattr(self, "_map", None)
-        if st is None:
-            raise SwrtError("record_map: call begin_map first")
-        st["frames"] += 1
-        st["pending"] += 1
-        if self.n > 0:
-            self.ctx.map_series_record()
-        if st["pending"] * 32 * st["m"] * st["m"] > MAP_DRAIN_BYTES:
-            self._drain_maps()
-
-    def _drain_maps(self):
-        """The frames on the device, combined over the shards, to the files or
-        the host list of rank 0; the device series emptied."""
-        st = self._map
-        T, m = st["pending"], st["m"]
-        if T == 0:
-            return
-        if self.n > 0:
-            planes, stats = self.ctx.map_series(0, T)
-            self.ctx.map_series_reset()
-        else:
-            planes, stats = np.zeros((T, 4, m, m), dtype=np.int64), np.zeros((T, 2), dtype=np.int64)
-        st["pending"] = 0
-        if self.world > 1:
-            import torch
-            import torch.distributed as dist
-
-            from .dist import _device_for
-            dev = _device_for(dist.get_backend())
-            summed = []
-            for a in (planes, stats):
-                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                dist.all_reduce(buf, op=dist.ReduceOp.SUM)  # (int64: exact, order-free)
-                summed.append(buf.cpu().numpy())
-            if self.rank != 0:
-                return
-            planes, stats = summed
-        if st["directory"] is None:
-            st["kept"].append((planes, stats))
-        else:
-            self._append_maps(st["directory"], planes, stats)
-
-    def _append_maps(self, directory, planes, stats):
-        st = self._map
-        for fr, s in zip(planes, stats):
-            for name, plane in zip(("map_n", "map_omega", "map_k", "map_l"), fr):
-                write_field(plane, os.path.join(directory, name))
-            write_field(np.array([s[0], s[1], st["m"], st["frac_bits"]], dtype=np.float64),
-                        os.path.join(directory, "map_stats"))
+        self._recorder("map", "record_map").record(self.ctx.map_series_record)
 
     def write_maps(self, directory):
         """The run's map series as write_field files (read_field(name, m, m, 1,
@@ -1112,17 +1271,7 @@ class PacketEnsemble:
         first index x — and map_stats.bin, [n, rejected, m, frac_bits] per
         frame.  Sharded: a collective; rank 0 writes.  Returns the frames
         recorded."""
-        st = getattr(self, "_map", None)
-        if st is None:
-            raise SwrtError("write_maps: call begin_map first")
-        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
-            raise ValueError("write_maps: begin_map drained into another directory")
-        self._drain_maps()
-        if st["directory"] is None:
-            for planes, stats in st["kept"]:
-                self._append_maps(directory, planes, stats)
-            st["kept"] = []
-        return st["frames"]
+        return self._recorder("map", "write_maps").write("write_maps", directory)
 
     def begin_kmap(self, K, m, frac_bits=16, directory=None):
         """Open the series of m x m count planes over [-K, K) x [-K, K) of the
@@ -1137,7 +1286,7 @@ class PacketEnsemble:
             raise ValueError("k-plane cells must be 1..4096")
         if not 0 <= frac_bits <= 32:
             raise ValueError("k-plane frac_bits must be 0..32")
-        self._kmap = dict(K=K, m=m, frac_bits=frac_bits, directory=directory, frames=0, pending=0, kept=[])
+        self._recorders["kmap"] = _KmapRecorder(self, directory, K, m, frac_bits)
         if self.n > 0:
             self.ctx.kmap_series_begin(K, m, frac_bits)
 
@@ -1147,73 +1296,14 @@ class PacketEnsemble:
         nothing.  When the device series holds more than 256 MB it is drained
         (get, combine, append, reset): a collective when sharded, at the same
         frame on every rank."""
-        st = getattr(self, "_kmap", None)
-        if st is None:
-            raise SwrtError("record_kmap: call begin_kmap first")
-        st["frames"] += 1
-        st["pending"] += 1
-        if self.n > 0:
-            self.ctx.kmap_series_record()
-        if st["pending"] * 8 * (st["m"] * st["m"] + 8) > MAP_DRAIN_BYTES:
-            self._drain_kmaps()
-
-    def _drain_kmaps(self):
-        """The frames on the device, summed over the shards, to the files or
-        the host list of rank 0; the device series emptied."""
-        st = self._kmap
-        T, m = st["pending"], st["m"]
-        if T == 0:
-            return
-        if self.n > 0:
-            planes, stats = self.ctx.kmap_series_get(0, T)
-            self.ctx.kmap_series_reset()
-        else:
-            planes, stats = np.zeros((T, m, m), dtype=np.int64), np.zeros((T, 8), dtype=np.int64)
-        st["pending"] = 0
-        if self.world > 1:
-            import torch
-            import torch.distributed as dist
-
-            from .dist import _device_for
-            dev = _device_for(dist.get_backend())
-            summed = []
-            for a in (planes, stats):
-                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                dist.all_reduce(buf, op=dist.ReduceOp.SUM)  # (int64: exact, order-free)
-                summed.append(buf.cpu().numpy())
-            if self.rank != 0:
-                return
-            planes, stats = summed
-        if st["directory"] is None:
-            st["kept"].append((planes, stats))
-        else:
-            self._append_kmaps(st["directory"], planes, stats)
-
-    @staticmethod
-    def _append_kmaps(directory, planes, stats):
-        with open(os.path.join(directory, "kmap_n.bin"), "ab") as fn, \
-                open(os.path.join(directory, "kmap_stats.bin"), "ab") as fs:
-            for fr, s in zip(planes, stats):
-                fn.write(np.asarray(fr, dtype=np.int64).tobytes(order="F"))  # (cell (i, j) at i + m*j)
-                fs.write(np.asarray(s, dtype=np.int64).tobytes())
+        self._recorder("kmap", "record_kmap").record(self.ctx.kmap_series_record)
 
     def kmap_series(self):
         """(planes (T, m, m) int64, stats (T, 8) int64) of the ensemble's
         frames still held (not yet drained into files): planes[t, i, j] the
         cell with k index i and l index j.  Sharded: a collective; rank 0 gets
         the sum of the shards' frames, the others None."""
-        st = getattr(self, "_kmap", None)
-        if st is None:
-            raise SwrtError("kmap_series: call begin_kmap first")
-        if st["directory"] is not None:
-            raise ValueError("kmap_series: begin_kmap drains into a directory (read its files)")
-        self._drain_kmaps()
-        if self.rank != 0:
-            return None
-        m = st["m"]
-        if not st["kept"]:
-            return np.zeros((0, m, m), dtype=np.int64), np.zeros((0, 8), dtype=np.int64)
-        return (np.concatenate([p for p, _ in st["kept"]]), np.concatenate([s for _, s in st["kept"]]))
+        return self._recorder("kmap", "kmap_series").series("kmap_series")
 
     def write_kmaps(self, directory):
         """The run's k-plane series as raw native-endian files: kmap_n.bin
@@ -1221,20 +1311,7 @@ class PacketEnsemble:
         k), kmap_stats.bin (8 int64 per frame: n, rejected, outside and the
         five moment sums) and kmap_geom.bin (three doubles [K, m, frac_bits]).
         Sharded: a collective; rank 0 writes.  Returns the frames recorded."""
-        st = getattr(self, "_kmap", None)
-        if st is None:
-            raise SwrtError("write_kmaps: call begin_kmap first")
-        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
-            raise ValueError("write_kmaps: begin_kmap drained into another directory")
-        self._drain_kmaps()
-        if self.rank == 0:
-            if st["directory"] is None:
-                for planes, stats in st["kept"]:
-                    self._append_kmaps(directory, planes, stats)
-                st["kept"] = []
-            with open(os.path.join(directory, "kmap_geom.bin"), "wb") as fh:
-                fh.write(np.array([st["K"], st["m"], st["frac_bits"]], dtype=np.float64).tobytes())
-        return st["frames"]
+        return self._recorder("kmap", "write_kmaps").write("write_kmaps", directory)
 
     def begin_cond(self, omega_edges, which, q_edges, frac_bits=20, directory=None):
         """Open the conditional spectrum series of this run
@@ -1243,21 +1320,13 @@ class PacketEnsemble:
         "sigma" or "D") at the packets over ``q_edges``.  ``directory``: where
         record_cond drains the device series when it grows large (default: the
         drained frames wait in host memory for write_conds)."""
-        from ._lib import COND_WHICH
         if which not in COND_WHICH:
             raise ValueError('the conditioning scalar must be "zeta", "sigma" or "D"')
-        wedges = np.array(omega_edges, dtype=np.float64).ravel()
-        qedges = np.array(q_edges, dtype=np.float64).ravel()
-        for name, e in (("omega", wedges), ("q", qedges)):
-            if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
-                raise ValueError(f"the {name} edges must be at least two finite increasing values")
-        frac_bits = int(frac_bits)
-        if not 0 <= frac_bits <= 32:
-            raise ValueError("conditional spectrum frac_bits must be 0..32")
-        if (qedges.size + 1) * (wedges.size + 1) > 65536:
-            raise ValueError("a conditional spectrum frame holds at most 65536 cells, (nq + 2) * (nw + 2)")
-        self._cond = dict(which=COND_WHICH[which], wedges=wedges, qedges=qedges, frac_bits=frac_bits,
-                          directory=directory, frames=0, pending=0, kept=[])
+        wedges, qedges, frac_bits = _plane_args(omega_edges, q_edges, frac_bits, "q", "conditional spectrum",
+                                                "a conditional spectrum", "nq")
+        head = [COND_WHICH[which], qedges.size - 1, wedges.size - 1, frac_bits]
+        self._recorders["cond"] = _PlaneRecorder(self, directory, "cond", wedges, qedges, frac_bits, head,
+                                                 combine_conds)
         if self.n > 0:
             self.ctx.cond_series_begin(self.f, self.Cg, wedges, COND_WHICH[which], qedges, frac_bits)
 
@@ -1268,82 +1337,14 @@ class PacketEnsemble:
         shard records nothing.  When the device series holds more than 256 MB
         it is drained (get, combine, append, reset): a collective when
         sharded, at the same frame on every rank."""
-        st = getattr(self, "_cond", None)
-        if st is None:
-            raise SwrtError("record_cond: call begin_cond first")
-        st["frames"] += 1
-        st["pending"] += 1
-        if self.n > 0:
-            if alpha is None:
-                self.ctx.cond_series_record(nslots=1, bump=self.bump)
-            else:
-                self.ctx.cond_series_record(nslots=2, alpha=alpha, bump=self.bump)
-        nqs, nws = st["qedges"].size + 1, st["wedges"].size + 1
-        if st["pending"] * 8 * (nqs * nws + nqs + 2) > MAP_DRAIN_BYTES:
-            self._drain_conds()
-
-    def _drain_conds(self):
-        """The frames on the device, summed over the shards, to the files or
-        the host list of rank 0; the device series emptied."""
-        st = self._cond
-        T, nqs, nws = st["pending"], st["qedges"].size + 1, st["wedges"].size + 1
-        if T == 0:
-            return
-        if self.n > 0:
-            part = self.ctx.cond_series_get(0, T)
-            self.ctx.cond_series_reset()
-        else:
-            part = (np.zeros((T, nqs, nws), dtype=np.int64), np.zeros((T, nqs), dtype=np.int64),
-                    np.zeros((T, 2), dtype=np.int64))
-        st["pending"] = 0
-        if self.world > 1:
-            import torch
-            import torch.distributed as dist
-
-            from .dist import _device_for
-            dev = _device_for(dist.get_backend())
-            gathered = []
-            for a in part:
-                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                out = [torch.empty_like(buf) for _ in range(self.world)]
-                dist.all_gather(out, buf)
-                gathered.append([o.cpu().numpy() for o in out])
-            if self.rank != 0:
-                return
-            part = combine_conds(zip(*gathered))
-        if st["directory"] is None:
-            st["kept"].append(part)
-        else:
-            self._append_conds(st["directory"], *part)
-
-    @staticmethod
-    def _append_conds(directory, counts, sums, stats):
-        with open(os.path.join(directory, "cond_hist.bin"), "ab") as fc, \
-                open(os.path.join(directory, "cond_sums.bin"), "ab") as fs, \
-                open(os.path.join(directory, "cond_stats.bin"), "ab") as ft:
-            for fr, s, t in zip(counts, sums, stats):
-                fc.write(np.ascontiguousarray(fr, dtype=np.int64).tobytes())  # (cell (qc, wc) at qc*(nw + 2) + wc)
-                fs.write(np.ascontiguousarray(s, dtype=np.int64).tobytes())
-                ft.write(np.ascontiguousarray(t, dtype=np.int64).tobytes())
+        self._record_blended("cond", alpha)
 
     def cond_series(self):
         """(counts (T, nq + 2, nw + 2), sums (T, nq + 2), stats (T, 2)), all
         int64, of the ensemble's frames still held (not yet drained into
         files).  Sharded: a collective; rank 0 gets combine_conds() of the
         shards' frames, the others None."""
-        st = getattr(self, "_cond", None)
-        if st is None:
-            raise SwrtError("cond_series: call begin_cond first")
-        if st["directory"] is not None:
-            raise ValueError("cond_series: begin_cond drains into a directory (read its files)")
-        self._drain_conds()
-        if self.rank != 0:
-            return None
-        nqs, nws = st["qedges"].size + 1, st["wedges"].size + 1
-        if not st["kept"]:
-            return (np.zeros((0, nqs, nws), dtype=np.int64), np.zeros((0, nqs), dtype=np.int64),
-                    np.zeros((0, 2), dtype=np.int64))
-        return tuple(np.concatenate([p[i] for p in st["kept"]]) for i in range(3))
+        return self._recorder("cond", "cond_series").series("cond_series")
 
     def write_conds(self, directory):
         """The run's conditional spectrum series as raw native-endian files:
@@ -1353,22 +1354,7 @@ class PacketEnsemble:
         (doubles [which, nq, nw, frac_bits], the nq + 1 q edges, the nw + 1
         omega edges).  Sharded: a collective; rank 0 writes.  Returns the
         frames recorded."""
-        st = getattr(self, "_cond", None)
-        if st is None:
-            raise SwrtError("write_conds: call begin_cond first")
-        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
-            raise ValueError("write_conds: begin_cond drained into another directory")
-        self._drain_conds()
-        if self.rank == 0:
-            if st["directory"] is None:
-                for part in st["kept"]:
-                    self._append_conds(directory, *part)
-                st["kept"] = []
-            with open(os.path.join(directory, "cond_geom.bin"), "wb") as fh:
-                head = np.array([st["which"], st["qedges"].size - 1, st["wedges"].size - 1, st["frac_bits"]],
-                                dtype=np.float64)
-                fh.write(np.concatenate([head, st["qedges"], st["wedges"]]).tobytes())
-        return st["frames"]
+        return self._recorder("cond", "write_conds").write("write_conds", directory)
 
     def begin_refr(self, omega_edges, a_edges, frac_bits=20, directory=None):
         """Open the refraction series of this run (swrt_refr_series_begin with
@@ -1377,18 +1363,10 @@ class PacketEnsemble:
         ``directory``: where record_refr drains the device series when it
         grows large (default: the drained frames wait in host memory for
         write_refrs)."""
-        wedges = np.array(omega_edges, dtype=np.float64).ravel()
-        aedges = np.array(a_edges, dtype=np.float64).ravel()
-        for name, e in (("omega", wedges), ("alignment", aedges)):
-            if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
-                raise ValueError(f"the {name} edges must be at least two finite increasing values")
-        frac_bits = int(frac_bits)
-        if not 0 <= frac_bits <= 32:
-            raise ValueError("refraction series frac_bits must be 0..32")
-        if (aedges.size + 1) * (wedges.size + 1) > 65536:
-            raise ValueError("a refraction frame holds at most 65536 cells, (na + 2) * (nw + 2)")
-        self._refr = dict(wedges=wedges, aedges=aedges, frac_bits=frac_bits, directory=directory, frames=0,
-                          pending=0, kept=[])
+        wedges, aedges, frac_bits = _plane_args(omega_edges, a_edges, frac_bits, "alignment", "refraction series",
+                                                "a refraction", "na")
+        self._recorders["refr"] = _PlaneRecorder(self, directory, "refr", wedges, aedges, frac_bits, None,
+                                                 combine_refrs)
         if self.n > 0:
             self.ctx.refr_series_begin(self.f, self.Cg, wedges, aedges, frac_bits)
 
@@ -1399,82 +1377,14 @@ class PacketEnsemble:
         shard records nothing.  When the device series holds more than 256 MB
         it is drained (get, combine, append, reset): a collective when
         sharded, at the same frame on every rank."""
-        st = getattr(self, "_refr", None)
-        if st is None:
-            raise SwrtError("record_refr: call begin_refr first")
-        st["frames"] += 1
-        st["pending"] += 1
-        if self.n > 0:
-            if alpha is None:
-                self.ctx.refr_series_record(nslots=1, bump=self.bump)
-            else:
-                self.ctx.refr_series_record(nslots=2, alpha=alpha, bump=self.bump)
-        nas, nws = st["aedges"].size + 1, st["wedges"].size + 1
-        if st["pending"] * 8 * (nas * nws + 3 * nws + nas + 2) > MAP_DRAIN_BYTES:
-            self._drain_refrs()
-
-    def _drain_refrs(self):
-        """The frames on the device, summed over the shards, to the files or
-        the host list of rank 0; the device series emptied."""
-        st = self._refr
-        T, nas, nws = st["pending"], st["aedges"].size + 1, st["wedges"].size + 1
-        if T == 0:
-            return
-        if self.n > 0:
-            part = self.ctx.refr_series_get(0, T)
-            self.ctx.refr_series_reset()
-        else:
-            part = (np.zeros((T, nas, nws), dtype=np.int64), np.zeros((T, 3 * nws + nas), dtype=np.int64),
-                    np.zeros((T, 2), dtype=np.int64))
-        st["pending"] = 0
-        if self.world > 1:
-            import torch
-            import torch.distributed as dist
-
-            from .dist import _device_for
-            dev = _device_for(dist.get_backend())
-            gathered = []
-            for a in part:
-                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                out = [torch.empty_like(buf) for _ in range(self.world)]
-                dist.all_gather(out, buf)
-                gathered.append([o.cpu().numpy() for o in out])
-            if self.rank != 0:
-                return
-            part = combine_refrs(zip(*gathered))
-        if st["directory"] is None:
-            st["kept"].append(part)
-        else:
-            self._append_refrs(st["directory"], *part)
-
-    @staticmethod
-    def _append_refrs(directory, counts, sums, stats):
-        with open(os.path.join(directory, "refr_hist.bin"), "ab") as fc, \
-                open(os.path.join(directory, "refr_sums.bin"), "ab") as fs, \
-                open(os.path.join(directory, "refr_stats.bin"), "ab") as ft:
-            for fr, s, t in zip(counts, sums, stats):
-                fc.write(np.ascontiguousarray(fr, dtype=np.int64).tobytes())  # (cell (ac, wc) at ac*(nw + 2) + wc)
-                fs.write(np.ascontiguousarray(s, dtype=np.int64).tobytes())
-                ft.write(np.ascontiguousarray(t, dtype=np.int64).tobytes())
+        self._record_blended("refr", alpha)
 
     def refr_series(self):
         """(counts (T, na + 2, nw + 2), sums (T, 3 (nw + 2) + (na + 2)), stats
         (T, 2)), all int64, of the ensemble's frames still held (not yet
         drained into files).  Sharded: a collective; rank 0 gets
         combine_refrs() of the shards' frames, the others None."""
-        st = getattr(self, "_refr", None)
-        if st is None:
-            raise SwrtError("refr_series: call begin_refr first")
-        if st["directory"] is not None:
-            raise ValueError("refr_series: begin_refr drains into a directory (read its files)")
-        self._drain_refrs()
-        if self.rank != 0:
-            return None
-        nas, nws = st["aedges"].size + 1, st["wedges"].size + 1
-        if not st["kept"]:
-            return (np.zeros((0, nas, nws), dtype=np.int64), np.zeros((0, 3 * nws + nas), dtype=np.int64),
-                    np.zeros((0, 2), dtype=np.int64))
-        return tuple(np.concatenate([p[i] for p in st["kept"]]) for i in range(3))
+        return self._recorder("refr", "refr_series").series("refr_series")
 
     def write_refrs(self, directory):
         """The run's refraction series as raw native-endian files:
@@ -1484,21 +1394,7 @@ class PacketEnsemble:
         refr_geom.bin (doubles [na, nw, frac_bits], the na + 1 alignment
         edges, the nw + 1 omega edges).  Sharded: a collective; rank 0 writes.
         Returns the frames recorded."""
-        st = getattr(self, "_refr", None)
-        if st is None:
-            raise SwrtError("write_refrs: call begin_refr first")
-        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
-            raise ValueError("write_refrs: begin_refr drained into another directory")
-        self._drain_refrs()
-        if self.rank == 0:
-            if st["directory"] is None:
-                for part in st["kept"]:
-                    self._append_refrs(directory, *part)
-                st["kept"] = []
-            with open(os.path.join(directory, "refr_geom.bin"), "wb") as fh:
-                head = np.array([st["aedges"].size - 1, st["wedges"].size - 1, st["frac_bits"]], dtype=np.float64)
-                fh.write(np.concatenate([head, st["aedges"], st["wedges"]]).tobytes())
-        return st["frames"]
+        return self._recorder("refr", "write_refrs").write("write_refrs", directory)
 
     def begin_absfreq(self, omega_edges, abs_edges, frac_bits=20, directory=None):
         """Open the absolute-frequency series of this run
@@ -1507,18 +1403,10 @@ class PacketEnsemble:
         ``abs_edges``.  ``directory``: where record_absfreq drains the device
         series when it grows large (default: the drained frames wait in host
         memory for write_absfreqs)."""
-        wedges = np.array(omega_edges, dtype=np.float64).ravel()
-        oedges = np.array(abs_edges, dtype=np.float64).ravel()
-        for name, e in (("omega", wedges), ("absolute-frequency", oedges)):
-            if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
-                raise ValueError(f"the {name} edges must be at least two finite increasing values")
-        frac_bits = int(frac_bits)
-        if not 0 <= frac_bits <= 32:
-            raise ValueError("absolute-frequency series frac_bits must be 0..32")
-        if (oedges.size + 1) * (wedges.size + 1) > 65536:
-            raise ValueError("an absolute-frequency frame holds at most 65536 cells, (no + 2) * (nw + 2)")
-        self._absfreq = dict(wedges=wedges, oedges=oedges, frac_bits=frac_bits, directory=directory, frames=0,
-                             pending=0, kept=[])
+        wedges, oedges, frac_bits = _plane_args(omega_edges, abs_edges, frac_bits, "absolute-frequency",
+                                                "absolute-frequency series", "an absolute-frequency", "no")
+        self._recorders["absfreq"] = _PlaneRecorder(self, directory, "absfreq", wedges, oedges, frac_bits, None,
+                                                    combine_absfreqs)
         if self.n > 0:
             self.ctx.absfreq_series_begin(self.f, self.Cg, wedges, oedges, frac_bits)
 
@@ -1530,79 +1418,15 @@ class PacketEnsemble:
         rates.  An empty shard records nothing.  When the device series holds
         more than 256 MB it is drained (get, combine, append, reset): a
         collective when sharded, at the same frame on every rank."""
-        st = getattr(self, "_absfreq", None)
-        if st is None:
-            raise SwrtError("record_absfreq: call begin_absfreq first")
-        st["frames"] += 1
-        st["pending"] += 1
-        if self.n > 0:
-            self.ctx.absfreq_series_record(slot_a, slot_b, alpha, tau, bump=self.bump)
-        nos, nws = st["oedges"].size + 1, st["wedges"].size + 1
-        if st["pending"] * 8 * (nos * nws + 3 * nws + 2 * nos + 2) > MAP_DRAIN_BYTES:
-            self._drain_absfreqs()
-
-    def _drain_absfreqs(self):
-        """The frames on the device, summed over the shards, to the files or
-        the host list of rank 0; the device series emptied."""
-        st = self._absfreq
-        T, nos, nws = st["pending"], st["oedges"].size + 1, st["wedges"].size + 1
-        if T == 0:
-            return
-        if self.n > 0:
-            part = self.ctx.absfreq_series_get(0, T)
-            self.ctx.absfreq_series_reset()
-        else:
-            part = (np.zeros((T, nos, nws), dtype=np.int64), np.zeros((T, 3 * nws + 2 * nos), dtype=np.int64),
-                    np.zeros((T, 2), dtype=np.int64))
-        st["pending"] = 0
-        if self.world > 1:
-            import torch
-            import torch.distributed as dist
-
-            from .dist import _device_for
-            dev = _device_for(dist.get_backend())
-            gathered = []
-            for a in part:
-                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                out = [torch.empty_like(buf) for _ in range(self.world)]
-                dist.all_gather(out, buf)
-                gathered.append([o.cpu().numpy() for o in out])
-            if self.rank != 0:
-                return
-            part = combine_absfreqs(zip(*gathered))
-        if st["directory"] is None:
-            st["kept"].append(part)
-        else:
-            self._append_absfreqs(st["directory"], *part)
-
-    @staticmethod
-    def _append_absfreqs(directory, counts, sums, stats):
-        with open(os.path.join(directory, "absfreq_hist.bin"), "ab") as fc, \
-                open(os.path.join(directory, "absfreq_sums.bin"), "ab") as fs, \
-                open(os.path.join(directory, "absfreq_stats.bin"), "ab") as ft:
-            for fr, s, t in zip(counts, sums, stats):
-                fc.write(np.ascontiguousarray(fr, dtype=np.int64).tobytes())  # (cell (oc, wc) at oc*(nw + 2) + wc)
-                fs.write(np.ascontiguousarray(s, dtype=np.int64).tobytes())
-                ft.write(np.ascontiguousarray(t, dtype=np.int64).tobytes())
+        self._recorder("absfreq", "record_absfreq").record(
+            lambda: self.ctx.absfreq_series_record(slot_a, slot_b, alpha, tau, bump=self.bump))
 
     def absfreq_series(self):
         """(counts (T, no + 2, nw + 2), sums (T, 3 (nw + 2) + 2 (no + 2)),
         stats (T, 2)), all int64, of the ensemble's frames still held (not yet
         drained into files).  Sharded: a collective; rank 0 gets
         combine_absfreqs() of the shards' frames, the others None."""
-        st = getattr(self, "_absfreq", None)
-        if st is None:
-            raise SwrtError("absfreq_series: call begin_absfreq first")
-        if st["directory"] is not None:
-            raise ValueError("absfreq_series: begin_absfreq drains into a directory (read its files)")
-        self._drain_absfreqs()
-        if self.rank != 0:
-            return None
-        nos, nws = st["oedges"].size + 1, st["wedges"].size + 1
-        if not st["kept"]:
-            return (np.zeros((0, nos, nws), dtype=np.int64), np.zeros((0, 3 * nws + 2 * nos), dtype=np.int64),
-                    np.zeros((0, 2), dtype=np.int64))
-        return tuple(np.concatenate([p[i] for p in st["kept"]]) for i in range(3))
+        return self._recorder("absfreq", "absfreq_series").series("absfreq_series")
 
     def write_absfreqs(self, directory):
         """The run's absolute-frequency series as raw native-endian files:
@@ -1612,21 +1436,7 @@ class PacketEnsemble:
         rejected) and absfreq_geom.bin (doubles [no, nw, frac_bits], the
         no + 1 Omega edges, the nw + 1 omega edges).  Sharded: a collective;
         rank 0 writes.  Returns the frames recorded."""
-        st = getattr(self, "_absfreq", None)
-        if st is None:
-            raise SwrtError("write_absfreqs: call begin_absfreq first")
-        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
-            raise ValueError("write_absfreqs: begin_absfreq drained into another directory")
-        self._drain_absfreqs()
-        if self.rank == 0:
-            if st["directory"] is None:
-                for part in st["kept"]:
-                    self._append_absfreqs(directory, *part)
-                st["kept"] = []
-            with open(os.path.join(directory, "absfreq_geom.bin"), "wb") as fh:
-                head = np.array([st["oedges"].size - 1, st["wedges"].size - 1, st["frac_bits"]], dtype=np.float64)
-                fh.write(np.concatenate([head, st["oedges"], st["wedges"]]).tobytes())
-        return st["frames"]
+        return self._recorder("absfreq", "write_absfreqs").write("write_absfreqs", directory)
 
     def begin_trans(self, omega_edges, src_edges, frac_bits=20, by=0, directory=None):
         """Open the transition series of this run (swrt_trans_series_begin
@@ -1636,20 +1446,13 @@ class PacketEnsemble:
         trans_geom.bin.  ``directory``: where record_trans drains the device
         series when it grows large (default: the drained frames wait in host
         memory for write_trans)."""
-        wedges = np.array(omega_edges, dtype=np.float64).ravel()
-        sedges = np.array(src_edges, dtype=np.float64).ravel()
-        for name, e in (("omega", wedges), ("source", sedges)):
-            if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
-                raise ValueError(f"the {name} edges must be at least two finite increasing values")
-        frac_bits = int(frac_bits)
-        if not 0 <= frac_bits <= 32:
-            raise ValueError("transition series frac_bits must be 0..32")
-        if (sedges.size + 1) * (wedges.size + 1) > 65536:
-            raise ValueError("a transition frame holds at most 65536 cells, (ns + 2) * (nw + 2)")
+        wedges, sedges, frac_bits = _plane_args(omega_edges, src_edges, frac_bits, "source", "transition series",
+                                                "a transition", "ns")
         if by not in (0, 1):
             raise ValueError("by must be 0 (omega at the mark) or 1 (ring)")
-        self._trans = dict(wedges=wedges, sedges=sedges, frac_bits=frac_bits, by=int(by), directory=directory,
-                           frames=0, pending=0, kept=[], times=[], t_mark=None)
+        head = [sedges.size - 1, wedges.size - 1, frac_bits, int(by)]
+        self._recorders["trans"] = _TransRecorder(self, directory, "trans", wedges, sedges, frac_bits, head,
+                                                  combine_transitions)
         if self.n > 0:
             self.ctx.trans_series_begin(self.f, self.Cg, wedges, sedges, frac_bits)
 
@@ -1659,9 +1462,7 @@ class PacketEnsemble:
         **whole** ensemble in the original order (a shard takes its own).
         ``t``: the time of the mark, kept for trans_time.bin.  Every rank
         calls it at the same frame, so the shards' mark serials agree."""
-        st = getattr(self, "_trans", None)
-        if st is None:
-            raise SwrtError("mark_trans: call begin_trans first")
+        rec = self._recorder("trans", "mark_trans")
         if values is not None:
             values = np.asarray(values, dtype=np.float64).ravel()
             if values.size != self.n_total:
@@ -1673,7 +1474,7 @@ class PacketEnsemble:
                 self.ctx.trans_series_mark()
             else:
                 self.ctx.trans_series_mark_values(values)
-        st["t_mark"] = np.nan if t is None else float(t)
+        rec.t_mark = np.nan if t is None else float(t)
 
     def record_trans(self, t=None):
         """Append this shard's transition frame at the current state to the
@@ -1681,86 +1482,18 @@ class PacketEnsemble:
         nothing.  When the device series holds more than 256 MB it is drained
         (get, combine, append, reset; the mark stays): a collective when
         sharded, at the same frame on every rank."""
-        st = getattr(self, "_trans", None)
-        if st is None:
-            raise SwrtError("record_trans: call begin_trans first")
-        if st["t_mark"] is None:
+        rec = self._recorder("trans", "record_trans")
+        if rec.t_mark is None:
             raise SwrtError("record_trans: call mark_trans first")
-        st["frames"] += 1
-        st["pending"] += 1
-        st["times"].append((np.nan if t is None else float(t), st["t_mark"]))
-        if self.n > 0:
-            self.ctx.trans_series_record()
-        nss, nws = st["sedges"].size + 1, st["wedges"].size + 1
-        if st["pending"] * 8 * (nss * nws + 3 * nss + 3) > MAP_DRAIN_BYTES:
-            self._drain_trans()
-
-    def _drain_trans(self):
-        """The frames on the device, combined over the shards, to the files or
-        the host list of rank 0; the device series emptied."""
-        st = self._trans
-        T, nss, nws = st["pending"], st["sedges"].size + 1, st["wedges"].size + 1
-        if T == 0:
-            return
-        if self.n > 0:
-            part = self.ctx.trans_series_get(0, T)
-            self.ctx.trans_series_reset()
-        else:
-            part = (np.zeros((T, nss, nws), dtype=np.int64), np.zeros((T, nss, 3), dtype=np.int64),
-                    np.zeros((T, 3), dtype=np.int64))
-        st["pending"] = 0
-        times, st["times"] = np.array(st["times"], dtype=np.float64).reshape(T, 2), []
-        if self.world > 1:
-            import torch
-            import torch.distributed as dist
-
-            from .dist import _device_for
-            dev = _device_for(dist.get_backend())
-            gathered = []
-            for a in part:
-                buf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                out = [torch.empty_like(buf) for _ in range(self.world)]
-                dist.all_gather(out, buf)
-                gathered.append([o.cpu().numpy() for o in out])
-            if self.rank != 0:
-                return
-            part = combine_transitions(zip(*gathered))
-        part = tuple(part) + (times,)
-        if st["directory"] is None:
-            st["kept"].append(part)
-        else:
-            self._append_trans(st["directory"], *part)
-
-    @staticmethod
-    def _append_trans(directory, counts, sums, stats, times):
-        with open(os.path.join(directory, "trans_hist.bin"), "ab") as fc, \
-                open(os.path.join(directory, "trans_sums.bin"), "ab") as fs, \
-                open(os.path.join(directory, "trans_stats.bin"), "ab") as ft, \
-                open(os.path.join(directory, "trans_time.bin"), "ab") as fm:
-            for fr, s, t, tm in zip(counts, sums, stats, times):
-                fc.write(np.ascontiguousarray(fr, dtype=np.int64).tobytes())  # (cell (sc, wc) at sc*(nw + 2) + wc)
-                fs.write(np.ascontiguousarray(s, dtype=np.int64).tobytes())
-                ft.write(np.ascontiguousarray(t, dtype=np.int64).tobytes())
-                fm.write(np.ascontiguousarray(tm, dtype=np.float64).tobytes())
+        rec.times.append((np.nan if t is None else float(t), rec.t_mark))
+        rec.record(self.ctx.trans_series_record)
 
     def trans_series(self):
         """(counts (T, ns + 2, nw + 2), sums (T, ns + 2, 3), stats (T, 3)), all
         int64, and times (T, 2) fp64 [t, t_mark] of the ensemble's frames still
         held (not yet drained into files).  Sharded: a collective; rank 0 gets
         combine_transitions() of the shards' frames, the others None."""
-        st = getattr(self, "_trans", None)
-        if st is None:
-            raise SwrtError("trans_series: call begin_trans first")
-        if st["directory"] is not None:
-            raise ValueError("trans_series: begin_trans drains into a directory (read its files)")
-        self._drain_trans()
-        if self.rank != 0:
-            return None
-        nss, nws = st["sedges"].size + 1, st["wedges"].size + 1
-        if not st["kept"]:
-            return (np.zeros((0, nss, nws), dtype=np.int64), np.zeros((0, nss, 3), dtype=np.int64),
-                    np.zeros((0, 3), dtype=np.int64), np.zeros((0, 2)))
-        return tuple(np.concatenate([p[i] for p in st["kept"]]) for i in range(4))
+        return self._recorder("trans", "trans_series").series("trans_series")
 
     def write_trans(self, directory):
         """The run's transition series as raw native-endian files:
@@ -1772,22 +1505,7 @@ class PacketEnsemble:
         (doubles [ns, nw, frac_bits, by], the ns + 1 source edges, the nw + 1
         omega edges).  Sharded: a collective; rank 0 writes.  Returns the
         frames recorded."""
-        st = getattr(self, "_trans", None)
-        if st is None:
-            raise SwrtError("write_trans: call begin_trans first")
-        if st["directory"] is not None and os.path.abspath(st["directory"]) != os.path.abspath(directory):
-            raise ValueError("write_trans: begin_trans drained into another directory")
-        self._drain_trans()
-        if self.rank == 0:
-            if st["directory"] is None:
-                for part in st["kept"]:
-                    self._append_trans(directory, *part)
-                st["kept"] = []
-            with open(os.path.join(directory, "trans_geom.bin"), "wb") as fh:
-                head = np.array([st["sedges"].size - 1, st["wedges"].size - 1, st["frac_bits"], st["by"]],
-                                dtype=np.float64)
-                fh.write(np.concatenate([head, st["sedges"], st["wedges"]]).tobytes())
-        return st["frames"]
+        return self._recorder("trans", "write_trans").write("write_trans", directory)
 
     def begin_recycle(self, omega_cut, seed=0, frac_bits=20, directory=None, every=1):
         """Begin recycling this run's packets (swrt_recycle_begin with the

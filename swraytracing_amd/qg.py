@@ -408,6 +408,32 @@ def _kmap_args(kmap_cells, kmap_kmax, kmap_frac_bits, ring_radius=None):
     return float(kmap_kmax), int(kmap_cells), int(kmap_frac_bits)
 
 
+def _plane_edges(spectrum_edges, needs_msg, name, edges, missing_msg=None):
+    """The first checks of a class-plane series' driver arguments: the run
+    has ``spectrum_edges`` (its omega classes), and the argument ``name`` holds
+    the second axis' edges, at least two finite increasing values."""
+    if spectrum_edges is None:
+        raise ValueError(needs_msg)
+    if edges is None:
+        raise ValueError(missing_msg)
+    edges = np.array(edges, dtype=np.float64).ravel()
+    if edges.size < 2 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
+        raise ValueError(f"{name} must be at least two finite increasing values")
+    return edges
+
+
+def _plane_frac_bits(name, frac_bits, edges, spectrum_edges, cap_msg):
+    """The last checks: the argument ``name`` an integer 0..32; at most 4096
+    classes and 65536 cells a frame."""
+    if isinstance(frac_bits, (bool, np.bool_)) or not isinstance(frac_bits, numbers.Real) \
+            or int(frac_bits) != frac_bits or not 0 <= int(frac_bits) <= 32:
+        raise ValueError(f"{name} must be an integer 0..32")
+    nw = np.asarray(spectrum_edges).size - 1
+    if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
+        raise ValueError(cap_msg)
+    return int(frac_bits)
+
+
 def _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges):
     """The drivers' ``cond_by`` / ``cond_edges`` / ``cond_frac_bits`` checked
     before anything runs: (which, q edges, frac_bits), or None without
@@ -416,20 +442,12 @@ def _cond_args(cond_by, cond_edges, cond_frac_bits, spectrum_edges):
         return None
     if not isinstance(cond_by, str) or cond_by not in ("zeta", "sigma", "D"):
         raise ValueError('cond_by must be None, "zeta", "sigma" or "D"')
-    if spectrum_edges is None:
-        raise ValueError("cond_by needs spectrum_edges: they are the conditional spectra's omega classes")
-    if cond_edges is None:
-        raise ValueError("cond_by needs cond_edges, the classes of the flow scalar")
-    edges = np.array(cond_edges, dtype=np.float64).ravel()
-    if edges.size < 2 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
-        raise ValueError("cond_edges must be at least two finite increasing values")
-    if isinstance(cond_frac_bits, (bool, np.bool_)) or not isinstance(cond_frac_bits, numbers.Real) \
-            or int(cond_frac_bits) != cond_frac_bits or not 0 <= int(cond_frac_bits) <= 32:
-        raise ValueError("cond_frac_bits must be an integer 0..32")
-    nw = np.asarray(spectrum_edges).size - 1
-    if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
-        raise ValueError("cond_edges: at most 4096 classes and (nq + 2) * (nbins + 2) <= 65536 cells a frame")
-    return cond_by, edges, int(cond_frac_bits)
+    edges = _plane_edges(spectrum_edges,
+                         "cond_by needs spectrum_edges: they are the conditional spectra's omega classes",
+                         "cond_edges", cond_edges, "cond_by needs cond_edges, the classes of the flow scalar")
+    frac_bits = _plane_frac_bits("cond_frac_bits", cond_frac_bits, edges, spectrum_edges,
+                                 "cond_edges: at most 4096 classes and (nq + 2) * (nbins + 2) <= 65536 cells a frame")
+    return cond_by, edges, frac_bits
 
 
 def _refr_args(refr_edges, refr_frac_bits, spectrum_edges):
@@ -438,18 +456,12 @@ def _refr_args(refr_edges, refr_frac_bits, spectrum_edges):
     omega classes are the run's ``spectrum_edges``."""
     if refr_edges is None:
         return None
-    if spectrum_edges is None:
-        raise ValueError("refr_edges needs spectrum_edges: they are the refraction series' omega classes")
-    edges = np.array(refr_edges, dtype=np.float64).ravel()
-    if edges.size < 2 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
-        raise ValueError("refr_edges must be at least two finite increasing values")
-    if isinstance(refr_frac_bits, (bool, np.bool_)) or not isinstance(refr_frac_bits, numbers.Real) \
-            or int(refr_frac_bits) != refr_frac_bits or not 0 <= int(refr_frac_bits) <= 32:
-        raise ValueError("refr_frac_bits must be an integer 0..32")
-    nw = np.asarray(spectrum_edges).size - 1
-    if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
-        raise ValueError("refr_edges: at most 4096 classes and (na + 2) * (nbins + 2) <= 65536 cells a frame")
-    return edges, int(refr_frac_bits)
+    edges = _plane_edges(spectrum_edges,
+                         "refr_edges needs spectrum_edges: they are the refraction series' omega classes",
+                         "refr_edges", refr_edges)
+    return edges, _plane_frac_bits(
+        "refr_frac_bits", refr_frac_bits, edges, spectrum_edges,
+        "refr_edges: at most 4096 classes and (na + 2) * (nbins + 2) <= 65536 cells a frame")
 
 
 def _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges):
@@ -458,18 +470,12 @@ def _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges):
     The omega classes are the run's ``spectrum_edges``."""
     if absfreq_edges is None:
         return None
-    if spectrum_edges is None:
-        raise ValueError("absfreq_edges needs spectrum_edges: they are the absolute-frequency series' omega classes")
-    edges = np.array(absfreq_edges, dtype=np.float64).ravel()
-    if edges.size < 2 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
-        raise ValueError("absfreq_edges must be at least two finite increasing values")
-    if isinstance(absfreq_frac_bits, (bool, np.bool_)) or not isinstance(absfreq_frac_bits, numbers.Real) \
-            or int(absfreq_frac_bits) != absfreq_frac_bits or not 0 <= int(absfreq_frac_bits) <= 32:
-        raise ValueError("absfreq_frac_bits must be an integer 0..32")
-    nw = np.asarray(spectrum_edges).size - 1
-    if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
-        raise ValueError("absfreq_edges: at most 4096 classes and (no + 2) * (nbins + 2) <= 65536 cells a frame")
-    return edges, int(absfreq_frac_bits)
+    edges = _plane_edges(spectrum_edges,
+                         "absfreq_edges needs spectrum_edges: they are the absolute-frequency series' omega classes",
+                         "absfreq_edges", absfreq_edges)
+    return edges, _plane_frac_bits(
+        "absfreq_frac_bits", absfreq_frac_bits, edges, spectrum_edges,
+        "absfreq_edges: at most 4096 classes and (no + 2) * (nbins + 2) <= 65536 cells a frame")
 
 
 def _packet_method_args(packet_method, packet_iterations, integrator):
@@ -514,23 +520,15 @@ def _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_
             raise ValueError('trans_by="ring" is never re-marked: leave trans_lag out')
         edges = np.arange(nrings + 1, dtype=np.float64) - 0.5
     else:
-        if trans_src_edges is None:
-            raise ValueError('trans_by="omega" needs trans_src_edges, the classes of omega at the mark')
-        edges = np.array(trans_src_edges, dtype=np.float64).ravel()
-        if edges.size < 2 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
-            raise ValueError("trans_src_edges must be at least two finite increasing values")
+        edges = _plane_edges(spectrum_edges, None, "trans_src_edges", trans_src_edges,
+                             'trans_by="omega" needs trans_src_edges, the classes of omega at the mark')
     if trans_lag is not None and (isinstance(trans_lag, (bool, np.bool_)) or not isinstance(trans_lag, numbers.Integral)
                                   or trans_lag < 1):
         raise ValueError("trans_lag must be None or an integer >= 1")
-    if isinstance(trans_frac_bits, (bool, np.bool_)) or not isinstance(trans_frac_bits, numbers.Real) \
-            or int(trans_frac_bits) != trans_frac_bits or not 0 <= int(trans_frac_bits) <= 32:
-        raise ValueError("trans_frac_bits must be an integer 0..32")
-    nw = np.asarray(spectrum_edges).size - 1
-    if not 1 <= edges.size - 1 <= 4096 or (edges.size + 1) * (nw + 2) > 65536:
-        raise ValueError("the transition series: at most 4096 source classes and (ns + 2) * (nbins + 2) <= 65536 "
-                         "cells a frame")
-    return (1 if trans_by == "ring" else 0), edges, (None if trans_lag is None else int(trans_lag)), \
-        int(trans_frac_bits)
+    frac_bits = _plane_frac_bits(
+        "trans_frac_bits", trans_frac_bits, edges, spectrum_edges,
+        "the transition series: at most 4096 source classes and (ns + 2) * (nbins + 2) <= 65536 cells a frame")
+    return (1 if trans_by == "ring" else 0), edges, (None if trans_lag is None else int(trans_lag)), frac_bits
 
 
 def _recycle_args(recycle_omega, recycle_seed, recycle_every, recycle_frac_bits, ring_factors, f, trans_src_edges,

@@ -253,6 +253,14 @@ int main() {
            h.fits(10, 2 * 512) && !h.fits(10, 2 * 4096) && h.fits(1, 2 * 4096) && !h.fits(2, 2 * 4096), true);
     expect("series_history_growth_for_larger_frame", h.grown(10, 2 * 4096, 0) == 10, true);
   }
+  {  // PlaneLayout at nw = 5, n2 = 3 against the four series' own formulas, worked out by hand:
+     // a 5 x 7 plane; tails nq + 4, 3 (ns + 2) + 3, 3 (nw + 2) + (na + 2) + 2, 3 (nw + 2) + 2 (no + 2) + 2
+    const PlaneLayout cond{5, 3, 0, 1, 2}, trans{5, 3, 0, 3, 3}, refr{5, 3, 3, 1, 2}, absfreq{5, 3, 3, 2, 2};
+    expect("plane_layout_cond", cond.frame() == 35 && cond.nsums() == 5 && cond.tail() == 7, true);
+    expect("plane_layout_trans", trans.frame() == 35 && trans.nsums() == 15 && trans.tail() == 18, true);
+    expect("plane_layout_refr", refr.frame() == 35 && refr.nsums() == 26 && refr.tail() == 28, true);
+    expect("plane_layout_absfreq", absfreq.frame() == 35 && absfreq.nsums() == 31 && absfreq.tail() == 33, true);
+  }
   std::printf("%s\n", fails ? "FAILED" : "ALL OK");
   return fails ? 1 : 0;
 }

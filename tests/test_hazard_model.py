@@ -41,3 +41,6 @@ def test_hazard_checker_model(tmp_path):
                  "series_released_drops_capacity", "series_history_smaller_frame_does_not_pass",
                  "series_history_growth_for_larger_frame"):
         assert name + " ok" in r.stdout, r.stdout
+    # the class-plane series' frame layout (PlaneLayout) against each series' own formulas
+    for name in ("plane_layout_cond", "plane_layout_trans", "plane_layout_refr", "plane_layout_absfreq"):
+        assert name + " ok" in r.stdout, r.stdout
