@@ -1107,6 +1107,81 @@ int swrt_absfreq_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t
 int swrt_absfreq_series_reset(swrt_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * The ray-tube tangent map (no reference counterpart: its interpolate has no
+ * derivative)
+ * ------------------------------------------------------------------------ */
+
+/* Per packet M = d(x, y, k, l) / d(x0, y0, k0, l0) since the last mark: the
+ * exact derivative of the DISCRETE leapfrog step (drift, Euler kick, drift),
+ * 4 x 4 row-major, carried along every ray on the device, and an int32
+ * caustic counter: the sign changes of J = M00 M11 - M01 M10 from step to
+ * step (J = 1 at a mark; 1/|J| scales the wave-action density of a packet
+ * launched as a plane wave).  M is the Jacobian of the map, not of the ray
+ * equations' flow: det M != 1 measures the scheme, and M overflows after some
+ * thousands of steps without a mark.  The operation order is stated in
+ * swrt_tangent.hpp and restated in numpy by tests/tangent_ref.py; results are
+ * bit-reproducible and do not depend on re-binning or on how the steps are
+ * split over calls.
+ *
+ * swrt_tangent_begin allocates the set for the current packets (M = I,
+ * counters 0, mark serial 1); it is live until swrt_tangent_end.  While it is
+ * live
+ *   - swrt_advance, swrt_advance_intervals and swrt_leapfrog take the
+ *     per-packet route (as swrt_set_kernel 1: re-binning moves the packets,
+ *     intervals run one at a time, history frames are written as ever) and
+ *     launch the tangent kernel on the current set in place; x and k keep the
+ *     bits of every other route;
+ *   - a non-default integrator (swrt_set_integrator) or the FMA gather
+ *     (swrt_set_gather_mode 1) makes those calls fail with SWRT_ERR_ARG;
+ *   - swrt_ode23_*, swrt_xka_step, swrt_spectral_leapfrog and
+ *     swrt_recycle_apply fail with SWRT_ERR_STATE: they would move packets
+ *     without their M;
+ *   - swrt_packets_set with another N drops the set (as it drops the raydiag
+ *     mark), with the same N it marks.
+ * Everything is queued on the packet stream in call order, with the raydiag
+ * calls' guarantees for streams and slots: a record or a get sees the M of
+ * every advance queued before it.  Without a live set nothing changes.
+ * swrt_tangent_mark: M = I, counters 0, ++serial (a new window).
+ * swrt_tangent_get: M (N x 16) and the counters (N) in the original packet
+ * order; either may be NULL.  Waits. */
+int swrt_tangent_begin(swrt_ctx* ctx);
+int swrt_tangent_mark(swrt_ctx* ctx);
+int swrt_tangent_get(swrt_ctx* ctx, double* M16_out, int32_t* caustics_out);
+int swrt_tangent_end(swrt_ctx* ctx);
+/* 1 while a set is live, else 0 (-1: NULL context); the mark serial (0: none). */
+int swrt_tangent_live(const swrt_ctx* ctx);
+int64_t swrt_tangent_serial(const swrt_ctx* ctx);
+
+/* The tangent series: class-plane frames of the live set.  Per packet omega =
+ * sqrt(f^2 + Cg^2 |k|^2) in the spectrum series' bits, s = (sum of M_ij^2,
+ * row-major) / 4 and J; e(v) = frexp exponent - 1 = floor(log2 v), exact.  A
+ * frame is
+ *   counts  (ns + 2) x (nw + 2) 64-bit counts, cell gc * (nw + 2) + wc: the
+ *           class of s over growth_edges by the class of omega over
+ *           omega_edges ([below, bins, above], comparisons only);
+ *   sums    per omega class the sums of e(s), e(|J|) and the caustic counters
+ *           (three rows of nw + 2, two's complement), then per growth class
+ *           the sum of the caustic counters (ns + 2);
+ *   stats   [n, rejected, mark serial].
+ * A packet is rejected, and adds to nothing else, if omega, s or J is not
+ * finite or J == 0.  Integer sums: frames of shards add.  At most 2^24
+ * packets a frame, 1..4096 classes an axis, (ns + 2) * (nw + 2) <= 65536.
+ * begin empties the series (it needs no live set); record needs one
+ * (SWRT_ERR_STATE otherwise) and is queued without a host wait. */
+int swrt_tangent_series_begin(swrt_ctx* ctx, double f, double Cg, const double* omega_edges, int64_t nw,
+                              const double* growth_edges, int64_t ns);
+int swrt_tangent_series_record(swrt_ctx* ctx);
+int64_t swrt_tangent_series_frames(const swrt_ctx* ctx);
+int swrt_tangent_series_bins(const swrt_ctx* ctx, int64_t* nw_out, int64_t* ns_out);
+/* Frames [first, first + count): counts_out count x (ns + 2) x (nw + 2),
+ * sums_out count x (3 (nw + 2) + (ns + 2)) and stats3_out count x 3,
+ * frame-major.  Each may be NULL.  Waits for the frames. */
+int swrt_tangent_series_get(swrt_ctx* ctx, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                            int64_t* stats3_out);
+/* Empty the series; the edges stay. */
+int swrt_tangent_series_reset(swrt_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * The invariant and the flow along the rays (symplectic_full_fourier.m:41,54-57,
  * SW_zero_background_raytracing.m:57,85-87, RaytracingScheme.m:18-31)
  * ------------------------------------------------------------------------ */
@@ -1552,7 +1627,10 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
  *   (tools/refr_series_rate.py).  Both values give the same integers.
  * SWRT_DEBUG_ABSFREQ_GLOBAL 0 / 1 (default 0): 1 makes the absolute-frequency
  *   series' records take the global kernel for every shape
- *   (tools/absfreq_series_rate.py).  Both values give the same integers. */
+ *   (tools/absfreq_series_rate.py).  Both values give the same integers.
+ * SWRT_DEBUG_TANGENT_GLOBAL 0 / 1 (default 0): 1 makes the tangent series'
+ *   records take the global kernel for every shape.  Both values give the
+ *   same integers. */
 #define SWRT_DEBUG_HAZARD_CHECK 1
 #define SWRT_DEBUG_SPIN_US 2
 #define SWRT_DEBUG_LEGACY_PARK 3
@@ -1575,6 +1653,7 @@ int swrt_clock_ghz_stamps(const uint64_t* stamps, int64_t waves, double realtime
 #define SWRT_DEBUG_TRANS_GLOBAL 21
 #define SWRT_DEBUG_REFR_GLOBAL 22
 #define SWRT_DEBUG_ABSFREQ_GLOBAL 23
+#define SWRT_DEBUG_TANGENT_GLOBAL 24
 int swrt_debug_set(swrt_ctx* ctx, int key, int64_t value);
 int swrt_debug_get(swrt_ctx* ctx, int key, int64_t* value_out);
 

@@ -270,6 +270,56 @@ classdef SwrtContext < handle
             swrt_mex('absfreq_series_reset', obj.id());
         end
 
+        % The ray-tube tangent map on the device: tangent_begin starts
+        % carrying, per packet, M = d(x, y, k, l)/d(x0, y0, k0, l0) of the
+        % discrete leapfrog step since the last mark (4 x 4, I at a mark) and
+        % a caustic counter (sign changes of J = M11*M22 - M12*M21); while it
+        % is live advance / leapfrog take the per-packet route (x and k keep
+        % their bits) and the ode23, xka, spectral and recycle calls are
+        % refused.  The series: counts of the packets over the classes of
+        % s = |M|_F^2/4 (growth_edges) by omega classes, per omega class the
+        % sums of floor(log2 s), floor(log2 |J|) and the counters, per growth
+        % class the sum of the counters, and [n; rejected; mark serial].
+        function tangent_begin(obj)
+            swrt_mex('tangent_begin', obj.id());
+        end
+
+        function tangent_mark(obj)
+            swrt_mex('tangent_mark', obj.id());
+        end
+
+        function [M, caustics] = tangent_get(obj)
+            % M: 16 x n, column i packet i's M row-major (reshape(M(:, i), 4, 4).');
+            % caustics: int64 n x 1; both in the order of packets_set
+            [M, caustics] = swrt_mex('tangent_get', obj.id());
+        end
+
+        function tangent_end(obj)
+            swrt_mex('tangent_end', obj.id());
+        end
+
+        function tangent_series_begin(obj, f, Cg, omega_edges, growth_edges)
+            swrt_mex('tangent_series_begin', obj.id(), f, Cg, omega_edges, growth_edges);
+        end
+
+        function tangent_series_record(obj)
+            swrt_mex('tangent_series_record', obj.id());
+        end
+
+        function n = tangent_series_frames(obj)
+            n = swrt_mex('tangent_series_frames', obj.id());
+        end
+
+        function [counts, sums, stats] = tangent_series_get(obj)
+            % counts: int64 (nw+2) x (ns+2) x frames (first index the omega class);
+            % sums: int64 (3(nw+2)+(ns+2)) x frames; stats: int64 3 x frames
+            [counts, sums, stats] = swrt_mex('tangent_series_get', obj.id());
+        end
+
+        function tangent_series_reset(obj)
+            swrt_mex('tangent_series_reset', obj.id());
+        end
+
         % Packet recycling on the device: at every recycle_apply a packet
         % whose omega has reached omega_cut is absorbed and re-injected in
         % place with its home wavevector (home_k, n x 2 in the order of

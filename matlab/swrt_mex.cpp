@@ -88,6 +88,15 @@
 //   n = swrt_mex('absfreq_series_frames', h)
 //   [counts, sums, stats] = swrt_mex('absfreq_series_get', h)    % int64 (nw+2) x (no+2) x frames, (3(nw+2)+2(no+2)) x frames, 2 x frames
 //   swrt_mex('absfreq_series_reset', h)
+//   swrt_mex('tangent_begin', h)                              % carry M = d(x,k)/d(x0,k0) of the discrete step: M = I, caustic counters 0
+//   swrt_mex('tangent_mark', h)                               % a new window: M = I, counters 0
+//   [M, caustics] = swrt_mex('tangent_get', h)                % 16 x n (column i: packet i's M, row-major), int64 n x 1; original order
+//   swrt_mex('tangent_end', h)
+//   swrt_mex('tangent_series_begin', h, f, Cg, omega_edges, growth_edges)   % classes of |M|_F^2/4 by omega classes
+//   swrt_mex('tangent_series_record', h)
+//   n = swrt_mex('tangent_series_frames', h)
+//   [counts, sums, stats] = swrt_mex('tangent_series_get', h)    % int64 (nw+2) x (ns+2) x frames, (3(nw+2)+(ns+2)) x frames, 3 x frames
+//   swrt_mex('tangent_series_reset', h)
 //   swrt_mex('track_begin', h, ids)                         % trajectories of chosen packets; ids 0-based doubles
 //   swrt_mex('track_record', h, f, gH, nslots, alpha, bump)   % nslots 0: no flow, Omega..D are NaN
 //   swrt_mex('track_record_history', h, first, count, f, gH, nslots, alphas, bump)   % alphas [] when nslots < 2
@@ -815,6 +824,67 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   }
   if (!strcmp(cmd, "absfreq_series_reset")) {
     check(c, swrt_absfreq_series_reset(c), "swrt_absfreq_series_reset");
+    return;
+  }
+  if (!strcmp(cmd, "tangent_begin")) {
+    check(c, swrt_tangent_begin(c), "swrt_tangent_begin");
+    return;
+  }
+  if (!strcmp(cmd, "tangent_mark")) {
+    check(c, swrt_tangent_mark(c), "swrt_tangent_mark");
+    return;
+  }
+  if (!strcmp(cmd, "tangent_get")) {  // -> M 16 x n (double), caustics n x 1 (int64), original order
+    const int64_t n = swrt_packets_count(c);
+    std::vector<int32_t> caus((size_t)n);
+    plhs[0] = mxCreateDoubleMatrix(16, (mwSize)n, mxREAL);
+    check(c, swrt_tangent_get(c, mxGetDoubles(plhs[0]), caus.data()), "swrt_tangent_get");
+    const mwSize dims[2] = {(mwSize)n, 1};
+    mxArray* b = mxCreateNumericArray(2, dims, mxINT64_CLASS, mxREAL);
+    int64_t* pb = (int64_t*)mxGetInt64s(b);
+    for (int64_t i = 0; i < n; ++i) pb[i] = caus[(size_t)i];
+    if (nlhs > 1) plhs[1] = b; else mxDestroyArray(b);
+    return;
+  }
+  if (!strcmp(cmd, "tangent_end")) {
+    check(c, swrt_tangent_end(c), "swrt_tangent_end");
+    return;
+  }
+  if (!strcmp(cmd, "tangent_series_begin")) {  // (f, Cg, omega_edges, growth_edges)
+    need(na, 5, cmd);
+    const size_t ne = mxGetNumberOfElements(a[3]), nge = mxGetNumberOfElements(a[4]);
+    check(c, swrt_tangent_series_begin(c, scalar(a[1]), scalar(a[2]), reals(a[3], "omega_edges"), (int64_t)ne - 1,
+                                       reals(a[4], "growth_edges"), (int64_t)nge - 1),
+          "swrt_tangent_series_begin");
+    return;
+  }
+  if (!strcmp(cmd, "tangent_series_record")) {
+    check(c, swrt_tangent_series_record(c), "swrt_tangent_series_record");
+    return;
+  }
+  if (!strcmp(cmd, "tangent_series_frames")) {
+    plhs[0] = mxCreateDoubleScalar((double)swrt_tangent_series_frames(c));
+    return;
+  }
+  if (!strcmp(cmd, "tangent_series_get")) {  // -> counts (nw+2) x (ns+2) x frames, sums (3(nw+2)+(ns+2)) x frames, stats 3 x frames
+    const int64_t nf = swrt_tangent_series_frames(c);
+    int64_t nw = 0, ns = 0;
+    check(c, swrt_tangent_series_bins(c, &nw, &ns), "swrt_tangent_series_bins");
+    const mwSize dims[3] = {(mwSize)(nw + 2), (mwSize)(ns + 2), (mwSize)nf},
+                 udims[2] = {(mwSize)(3 * (nw + 2) + (ns + 2)), (mwSize)nf}, sdims[2] = {3, (mwSize)nf};
+    plhs[0] = mxCreateNumericArray(3, dims, mxINT64_CLASS, mxREAL);
+    mxArray* sums = mxCreateNumericArray(2, udims, mxINT64_CLASS, mxREAL);
+    mxArray* stats = mxCreateNumericArray(2, sdims, mxINT64_CLASS, mxREAL);
+    if (nf > 0)
+      check(c, swrt_tangent_series_get(c, 0, nf, (int64_t*)mxGetInt64s(plhs[0]), (int64_t*)mxGetInt64s(sums),
+                                       (int64_t*)mxGetInt64s(stats)),
+            "swrt_tangent_series_get");
+    if (nlhs > 1) plhs[1] = sums; else mxDestroyArray(sums);
+    if (nlhs > 2) plhs[2] = stats; else mxDestroyArray(stats);
+    return;
+  }
+  if (!strcmp(cmd, "tangent_series_reset")) {
+    check(c, swrt_tangent_series_reset(c), "swrt_tangent_series_reset");
     return;
   }
   if (!strcmp(cmd, "recycle_begin")) {  // (f, Cg, omega_cut, L[, seed = 0, index_base = 0, frac_bits = 20, home_k = []])

@@ -9,7 +9,7 @@ from ._lib import Context, SwrtError, integrator_weights, load
 from .integrate import (PacketEnsemble, combine_conds, combine_frames, combine_kmaps, combine_maps, combine_spectra, combine_tracks,
                         combine_transitions, trans_moments, combine_recycles, recycle_flux,
                         combine_refrs, alignment_edges, refr_rates,
-                        combine_absfreqs, absfreq_rates,
+                        combine_absfreqs, absfreq_rates, combine_tangents, tangent_growth,
                         cond_spectra, energy_spectrum, kmap_moments, map_fields,
                         ode23_packets, ode23_trajectory,
                         ode_symplectic, raytrace_sw, raytrace_xka, rsw_background, step_packet_xka)
@@ -25,7 +25,7 @@ __all__ = [
     "combine_tracks", "combine_kmaps", "combine_conds", "cond_spectra",
     "combine_transitions", "trans_moments", "combine_recycles", "recycle_flux",
     "combine_refrs", "alignment_edges", "refr_rates",
-    "combine_absfreqs", "absfreq_rates",
+    "combine_absfreqs", "absfreq_rates", "combine_tangents", "tangent_growth",
     "energy_spectrum", "kmap_moments", "map_fields", "ode23_packets", "ode23_trajectory",
     "ode_symplectic",
     "raytrace_sw", "raytrace_xka", "rsw_background", "step_packet_xka",

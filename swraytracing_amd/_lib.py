@@ -143,6 +143,19 @@ SIGNATURES = {
     "swrt_absfreq_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                        ctypes.POINTER(ctypes.c_int64)]),
     "swrt_absfreq_series_reset": (_INT, [_VP]),
+    "swrt_tangent_begin": (_INT, [_VP]),
+    "swrt_tangent_mark": (_INT, [_VP]),
+    "swrt_tangent_get": (_INT, [_VP, _P, ctypes.POINTER(ctypes.c_int32)]),
+    "swrt_tangent_end": (_INT, [_VP]),
+    "swrt_tangent_live": (_INT, [_VP]),
+    "swrt_tangent_serial": (_I, [_VP]),
+    "swrt_tangent_series_begin": (_INT, [_VP, _D, _D, _P, _I, _P, _I]),
+    "swrt_tangent_series_record": (_INT, [_VP]),
+    "swrt_tangent_series_frames": (_I, [_VP]),
+    "swrt_tangent_series_bins": (_INT, [_VP, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_tangent_series_get": (_INT, [_VP, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                       ctypes.POINTER(ctypes.c_int64)]),
+    "swrt_tangent_series_reset": (_INT, [_VP]),
     "swrt_recycle_begin": (_INT, [_VP, _D, _D, _D, _D, ctypes.c_uint64, _I, _INT, _P]),
     "swrt_recycle_apply": (_INT, [_VP]),
     "swrt_recycle_frames": (_I, [_VP]),
@@ -242,10 +255,12 @@ DEBUG_COND_GLOBAL = 20
 DEBUG_TRANS_GLOBAL = 21
 DEBUG_REFR_GLOBAL = 22
 DEBUG_ABSFREQ_GLOBAL = 23
+DEBUG_TANGENT_GLOBAL = 24
 COND_WHICH = {"zeta": 0, "sigma": 1, "D": 2}  # swrt_cond_series_begin's ``which``
 # The class-plane series' tails (PlaneLayout, swrt_packet_state.hpp): sums per
 # omega class, sums per class of the second axis, stats words.
-PLANE_TAILS = {"cond": (0, 1, 2), "trans": (0, 3, 3), "refr": (3, 1, 2), "absfreq": (3, 2, 2)}
+PLANE_TAILS = {"cond": (0, 1, 2), "trans": (0, 3, 3), "refr": (3, 1, 2), "absfreq": (3, 2, 2),
+               "tangent": (3, 1, 3)}
 
 
 def plane_sums_shape(prefix, nw, n2):
@@ -1031,6 +1046,67 @@ class Context:
 
     def recycle_end(self):
         self._chk(self._L.swrt_recycle_end(self._h), "swrt_recycle_end")
+
+    # ---- the tangent map (swrt_tangent_*: the discrete step's derivative along every ray) ----
+    def tangent_begin(self):
+        """Allocate M (= I) and the caustic counters (0) for the current
+        packets, mark serial 1.  Until ``tangent_end`` the leapfrog calls take
+        the per-packet route and carry M; x and k keep their bits."""
+        self._chk(self._L.swrt_tangent_begin(self._h), "swrt_tangent_begin")
+
+    def tangent_mark(self):
+        """M = I, counters 0, the next serial: a new window (queued; no host wait)."""
+        self._chk(self._L.swrt_tangent_mark(self._h), "swrt_tangent_mark")
+
+    def tangent_get(self):
+        """(M (N, 16) float64 row-major, caustics (N,) int32) in the original packet order."""
+        n = self.packets_count()
+        M = np.zeros((n, 16), dtype=np.float64)
+        caustics = np.zeros(n, dtype=np.int32)
+        self._chk(self._L.swrt_tangent_get(self._h, _p(M), caustics.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+                  "swrt_tangent_get")
+        return M, caustics
+
+    def tangent_end(self):
+        self._chk(self._L.swrt_tangent_end(self._h), "swrt_tangent_end")
+
+    def tangent_live(self):
+        return bool(self._L.swrt_tangent_live(self._h) == 1)
+
+    def tangent_serial(self):
+        """The live set's mark serial (0: none)."""
+        return int(self._L.swrt_tangent_serial(self._h))
+
+    def tangent_series_begin(self, f, Cg, omega_edges, growth_edges):
+        """Open a series of (ns + 2) x (nw + 2) count planes: the classes of
+        s = |M|_F^2 / 4 over ``growth_edges`` (ns + 1 increasing values) by the
+        omega classes over ``omega_edges`` (nw + 1).  Empties the series."""
+        wedges = _f64(np.asarray(omega_edges, dtype=np.float64).ravel())
+        gedges = _f64(np.asarray(growth_edges, dtype=np.float64).ravel())
+        self._chk(self._L.swrt_tangent_series_begin(self._h, float(f), float(Cg), _p(wedges), wedges.size - 1,
+                                                    _p(gedges), gedges.size - 1), "swrt_tangent_series_begin")
+
+    def tangent_series_record(self):
+        """Append the live set's frame (queued; no host wait)."""
+        self._chk(self._L.swrt_tangent_series_record(self._h), "swrt_tangent_series_record")
+
+    def tangent_series_frames(self):
+        return int(self._L.swrt_tangent_series_frames(self._h))
+
+    def tangent_series_bins(self):
+        """(nw, ns) of the open series, (0, 0) if none."""
+        return self._plane_bins("tangent")
+
+    def tangent_series_get(self, first=0, count=None):
+        """Recorded frames [first, first + count) -> (counts (count, ns + 2,
+        nw + 2) int64, counts[t, gc, wc]; sums (count, 3 (nw + 2) + (ns + 2))
+        int64: per omega class the sums of e(s), e(|J|) and the caustic
+        counters, then per growth class the caustic counters; stats (count, 3)
+        int64 [n, rejected, mark serial])."""
+        return self._plane_get("tangent", first, count)
+
+    def tangent_series_reset(self):
+        self._chk(self._L.swrt_tangent_series_reset(self._h), "swrt_tangent_series_reset")
 
     # ---- the track series (swrt_track_*: trajectories of chosen packets) ------
     def track_begin(self, ids):

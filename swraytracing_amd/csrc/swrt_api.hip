@@ -441,6 +441,7 @@ int swrt_packets_set(swrt_ctx* c, const double* x, const double* k, int64_t n) {
   if (n != c->n) c->absfreq.drop();  // (the absolute-frequency frames too)
   c->trans.drop();  // the transition series' mark belongs to the packet set it was taken on
   c->recycle.drop();  // (home, gen and born too)
+  if (n != c->n) c->tan.drop();  // (the tangent maps too; with the same N the set is marked below)
   c->n = n;
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(c->pk.cur.x.get(), x, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
@@ -448,6 +449,7 @@ int swrt_packets_set(swrt_ctx* c, const double* x, const double* k, int64_t n) {
     hipLaunchKernelGGL(iota_kernel, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, c->pk.cur.perm.get(), n);
     HIPCHK(c, hipGetLastError());
   }
+  if (c->tan.live && n > 0) HIPCHK_RC(tangent_mark_queue(c));  // new packets: a new window
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->hz.on) {  // every packet stream's work is complete (joined, then synchronised)
     c->hz.quiesce();
@@ -616,6 +618,7 @@ int swrt_advance(swrt_ctx* c, double dt, int64_t nsteps, double f, double gH, in
     return fail(c, SWRT_ERR_ARG,
                 "the FMA gather (swrt_set_gather_mode 1) has the leapfrog step only: set the integrator back to "
                 "(0, 1, 0) or the gather mode to 0");
+  HIPCHK_RC(tangent_step_check(c));
   for (int s = 0; s < nslots; ++s)
     if (!c->slot[s].set) return fail(c, SWRT_ERR_STATE, "field slot not set");
   if (nslots == 2 && (c->slot[1].nx != c->slot[0].nx || c->slot[1].L != c->slot[0].L ||
@@ -652,6 +655,7 @@ int swrt_advance_intervals(swrt_ctx* c, int nintervals, const double* dts, int64
     return fail(c, SWRT_ERR_ARG,
                 "the FMA gather (swrt_set_gather_mode 1) has the leapfrog step only: set the integrator back to "
                 "(0, 1, 0) or the gather mode to 0");
+  HIPCHK_RC(tangent_step_check(c));
   if (save_every < 0 || (save_every > 0 && nsub % save_every))
     return fail(c, SWRT_ERR_ARG, "save_every must divide nsub");
   for (int s = 0; s <= nintervals; ++s) {
@@ -704,6 +708,7 @@ int swrt_leapfrog(swrt_ctx* c, double* x, double* k, int64_t n, double dt, int64
     return fail(c, SWRT_ERR_ARG,
                 "the FMA gather (swrt_set_gather_mode 1) has the leapfrog step only: set the integrator back to "
                 "(0, 1, 0) or the gather mode to 0");
+  HIPCHK_RC(tangent_step_check(c));
   if ((rc = swrt_packets_set(c, x, k, n))) return rc;
   const int64_t se = (hist_x && hist_k) ? save_every : 0;
   if ((rc = swrt_advance(c, dt, nsteps, f, gH, nslots, alpha0, dalpha, bump, se))) return rc;
@@ -807,6 +812,7 @@ int64_t swrt_qg_grid(const swrt_ctx* c, int* nlayers_out) {
 int swrt_xka_step(swrt_ctx* c, double* state5, int64_t n, double C0, double f, double dt, int64_t nsteps,
                   int64_t save_every, double* hist5) {
   if (!c) return SWRT_ERR_ARG;
+  HIPCHK_RC(tangent_refuse(c, "swrt_xka_step"));
   GUARD_BEGIN
   if (!c->xka.nodes) return fail(c, SWRT_ERR_STATE, "call swrt_xka_set_fields first");
   if (n < 0 || nsteps < 0 || save_every < 0) return fail(c, SWRT_ERR_ARG, "negative size");
@@ -1062,6 +1068,7 @@ int swrt_spectral_eval(swrt_ctx* c, const double* x, const double* y, int64_t n,
 int swrt_spectral_leapfrog(swrt_ctx* c, double* x, double* k, int64_t n, double dt, int64_t nsteps, double f,
                            double gH, int precision) {
   if (!c) return SWRT_ERR_ARG;
+  HIPCHK_RC(tangent_refuse(c, "swrt_spectral_leapfrog"));
   GUARD_BEGIN
   if (!c->spec.set) return fail(c, SWRT_ERR_STATE, "call swrt_spectral_set_modes first");
   if (precision != 64 && precision != 32) return fail(c, SWRT_ERR_ARG, "precision must be 64 or 32");
@@ -1812,6 +1819,7 @@ int swrt_recycle_begin(swrt_ctx* c, double f, double Cg, double omega_cut, doubl
 
 int swrt_recycle_apply(swrt_ctx* c) {
   if (!c) return SWRT_ERR_ARG;
+  HIPCHK_RC(tangent_refuse(c, "swrt_recycle_apply"));
   GUARD_BEGIN
   HIPCHK_RC(recycle_check(c));
   HIPCHK(c, hipSetDevice(c->device));
@@ -1974,6 +1982,123 @@ int swrt_absfreq_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* 
 
 int swrt_absfreq_series_reset(swrt_ctx* c) { return plane_series_reset(c, &swrt_ctx::absfreq); }
 
+// ---- the tangent map (swrt_tangent.hpp, swrt_host_packets.hpp, swrt_host_diag.hpp) ----
+int swrt_tangent_begin(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(packets_check(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  TangentState& ts = c->tan;
+  ts.live = false;
+  if (c->n != ts.n || !ts.M) {  // (releasing the old buffers waits for their queued users)
+    if (c->hz.on) {
+      c->hz.bufs.erase(ts.M.get());
+      c->hz.bufs.erase(ts.caustics.get());
+    }
+    ts.n = 0;
+    HIPCHK(c, ts.M.alloc((size_t)kTanM * c->n));
+    HIPCHK(c, ts.caustics.alloc(c->n));
+    ts.n = c->n;
+    if (c->hz.on) {
+      c->hz.name(ts.M.get(), "tangent maps");
+      c->hz.name(ts.caustics.get(), "caustic counters");
+    }
+  }
+  ts.serial = 0;
+  HIPCHK_RC(tangent_mark_queue(c));  // serial 1
+  ts.live = true;
+  c->bin.invalidate();  // the per-packet route's binning from here on
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_tangent_mark(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(tangent_check(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  return tangent_mark_queue(c);
+  GUARD_END(c)
+}
+
+int swrt_tangent_get(swrt_ctx* c, double* M16_out, int32_t* caustics_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  HIPCHK_RC(tangent_check(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  const TangentState& ts = c->tan;
+  if (M16_out)
+    HIPCHK(c, hipMemcpyAsync(M16_out, ts.M.get(), sizeof(double) * kTanM * ts.n, hipMemcpyDeviceToHost, c->stream));
+  if (caustics_out)
+    HIPCHK(c, hipMemcpyAsync(caustics_out, ts.caustics.get(), sizeof(int32_t) * ts.n, hipMemcpyDeviceToHost,
+                             c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return dev_err_check(c);
+  GUARD_END(c)
+}
+
+int swrt_tangent_end(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  TangentState& ts = c->tan;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // nothing queued uses the buffers below any more
+  hz_synced(c);
+  if (c->hz.on) {
+    c->hz.bufs.erase(ts.M.get());
+    c->hz.bufs.erase(ts.caustics.get());
+  }
+  ts.live = false;
+  ts.n = 0;
+  ts.serial = 0;
+  ts.M.reset();
+  ts.caustics.reset();
+  c->bin.invalidate();  // back to the route the settings name
+  return SWRT_OK;
+  GUARD_END(c)
+}
+
+int swrt_tangent_live(const swrt_ctx* c) { return c ? (c->tan.live ? 1 : 0) : -1; }
+
+int64_t swrt_tangent_serial(const swrt_ctx* c) { return c ? (c->tan.live ? c->tan.serial : 0) : -1; }
+
+int swrt_tangent_series_begin(swrt_ctx* c, double f, double Cg, const double* omega_edges, int64_t nw,
+                              const double* growth_edges, int64_t ns) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  return plane_series_begin(c, c->tan, f, Cg, omega_edges, nw, growth_edges, ns, 0,
+                            "(ns + 2) * (nw + 2) must be at most 65536", nullptr, [] {});
+  GUARD_END(c)
+}
+
+int swrt_tangent_series_record(swrt_ctx* c) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  if (!c->tan.open) return fail(c, SWRT_ERR_STATE, "call swrt_tangent_series_begin first");
+  HIPCHK_RC(tangent_check(c));
+  if (c->n > kTanMaxPackets) return fail(c, SWRT_ERR_ARG, "a tangent frame takes at most 2^24 packets");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK_RC(plane_reserve_zeroed(c, c->tan, 1));
+  return tangent_record_launch(c);
+  GUARD_END(c)
+}
+
+int64_t swrt_tangent_series_frames(const swrt_ctx* c) { return plane_series_frames(c, &swrt_ctx::tan); }
+
+int swrt_tangent_series_bins(const swrt_ctx* c, int64_t* nw_out, int64_t* ns_out) {
+  return plane_series_bins(c, &swrt_ctx::tan, nw_out, ns_out);
+}
+
+int swrt_tangent_series_get(swrt_ctx* c, int64_t first, int64_t count, int64_t* counts_out, int64_t* sums_out,
+                            int64_t* stats3_out) {
+  if (!c) return SWRT_ERR_ARG;
+  GUARD_BEGIN
+  return plane_series_get(c, c->tan, first, count, counts_out, sums_out, stats3_out);
+  GUARD_END(c)
+}
+
+int swrt_tangent_series_reset(swrt_ctx* c) { return plane_series_reset(c, &swrt_ctx::tan); }
+
 int swrt_check_arith(swrt_ctx* c, int64_t n, uint64_t seed, int64_t* mismatches3) {
   if (!c) return SWRT_ERR_ARG;
   GUARD_BEGIN
@@ -2061,6 +2186,10 @@ int swrt_debug_set(swrt_ctx* c, int key, int64_t value) {
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "absolute-frequency series path must be 0 or 1");
       c->dbg.absfreq_global = value != 0;
       return SWRT_OK;
+    case SWRT_DEBUG_TANGENT_GLOBAL:
+      if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "tangent series path must be 0 or 1");
+      c->dbg.tangent_global = value != 0;
+      return SWRT_OK;
     case SWRT_DEBUG_QG_UPDATE_COLS:
       if (value != 0 && value != 1) return fail(c, SWRT_ERR_ARG, "QG update/column-pass fusion must be 0 or 1");
       if (c->qg.spec) return fail(c, SWRT_ERR_STATE, "a speculative QG step is pending (swrt_qg_resolve first)");
@@ -2103,6 +2232,7 @@ int swrt_debug_get(swrt_ctx* c, int key, int64_t* value_out) {
     case SWRT_DEBUG_TRANS_GLOBAL: *value_out = c->dbg.trans_global ? 1 : 0; return SWRT_OK;
     case SWRT_DEBUG_REFR_GLOBAL: *value_out = c->dbg.refr_global ? 1 : 0; return SWRT_OK;
     case SWRT_DEBUG_ABSFREQ_GLOBAL: *value_out = c->dbg.absfreq_global ? 1 : 0; return SWRT_OK;
+    case SWRT_DEBUG_TANGENT_GLOBAL: *value_out = c->dbg.tangent_global ? 1 : 0; return SWRT_OK;
     case SWRT_DEBUG_MAP_STRAYS: {  // the device's counter: waits for the queued records
       unsigned long long v = 0;
       if (c->map.strays) {
@@ -2588,6 +2718,7 @@ int swrt_swap_slots(swrt_ctx* c, int a, int b) {
 int swrt_ode23_f1(swrt_ctx* c, double t, double tmax, double f, double Cg, int nslots, double thr, double bump,
                   double* rh_raw_out) {
   if (!c) return SWRT_ERR_ARG;
+  HIPCHK_RC(tangent_refuse(c, "swrt_ode23_f1"));
   GUARD_BEGIN
   HIPCHK_RC(lost_check(c));
   SlotUse slot_use(c, false, kSlots01);
@@ -2600,6 +2731,7 @@ int swrt_ode23_f1(swrt_ctx* c, double t, double tmax, double f, double Cg, int n
 int swrt_ode23_attempt(swrt_ctx* c, double t, double h, double tnew, double tmax, double f, double Cg,
                        int nslots, double thr, double bump, double* err_raw_out) {
   if (!c) return SWRT_ERR_ARG;
+  HIPCHK_RC(tangent_refuse(c, "swrt_ode23_attempt"));
   GUARD_BEGIN
   HIPCHK_RC(lost_check(c));
   SlotUse slot_use(c, false, kSlots01);
@@ -2611,6 +2743,7 @@ int swrt_ode23_attempt(swrt_ctx* c, double t, double h, double tnew, double tmax
 
 int swrt_ode23_accept(swrt_ctx* c) {
   if (!c) return SWRT_ERR_ARG;
+  HIPCHK_RC(tangent_refuse(c, "swrt_ode23_accept"));
   c->s0_dirty = true;  // (conservative: settings and syncs may precede packet-stream work)
   if (c->in_hook) return fail(c, SWRT_ERR_STATE, "this call may touch the packets: not allowed inside an ode23 hook");
   HIPCHK_RC(lost_check(c));
@@ -2631,6 +2764,7 @@ int swrt_ode23_set_dense(swrt_ctx* c, int on) {
 
 int swrt_ode23_ntrp(swrt_ctx* c, double t, double tnew, const double* tout, int64_t nout) {
   if (!c) return SWRT_ERR_ARG;
+  HIPCHK_RC(tangent_refuse(c, "swrt_ode23_ntrp"));
   HOOK_REFUSE
   // (reads the packets and the stage buffers only: whatever dropped the chain
   // since the attempt also ended the attempt's validity)
@@ -2658,6 +2792,7 @@ int swrt_ode23_run_at(swrt_ctx* c, const double* tspan, int64_t nt, double tmax,
                       double rtol, double atol, double bump, double* ts_out, int64_t ts_cap, int64_t* nts_out,
                       int64_t* stats3_out) {
   if (!c) return SWRT_ERR_ARG;
+  HIPCHK_RC(tangent_refuse(c, "swrt_ode23_run_at"));
   if (!tspan) return fail(c, SWRT_ERR_ARG, "tspan is NULL");
   if (nt < 2) return fail(c, SWRT_ERR_ARG, "tspan needs at least two times");
   if (!ts_out || ts_cap < 1 || !nts_out) return fail(c, SWRT_ERR_ARG, "ts_out / ts_cap / nts_out");
@@ -2717,6 +2852,7 @@ int swrt_ode23_run_sharded(swrt_ctx* c, double t0, double tfinal, double tmax, d
                            int64_t* stats3_out, void (*hook)(void*), void* hook_user,
                            int (*reduce)(double*, void*), void* reduce_user) {
   if (!c) return SWRT_ERR_ARG;
+  HIPCHK_RC(tangent_refuse(c, "swrt_ode23_run_sharded"));
   if (!ts_out || ts_cap < 1 || !nts_out) return fail(c, SWRT_ERR_ARG, "ts_out / ts_cap / nts_out");
   if (c->in_hook) return fail(c, SWRT_ERR_STATE, "an ode23 hook may not start another ode23 call");
   GUARD_BEGIN_KEEP_CHAIN

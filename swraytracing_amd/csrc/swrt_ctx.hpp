@@ -454,6 +454,22 @@ struct AbsfreqSeriesState : PlaneSeriesState {
   void drop() { series.ext.cleared(); }  // the ensemble changed size: the frames describe another one
 };
 
+// the tangent map (swrt_tangent_*, swrt_tangent.hpp).  M and the caustic
+// counters (by original index) belong to the packet set: swrt_packets_set with
+// another N drops them (live), with the same N marks.  While live, the
+// leapfrog calls take the per-packet route and launch the tangent kernel.  The
+// series (3 sums per omega class, 1 per growth class, [n, rejected, serial])
+// keeps its frames like the other class-plane series.
+struct TangentState : PlaneSeriesState {
+  TangentState() : PlaneSeriesState(3, 1, 3) {}
+  bool live = false;        // M and caustics describe the current packet set
+  int64_t n = 0;            // packets they were allocated for
+  int64_t serial = 0;       // marks since begin (begin's is 1)
+  DevBuf<double> M;         // n x 16
+  DevBuf<int> caustics;     // n
+  void drop() { live = false; }  // another packet set: the maps describe the old one
+};
+
 // packet recycling (swrt_recycle_*, swrt_recycle.hpp).  The per-packet state
 // (home, gen, born, by original index) belongs to the packet set:
 // swrt_packets_set drops it (live), the recorded frames stay readable until
@@ -490,6 +506,7 @@ struct DebugKnobs {
   bool trans_global = false; // SWRT_DEBUG_TRANS_GLOBAL: the transition series' global kernel for every shape
   bool refr_global = false; // SWRT_DEBUG_REFR_GLOBAL: the refraction series' global kernel for every shape
   bool absfreq_global = false; // SWRT_DEBUG_ABSFREQ_GLOBAL: the absolute-frequency series' global kernel for every shape
+  bool tangent_global = false; // SWRT_DEBUG_TANGENT_GLOBAL: the tangent series' global kernel for every shape
 };
 }  // namespace
 
@@ -566,6 +583,7 @@ struct swrt_ctx {
   TransSeriesState trans;
   RefrSeriesState refr;
   AbsfreqSeriesState absfreq;
+  TangentState tan;
   RecycleState recycle;
   // the packet stream got work since the last split launch's part 0 that the
   // next split launch's part 1 (on sx[0]) must follow: that launch forks (an

@@ -822,4 +822,61 @@ int absfreq_launch(swrt_ctx* c, int slot_a, int slot_b, double alpha, const doub
   return plane_launch(c, as, absfreq_kernel<true>, absfreq_kernel<false>, lds, bytes, shape, a, count);
 }
 
+// ---- the tangent map ----
+static_assert(kTanWSums == kRefrWSums && kTanStats == 3,
+              "TangentState's PlaneLayout (swrt_ctx.hpp) and refr_lds_bytes restate what tangent_record_kernel writes");
+
+// A mark, queued: M = I, the counters 0, a new serial.
+int tangent_mark_queue(swrt_ctx* c) {
+  TangentState& ts = c->tan;
+  if (c->hz.on) {
+    HazardChecker& h = c->hz;
+    if (!hz_whole(h, h.op(0), kHzWrite, "a tangent mark", {ts.M.get(), ts.caustics.get()}))
+      return fail(c, SWRT_ERR_STATE, h.err);
+  }
+  hipLaunchKernelGGL(tangent_mark_kernel, dim3(nblocks(ts.n * kTanM, kTanThreads)), dim3(kTanThreads), 0, c->stream, ts.n,
+                     TangentArgs{ts.M.get(), ts.caustics.get()});
+  HIPCHK(c, hipGetLastError());
+  ++ts.serial;
+  return SWRT_OK;
+}
+
+// The calls that need a live set.
+int tangent_check(swrt_ctx* c) {
+  if (!c->tan.live) return fail(c, SWRT_ERR_STATE, "no tangent set is live (swrt_tangent_begin first)");
+  return packets_check(c);
+}
+
+// One frame at the series' end from the current packets and their M rows: the
+// LDS kernel for refr_lds_form's shapes (the tail has the refraction series'
+// shape), the global one beyond (or when SWRT_DEBUG_TANGENT_GLOBAL says so).
+int tangent_record_launch(swrt_ctx* c) {
+  TangentState& ts = c->tan;
+  TangentRecordArgs a;
+  a.k = c->pk.cur.k.get();
+  a.perm = c->pk.cur.perm.get();
+  a.M = ts.M.get();
+  a.caustics = ts.caustics.get();
+  a.n = c->n;
+  a.f2 = ts.f2;
+  a.Cg2 = ts.Cg2;
+  a.wedges = ts.edges.get();
+  a.sedges = ts.edges.get() + ts.lay.nw + 1;
+  a.nw = ts.lay.nw;
+  a.ns = ts.lay.n2;
+  a.serial = (unsigned long long)ts.serial;
+  a.counts = ts.series.end_a(ts.lay.frame());
+  a.tail = ts.series.end_b(ts.lay.tail());
+  if (c->hz.on) {
+    HazardChecker& h = c->hz;
+    if (!hz_whole(h, h.op(0), kHzRead, "a tangent record", {a.k, a.perm, a.M, a.caustics}))
+      return fail(c, SWRT_ERR_STATE, h.err);
+  }
+  const bool lds = !c->dbg.tangent_global && refr_lds_form(ts.lay.nw, ts.lay.n2);
+  const size_t bytes = refr_lds_bytes(ts.lay.nw, ts.lay.n2, lds);
+  const PlaneLaunchShape shape = {kTanThreads, kRefrMaxLdsBytes, kRefrBlocks, kRefrBigPlaneBlocks, kRefrHugeTailBlocks,
+                                  kRefrBigPlaneBytes, kRefrLdsFormBytes};
+  return plane_launch(c, ts, tangent_record_kernel<true>, tangent_record_kernel<false>, lds, bytes, shape, a, 1);
+}
+
 }  // namespace

@@ -15,10 +15,12 @@
 #include "swrt_share.hpp"
 #include "swrt_xka.hpp"
 #include "swrt_spectral.hpp"
+#include "swrt_tangent.hpp"
 
 namespace {
 
 bool use_tile_kernel(const swrt_ctx* c) {
+  if (c->tan.live) return false;  // a live tangent set: the per-packet route carries M (swrt_tangent.hpp)
   if (c->rebin_every <= 0) return false;
   if (c->kernel == 2) return true;
   return c->kernel == 0 && c->slot[0].nx >= 2 * kTile;
@@ -243,6 +245,35 @@ using LeapStageKernel = void (*)(StepArgs, StageArgs);
 LeapStageKernel leap_stage_kernel(int nslots) {
   return nslots == 2 ? leapfrog_stage_kernel<true> : leapfrog_stage_kernel<false>;
 }
+// ... and the form that carries the tangent map (swrt_tangent_begin)
+using LeapTangentKernel = void (*)(StepArgs, TangentArgs);
+LeapTangentKernel leap_tangent_kernel(int nslots) {
+  return nslots == 2 ? leapfrog_tangent_kernel<true> : leapfrog_tangent_kernel<false>;
+}
+TangentArgs tangent_args(const swrt_ctx* c) { return TangentArgs{c->tan.M.get(), c->tan.caustics.get()}; }
+
+// The leapfrog calls' check while a tangent set is live: M is the derivative
+// of the default step with its mul-then-add sums.
+int tangent_step_check(swrt_ctx* c) {
+  if (!c->tan.live) return SWRT_OK;
+  if (!default_integrator(c))
+    return fail(c, SWRT_ERR_ARG,
+                "a tangent set is live: the tangent map has the leapfrog step only (set the integrator back to "
+                "(0, 1, 0) or call swrt_tangent_end)");
+  if (c->gather_mode == 1)
+    return fail(c, SWRT_ERR_ARG,
+                "a tangent set is live: the tangent map has the mul-then-add gather only (set the gather mode to 0 "
+                "or call swrt_tangent_end)");
+  return SWRT_OK;
+}
+
+// The calls that move packets some other way, while a tangent set is live.
+int tangent_refuse(swrt_ctx* c, const char* call) {
+  if (!c->tan.live) return SWRT_OK;
+  return fail(c, SWRT_ERR_STATE,
+              std::string(call) + ": a tangent set is live and this call would move packets without their tangent "
+                                  "maps (swrt_tangent_end first)");
+}
 
 // Counting-sort the packets by spatial tile of slot 0's grid (swrt_bin.hpp).
 // indirect: only build the source index of the binned order (c->src_idx);
@@ -412,11 +443,14 @@ int leap_launch(swrt_ctx* c, const StepArgs& a, unsigned grid) {
     const uint64_t t = h.op(0);
     const char* what = "the per-packet leapfrog launch";
     if (!(hz_whole(h, t, kHzWrite, what, {a.x, a.k}) && hz_whole(h, t, kHzRead, what, {a.perm}) &&
-          hz_whole(h, t, kHzWrite, what, {a.hist_x, a.hist_k})))
+          hz_whole(h, t, kHzWrite, what, {a.hist_x, a.hist_k}) &&
+          (!c->tan.live || hz_whole(h, t, kHzWrite, what, {c->tan.M.get(), c->tan.caustics.get()}))))
       return fail(c, SWRT_ERR_STATE, h.err);
   }
   c->bin.per_packet_launched();
-  if (!default_integrator(c)) {
+  if (c->tan.live) {  // (tangent_step_check: the default step)
+    launch_k(c, leap_tangent_kernel(a.nslots), dim3(grid), dim3(256), a, tangent_args(c));
+  } else if (!default_integrator(c)) {
     launch_k(c, leap_stage_kernel(a.nslots), dim3(grid), dim3(256), a, stage_args(c));
   } else if (c->kev1) {  // a timed launch: the dispatch stamps the events
     launch_k(c, leap_kernel(a.nslots), dim3(grid), dim3(256), a);

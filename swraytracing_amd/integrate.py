@@ -283,6 +283,65 @@ def combine_absfreqs(parts):
                           "and stats (T, 2)"))
 
 
+def combine_tangents(parts):
+    """The tangent series of an ensemble from its shards' series
+    (swrt_tangent_series_*).  ``parts``: a sequence of (counts, sums, stats)
+    triples, one per shard, counts (T, ns + 2, nw + 2) int64, sums
+    (T, 3 (nw + 2) + (ns + 2)) int64 and stats (T, 3) int64 [n, rejected, mark
+    serial]: counts, sums, n and rejected add (integer, exact and order-free);
+    the serial is the shards' common one.  Frames whose shards marked a
+    different number of times describe different windows and are refused.  A
+    shard without packets stands as zeros (its serial does not count)."""
+    counts, sums, stats = _stack_planes(
+        parts, "tangent", "every shard must give counts (T, ns + 2, nw + 2), sums (T, 3 (nw + 2) + (ns + 2)) "
+                          "and stats (T, 3)")
+    holds = stats[..., 0] > 0                       # (shard, frame): the shard had packets
+    serial = np.where(holds, stats[..., 2], 0).max(axis=0)
+    if np.any(holds & (stats[..., 2] != serial[None, :])):
+        raise ValueError("the shards' mark serials differ: their frames describe different windows")
+    out = stats.sum(axis=0)
+    out[..., 2] = serial
+    return counts.sum(axis=0), sums.sum(axis=0), out
+
+
+def tangent_growth(counts, sums, stats, tau):
+    """Growth figures of tangent frames counts (..., ns + 2, nw + 2), sums
+    (..., 3 (nw + 2) + (ns + 2)) and stats (..., 3) int64, as fp64; ``tau`` the
+    time since the frame's mark (a scalar or (...)).  Per omega class: ``n``
+    (..., nw + 2) its packets, ``log2_stretch_mean`` the mean of e(s) =
+    floor(log2(|M|_F^2 / 4)), ``lyapunov`` = (ln 2 / 2) <e(s)> / tau the
+    finite-time Lyapunov estimate (|M| ~ exp(lambda tau)), ``log2_amplitude_mean``
+    the mean log2 of 1/|J| (the wave-action density's growth, -<e(|J|)>) and
+    ``caustics_mean`` the caustic crossings per packet.  Per growth class:
+    ``n_growth`` (..., ns + 2) and ``caustics_mean_growth``.  ``accepted`` (...)
+    is n - rejected.  The means are NaN where the class is empty."""
+    counts = np.asarray(counts)
+    sums = np.asarray(sums)
+    stats = np.asarray(stats)
+    if counts.ndim < 2:
+        raise ValueError("counts must be (..., ns + 2, nw + 2)")
+    nss, nws = counts.shape[-2:]
+    if sums.shape != counts.shape[:-2] + (3 * nws + nss,) or stats.shape != counts.shape[:-2] + (3,):
+        raise ValueError("counts must be (..., ns + 2, nw + 2), sums (..., 3 (nw + 2) + (ns + 2)) and stats (..., 3)")
+    tau = np.asarray(tau, dtype=np.float64)
+    if np.any(~(tau > 0)):
+        raise ValueError("tau must be positive")
+    n = counts.sum(axis=-2).astype(np.float64)
+    empty = n == 0
+    count = np.where(empty, 1.0, n)
+    es, ej, cz = (sums[..., j * nws:(j + 1) * nws].astype(np.float64) / count for j in range(3))
+    lyap = (np.log(2.0) / 2.0) * es / tau[..., None]
+    amp = -ej
+    for a in (es, lyap, amp, cz):
+        a[empty] = np.nan
+    n_g = counts.sum(axis=-1).astype(np.float64)
+    empty_g = n_g == 0
+    cz_g = sums[..., 3 * nws:].astype(np.float64) / np.where(empty_g, 1.0, n_g)
+    cz_g[empty_g] = np.nan
+    return dict(n=n, log2_stretch_mean=es, lyapunov=lyap, log2_amplitude_mean=amp, caustics_mean=cz,
+                n_growth=n_g, caustics_mean_growth=cz_g, accepted=(stats[..., 0] - stats[..., 1]).astype(np.float64))
+
+
 def absfreq_rates(counts, sums, stats, frac_bits):
     """Rates of absolute-frequency frames counts (..., no + 2, nw + 2), sums
     (..., 3 (nw + 2) + 2 (no + 2)) and stats (..., 2) int64, as fp64.  Per
@@ -527,7 +586,8 @@ def _host_stage(xc, kc, h, f, gH, scheme, midpoint, iters):
     return x2 + hh * gv(k2), k2
 
 
-def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False, method="leapfrog", iterations=None):
+def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False, method="leapfrog", iterations=None,
+                   tangent=False):
     """[x, k, t] = ode_symplectic(x0, k0, dt, T, f, gH, scheme).
 
     ``method``: "leapfrog" (default: ode_symplectic.m:13-37, whose Euler kick
@@ -545,7 +605,13 @@ def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False, method="leap
     series of swrt_raydiag frames — row i belongs to x[i], k[i]; row 0 is the
     initial state, where Omega_0 is marked (symplectic_full_fourier.m:41,54-57:
     solver_error against t).  The packets then advance one step per call with
-    a frame recorded on the device after each; x, k and t are the same bits."""
+    a frame recorded on the device after each; x, k and t are the same bits.
+
+    ``tangent`` (GPU-backed schemes, method "leapfrog", not with
+    ``diagnostics``): two more values, the final tangent map M (P x 4 x 4,
+    d(x, y, k, l)/d(x0, y0, k0, l0) of the discrete map over all the steps) and
+    the caustic counters (P,) int32 (swrt_tangent_*); x, k and t are the same
+    bits."""
     x0 = np.asarray(x0, dtype=np.float64)
     k0 = np.asarray(k0, dtype=np.float64)
     if x0.ndim == 2:
@@ -559,6 +625,11 @@ def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False, method="leap
     gpu = isinstance(scheme, (SpectralScheme, SnapshotPairScheme))
     if diagnostics and not gpu:
         raise ValueError("diagnostics needs a GPU-backed scheme (SpectralScheme / SnapshotPairScheme)")
+    if tangent and (not gpu or diagnostics or method != "leapfrog"):
+        raise ValueError('tangent needs a GPU-backed scheme, method="leapfrog" and diagnostics=False')
+    if Nsteps <= 1 and tangent:
+        x[:Nsteps], k[:Nsteps] = x0[0], k0[0]
+        return x, k, t, np.tile(np.eye(4), (P, 1, 1)), np.zeros(P, dtype=np.int32)
     if Nsteps == 0:
         return (x, k, t, np.zeros((0, 8))) if diagnostics else (x, k, t)
     x[0] = x0[0]
@@ -571,6 +642,8 @@ def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False, method="leap
         before = ctx.get_integrator()
         ctx.set_integrator(kick, iters, comp)
         try:
+            if tangent:
+                return _ode_symplectic_tangent(ctx, scheme, x, k, t, x0, k0, dt, Nsteps, f, gH)
             return _ode_symplectic_gpu(ctx, scheme, x, k, t, x0, k0, dt, Nsteps, f, gH, diagnostics)
         finally:
             ctx.set_integrator(*before)
@@ -583,6 +656,20 @@ def ode_symplectic(x0, k0, dt, T, f, gH, scheme, diagnostics=False, method="leap
         x[i] = xc[0]
         k[i] = kc[0]
     return x, k, t
+
+
+def _ode_symplectic_tangent(ctx, scheme, x, k, t, x0, k0, dt, Nsteps, f, gH):
+    """ode_symplectic with the tangent map carried beside the packets."""
+    nslots = 1 if isinstance(scheme, SpectralScheme) else 2
+    ctx.packets_set(np.asfortranarray(x0[0].T), np.asfortranarray(k0[0].T))  # (starts a new history)
+    ctx.tangent_begin()
+    try:
+        ctx.advance(dt, Nsteps - 1, f, gH, nslots=nslots, alpha0=0.0, dalpha=0.0, bump=scheme.bump, save_every=1)
+        x[1:], k[1:] = ctx.history()
+        M, caustics = ctx.tangent_get()
+    finally:
+        ctx.tangent_end()
+    return x, k, t, M.reshape(-1, 4, 4), caustics
 
 
 def _ode_symplectic_gpu(ctx, scheme, x, k, t, x0, k0, dt, Nsteps, f, gH, diagnostics):
@@ -978,7 +1065,8 @@ class _KmapRecorder(_Recorder):
 
 
 class _PlaneRecorder(_Recorder):
-    """The four class-plane series: ``prefix`` names the context's calls and
+    """The class-plane series (cond, trans, refr, absfreq, tangent; at most 4096
+    classes an axis and 65536 cells a frame): ``prefix`` names the context's calls and
     the files, ``head`` leads <prefix>_geom.bin before the second axis' edges
     and the omega edges."""
     ndev = 3
@@ -1506,6 +1594,75 @@ class PacketEnsemble:
         omega edges).  Sharded: a collective; rank 0 writes.  Returns the
         frames recorded."""
         return self._recorder("trans", "write_trans").write("write_trans", directory)
+
+    def begin_tangent(self, omega_edges, growth_edges, directory=None, t=None):
+        """Start carrying the tangent map (swrt_tangent_begin: M = I, the
+        caustic counters 0; from here on the leapfrog calls take the per-packet
+        route, x and k keep their bits) and open its series with the
+        ensemble's f, Cg: the classes of s = |M|_F^2 / 4 over ``growth_edges``
+        by the omega classes over ``omega_edges``.  ``t``: the time of this
+        first mark, kept for tangent_time.bin.  ``directory``: where
+        record_tangent drains the device series when it grows large (default:
+        the drained frames wait in host memory for write_tangents)."""
+        wedges, gedges, _ = _plane_args(omega_edges, growth_edges, 0, "growth", "tangent series", "a tangent", "ns")
+        head = [gedges.size - 1, wedges.size - 1]
+        rec = _TransRecorder(self, directory, "tangent", wedges, gedges, 0, head, combine_tangents)
+        rec.t_mark = np.nan if t is None else float(t)
+        self._recorders["tangent"] = rec
+        if self.n > 0:
+            self.ctx.tangent_begin()
+            self.ctx.tangent_series_begin(self.f, self.Cg, wedges, gedges)
+
+    def mark_tangent(self, t=None):
+        """A new window: M = I, the counters 0, the next mark serial (queued, no
+        host wait).  Every rank calls it at the same frame, so the shards'
+        serials agree."""
+        rec = self._recorder("tangent", "mark_tangent")
+        if self.n > 0:
+            self.ctx.tangent_mark()
+        rec.t_mark = np.nan if t is None else float(t)
+
+    def record_tangent(self, t=None):
+        """Append this shard's tangent frame at the current state to the
+        device-side series (queued, no host wait).  An empty shard records
+        nothing.  Drained like the transition series' frames."""
+        rec = self._recorder("tangent", "record_tangent")
+        rec.times.append((np.nan if t is None else float(t), rec.t_mark))
+        rec.record(self.ctx.tangent_series_record)
+
+    def tangent_series(self):
+        """(counts (T, ns + 2, nw + 2), sums (T, 3 (nw + 2) + (ns + 2)), stats
+        (T, 3)), all int64, and times (T, 2) fp64 [t, t_mark] of the ensemble's
+        frames still held.  Sharded: a collective; rank 0 gets
+        combine_tangents() of the shards' frames, the others None."""
+        return self._recorder("tangent", "tangent_series").series("tangent_series")
+
+    def tangent_state(self):
+        """(M (n, 16) row-major, caustics (n,) int32) of this shard's packets in
+        their original order (swrt_tangent_get; waits)."""
+        self._recorder("tangent", "tangent_state")
+        if self.n == 0:
+            return np.zeros((0, 16)), np.zeros(0, dtype=np.int32)
+        return self.ctx.tangent_get()
+
+    def end_tangent(self):
+        """Stop carrying the tangent map (swrt_tangent_end); the series' frames
+        already drained or written stay."""
+        self._recorder("tangent", "end_tangent")
+        if self.n > 0 and self.ctx.tangent_live():
+            self.ctx.tangent_end()
+
+    def write_tangents(self, directory):
+        """The run's tangent series as raw native-endian files:
+        tangent_hist.bin (int64, one (ns + 2) x (nw + 2) plane per frame, cell
+        (gc, wc) at gc*(nw + 2) + wc), tangent_sums.bin (3 (nw + 2) + (ns + 2)
+        int64 per frame: per omega class the sums of e(s), e(|J|) and the
+        caustic counters, then per growth class the caustic counters),
+        tangent_stats.bin (3 int64 per frame: n, rejected, mark serial),
+        tangent_time.bin (2 doubles per frame: t, t_mark) and tangent_geom.bin
+        (doubles [ns, nw], the ns + 1 growth edges, the nw + 1 omega edges).
+        Sharded: a collective; rank 0 writes.  Returns the frames recorded."""
+        return self._recorder("tangent", "write_tangents").write("write_tangents", directory)
 
     def begin_recycle(self, omega_cut, seed=0, frac_bits=20, directory=None, every=1):
         """Begin recycling this run's packets (swrt_recycle_begin with the

@@ -15,6 +15,7 @@ drivers built on them.
 """
 from __future__ import annotations
 
+import functools
 import math
 import numbers
 import os
@@ -352,7 +353,8 @@ def _fresh_outputs(out_dir, fresh):
                  "track_ids", "kmap_n", "kmap_stats", "kmap_geom", "flow_spec", "flow_stats", "flow_geom", "cond_hist",
                  "cond_sums", "cond_stats", "cond_geom", "trans_hist", "trans_sums", "trans_stats", "trans_time",
                  "trans_geom", "recycle_stats", "recycle_time", "recycle_geom", "recycle_gen", "refr_hist", "refr_sums",
-                 "refr_stats", "refr_geom", "absfreq_hist", "absfreq_sums", "absfreq_stats", "absfreq_geom"):
+                 "refr_stats", "refr_geom", "absfreq_hist", "absfreq_sums", "absfreq_stats", "absfreq_geom", "tangent_hist",
+                 "tangent_sums", "tangent_stats", "tangent_time", "tangent_geom"):
         p = os.path.join(out_dir, name + ".bin")
         if os.path.exists(p):
             os.remove(p)
@@ -476,6 +478,52 @@ def _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges):
     return edges, _plane_frac_bits(
         "absfreq_frac_bits", absfreq_frac_bits, edges, spectrum_edges,
         "absfreq_edges: at most 4096 classes and (no + 2) * (nbins + 2) <= 65536 cells a frame")
+
+
+def _tangent_args(tangent_edges, tangent_lag, spectrum_edges, integrator, packet_method, recycle_omega, Npackets):
+    """The drivers' ``tangent_edges`` / ``tangent_lag`` checked before anything
+    runs: (growth edges, lag), or None without ``tangent_edges``.  The omega
+    classes are the run's ``spectrum_edges``; the tangent map has the leapfrog
+    step only and does not follow recycled packets."""
+    if tangent_edges is None:
+        if tangent_lag != 1:
+            raise ValueError("tangent_lag needs tangent_edges")
+        return None
+    edges = _plane_edges(spectrum_edges, "tangent_edges needs spectrum_edges: they are the tangent series' omega classes",
+                         "tangent_edges", tangent_edges)
+    _plane_frac_bits("tangent", 0, edges, spectrum_edges,
+                     "tangent_edges: at most 4096 classes and (ns + 2) * (nbins + 2) <= 65536 cells a frame")
+    if isinstance(tangent_lag, (bool, np.bool_)) or not isinstance(tangent_lag, numbers.Integral) or tangent_lag < 1:
+        raise ValueError("tangent_lag must be an integer >= 1")
+    if integrator == "ode23":
+        raise ValueError('tangent_edges: the tangent map belongs to integrator="leapfrog"')
+    if packet_method != "leapfrog":
+        raise ValueError('tangent_edges: the tangent map has packet_method="leapfrog" only')
+    if recycle_omega is not None:
+        raise ValueError("tangent_edges: the tangent map does not follow recycled packets (leave recycle_omega out)")
+    if Npackets <= 0:
+        raise ValueError("the tangent series needs packets")
+    return edges, int(tangent_lag)
+
+
+def _ends_tangent(driver):
+    """A driver that leaves the caller's context without a live tangent set
+    when it raises in mid-run (the normal path ends it itself): the context
+    would stay on the per-packet route and refuse the ode23, xka, spectral and
+    recycle calls."""
+    @functools.wraps(driver)
+    def run(*args, ctx=None, **kw):
+        try:
+            return driver(*args, ctx=ctx, **kw)
+        except BaseException:
+            if ctx is not None and kw.get("tangent_edges") is not None:
+                try:
+                    if ctx.tangent_live():
+                        ctx.tangent_end()
+                except Exception:  # (the run's own error is the one to report)
+                    pass
+            raise
+    return run
 
 
 def _packet_method_args(packet_method, packet_iterations, integrator):
@@ -615,7 +663,7 @@ def _track_args(track_ids, track_every, Npackets, default_every):
 
 
 def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False, conds=False, trans=None, index=0,
-                refrs=False, absfreq=None):
+                refrs=False, absfreq=None, tangent=None):
     """One packet frame: its spectrum, its map, its k-plane, its conditional
     spectrum and its refraction frame (both in the flow of slot 0, the snapshot
     at the packets' time), its absolute-frequency frame (``absfreq``: the
@@ -625,7 +673,8 @@ def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False
     transition frame recorded on the device (queued, no host wait) whether or
     not the frame itself is written.  ``trans``: the run's lag (0: never
     re-marked); packet frame ``index`` records against the mark, and re-marks
-    after the record when the lag divides its index."""
+    after the record when the lag divides its index.  ``tangent``: the tangent
+    series' lag, likewise (None: no tangent series)."""
     if spectrum:
         ens.record_spectrum()
     if maps:
@@ -642,6 +691,10 @@ def _save_frame(ens, t, out_dir, spectrum, packet_files, maps=False, kmaps=False
         ens.record_trans(t)
         if trans and index % trans == 0:
             ens.mark_trans(t=t)
+    if tangent is not None:
+        ens.record_tangent(t)
+        if index % tangent == 0:
+            ens.mark_tangent(t)
     ens.write_frame(t, out_dir, packet_files)
 
 
@@ -891,6 +944,7 @@ class ReceiverLoop:
         pass
 
 
+@_ends_tangent
 def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_days, U_g, f, Cg, *,
                   out_dir="data", nsub=4, max_steps=None, seed=146, verbose=False, r_drag=0.1,
                   packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
@@ -901,6 +955,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                   trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20,
                   recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20,
                   refr_edges=None, refr_frac_bits=20, absfreq_edges=None, absfreq_frac_bits=20,
+                  tangent_edges=None, tangent_lag=1,
                   packet_method="leapfrog", packet_iterations=None):
     """qgsw_raytrace.m:1-180 with the PDE and the packets on the GPU.
 
@@ -1045,7 +1100,18 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     Returns a dict of run facts (dt, Nsteps, steps run, frames written,
     final t, spectrum_frames, map_frames, track_frames, kmap_frames,
     flow_frames, cond_frames, trans_frames, recycle_events, refr_frames,
-    absfreq_frames)."""
+    absfreq_frames, tangent_frames).
+    ``tangent_edges`` (needs ``spectrum_edges``; integrator="leapfrog",
+    packet_method="leapfrog" and no ``recycle_omega``, else ValueError): the
+    packets carry the tangent map M of the discrete step from the first packet
+    frame on (swrt_tangent_*: the leapfrog calls take the per-packet route; x
+    and k keep their bits) and every later packet frame records a tangent
+    frame over the growth classes ``tangent_edges`` (of s = |M|_F^2 / 4) by
+    the omega classes, then, with ``tangent_lag`` = m (default 1), re-marks
+    (M = I) after every m-th frame.  Written as tangent_hist.bin,
+    tangent_sums.bin, tangent_stats.bin, tangent_time.bin (t and t_mark per
+    frame) and tangent_geom.bin (PacketEnsemble.write_tangents); frame i
+    belongs to packet frame i + 1."""
     _flow_args(flow_spectrum, Npackets)
     spectrum_edges = _spectrum_args(spectrum_edges, packet_files, kmap_cells)
     map_args = _map_args(map_cells, map_frac_bits)
@@ -1058,6 +1124,8 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     absfreq_args = _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges)
     method_args = _packet_method_args(packet_method, packet_iterations, integrator)
     trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
+    tangent_args = _tangent_args(tangent_edges, tangent_lag, spectrum_edges, integrator, packet_method, recycle_omega,
+                                 Npackets)
     if trans_args is not None and Npackets <= 0:
         raise ValueError("the transition series needs packets")
     recycle_args = _recycle_args(recycle_omega, recycle_seed, recycle_every, recycle_frac_bits, ring_factors, f,
@@ -1140,6 +1208,10 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
         _begin_trans(ens, trans_args, spectrum_edges, out_dir, dt * (packet_step_start - 1), Npackets,
                      len(ring_factors))
         trans = trans_args[2] or 0
+    tangent = None  # (the lag; None: no tangent series)
+    if ens is not None and tangent_args is not None:  # (M = I beside the first packet frame; frames from the second on)
+        ens.begin_tangent(spectrum_edges, tangent_args[0], directory=out_dir, t=dt * (packet_step_start - 1))
+        tangent = tangent_args[1]
     recycle = 0  # (packet frames per recycle event; 0: no recycling)
     if ens is not None and recycle_args is not None:  # (events from the second packet frame on)
         ens.begin_recycle(recycle_args[0], seed=recycle_args[1], frac_bits=recycle_args[3], directory=out_dir,
@@ -1185,7 +1257,7 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                 if recycle and frames % recycle == 0:
                     ens.recycle(t)  # (before the frame: it holds no packet at or above the cut)
                 _save_frame(ens, t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames, refrs,
-                            group.last if absfreqs else None)
+                            group.last if absfreqs else None, tangent)
                 if flows:
                     model.record_flow_spectrum()
                 frames += 1
@@ -1208,6 +1280,9 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
     recycle_events = ens.write_recycle(out_dir) if recycle else 0
     refr_frames = ens.write_refrs(out_dir) if refrs else 0
     absfreq_frames = ens.write_absfreqs(out_dir) if absfreqs else 0
+    tangent_frames = ens.write_tangents(out_dir) if tangent is not None else 0
+    if tangent is not None:
+        ens.end_tangent()  # (the context goes back to the route its settings name)
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -1220,9 +1295,10 @@ def qgsw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_da
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
                 track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames,
                 trans_frames=trans_frames, recycle_events=recycle_events, refr_frames=refr_frames,
-                absfreq_frames=absfreq_frames)
+                absfreq_frames=absfreq_frames, tangent_frames=tangent_frames)
 
 
+@_ends_tangent
 def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_delay_Fr_days, U_g, f, Cg, *,
                         out_dir="data", nsub=5, max_steps=None, seed=5, verbose=False,
                         packet_intervals=1, integrator="leapfrog", fresh=True, ctx: Context | None = None,
@@ -1233,6 +1309,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                         trans_src_edges=None, trans_by=None, trans_lag=None, trans_frac_bits=20,
                         recycle_omega=None, recycle_seed=0, recycle_every=1, recycle_frac_bits=20,
                         refr_edges=None, refr_frac_bits=20, absfreq_edges=None, absfreq_frac_bits=20,
+                        tangent_edges=None, tangent_lag=1,
                         packet_method="leapfrog", packet_iterations=None):
     """qg2layersw_raytrace.m:1-247 with the PDE and the packets on the GPU
     (adaptive CFL :156-165, packets on layer 1 with u += shear_strength and
@@ -1247,7 +1324,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     ``trans_src_edges``, ``trans_by``, ``trans_lag``, ``trans_frac_bits``,
     ``recycle_omega``, ``recycle_seed``, ``recycle_every``,
     ``recycle_frac_bits``, ``refr_edges``, ``refr_frac_bits``,
-    ``absfreq_edges``, ``absfreq_frac_bits`` and a
+    ``absfreq_edges``, ``absfreq_frac_bits``, ``tangent_edges``,
+    ``tangent_lag`` and a
     sequence of factors as ``near_inertial_factor``: as in
     :func:`qgsw_raytrace`.
 
@@ -1271,6 +1349,8 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     absfreq_args = _absfreq_args(absfreq_edges, absfreq_frac_bits, spectrum_edges)
     method_args = _packet_method_args(packet_method, packet_iterations, integrator)
     trans_args = _trans_args(trans_src_edges, trans_by, trans_lag, trans_frac_bits, spectrum_edges, len(ring_factors))
+    tangent_args = _tangent_args(tangent_edges, tangent_lag, spectrum_edges, integrator, packet_method, recycle_omega,
+                                 Npackets)
     if trans_args is not None and Npackets <= 0:
         raise ValueError("the transition series needs packets")
     recycle_args = _recycle_args(recycle_omega, recycle_seed, recycle_every, recycle_frac_bits, ring_factors, f,
@@ -1346,6 +1426,10 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
         _begin_trans(ens, trans_args, spectrum_edges, out_dir, dt * (packet_step_start - 1), Npackets,
                      len(ring_factors))
         trans = trans_args[2] or 0
+    tangent = None  # (the lag; None: no tangent series)
+    if ens is not None and tangent_args is not None:  # (M = I beside the first packet frame; frames from the second on)
+        ens.begin_tangent(spectrum_edges, tangent_args[0], directory=out_dir, t=dt * (packet_step_start - 1))
+        tangent = tangent_args[1]
     recycle = 0  # (packet frames per recycle event; 0: no recycling)
     if ens is not None and recycle_args is not None:  # (events from the second packet frame on)
         ens.begin_recycle(recycle_args[0], seed=recycle_args[1], frac_bits=recycle_args[3], directory=out_dir,
@@ -1389,7 +1473,7 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
             if recycle and frames % recycle == 0:
                 ens.recycle(loop.t)  # (before the frame: it holds no packet at or above the cut)
             _save_frame(ens, loop.t, out_dir, spectrum, packet_files, maps, kmaps, conds, trans, frames, refrs,
-                        loop.group.last if absfreqs else None)
+                        loop.group.last if absfreqs else None, tangent)
             if flows:
                 model.record_flow_spectrum()  # (the committed qk at loop.t; the next step is only speculative)
             frames += 1
@@ -1407,6 +1491,9 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
     recycle_events = ens.write_recycle(out_dir) if recycle else 0
     refr_frames = ens.write_refrs(out_dir) if refrs else 0
     absfreq_frames = ens.write_absfreqs(out_dir) if absfreqs else 0
+    tangent_frames = ens.write_tangents(out_dir) if tangent is not None else 0
+    if tangent is not None:
+        ens.end_tangent()  # (the context goes back to the route its settings name)
     if flows:
         model.write_flow_spectrum(out_dir, first_time=dt * (packet_step_start - 1))
     flow_frames = frames if flow_spectrum else 0
@@ -1421,4 +1508,4 @@ def qg2layersw_raytrace(nx, Npackets, near_inertial_factor, T_Fr_days, packet_de
                 packet_step_start=packet_step_start, spectrum_frames=spectrum_frames, map_frames=map_frames,
                 track_frames=track_frames, kmap_frames=kmap_frames, flow_frames=flow_frames, cond_frames=cond_frames,
                 trans_frames=trans_frames, recycle_events=recycle_events, refr_frames=refr_frames,
-                absfreq_frames=absfreq_frames)
+                absfreq_frames=absfreq_frames, tangent_frames=tangent_frames)
